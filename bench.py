@@ -12,6 +12,12 @@ relays rank 0's single JSON line and exits with the ranks' exit code (any rank f
 A step = forward + losses + backward + gradient all-reduce (N>1) + Adam + weight repack on one synthetic batch
 that is resident in HBM before the timed region. Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds the legs rank 0 runs after the timed
+region: the dominant-kernel and weight-gradient rooflines, the kernel families inside the step, the CPU baseline and the
+decode / render / f32 build / bf16-vs-f32 / PRN / RetinaNet / joint-inference / host-fed legs (`--no-roofline` and
+`--no-cpu-baseline` leave out either half). `--dump-outputs DIR` writes what the last timed step computed as float32 .npy files
+(`dump_outputs`); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 `--dry-run-cpu` (tests): the same launcher, rendezvous, two-phase gradient exchange, barrier and max-over-ranks timing
 on CPU tensors over gloo - no kernel runs, the line says "dry_run": true and is not a measurement.
 """
@@ -32,6 +38,24 @@ if ROOT not in sys.path:
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
 GMAC_PER_IMAGE = 17.946     # forward MACs per 512x512 image
+DUMP_LOGITS_SAMPLE = 1 << 20   # logits elements --dump-outputs keeps (4 MB; the whole tensor is 38 MB at bs32 @ 512x512)
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last timed step computed, as float32 `<name>.npy` under out_dir - the f32[8] losses step()
+    returned, the network's flat arenas after it (variables after the Adam update, the gradient that update applied, batch-norm
+    moving statistics) and a fixed seeded sample (sorted flat indices) of the f32 heatmap logits of its forward pass. About 48 MB
+    in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    net = trainer.net
+    logits = trainer._static_bufs()["logits"].reshape(-1)
+    if logits.numel() > DUMP_LOGITS_SAMPLE:
+        idx = np.sort(np.random.RandomState(0).choice(logits.numel(), DUMP_LOGITS_SAMPLE, replace=False))
+        logits = logits[torch.from_numpy(idx).to(logits.device)]
+    arrays = {"losses": trainer._losses, "theta": net.theta, "grad": net.grad, "moving": net.moving, "logits_sample": logits}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def _free_port():
@@ -199,8 +223,11 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run rank 0's roofline, CPU-baseline and other measurement legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the legs beside it")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline legs")
     ap.add_argument("--no-fuse-stem-stats", action="store_true", help="A/B: batch-norm statistics of the stem output as a separate pass")
     ap.add_argument("--no-fuse-conv-bn", action="store_true", help="A/B: batch-norm reductions behind the 3x3 data gradients as separate passes")
     ap.add_argument("--dry-run-cpu", action="store_true", help="rehearse launcher + exchange on CPU over gloo (tests)")
@@ -305,10 +332,14 @@ def main():
         # the launch stream may run the optimizer graph (rank 0's view)
         ex = sorted(a.elapsed_time(b) for a, b in trainer.comm_events[-args.steps:])
         out["config"]["exposed_allreduce_ms_per_step"] = {"median": round(ex[len(ex) // 2], 3), "max": round(ex[-1], 3)}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer)     # before any leg below steps the trainer again
     if rank == 0 and not args.no_roofline:
-        from bench_legs import dominant_kernel_roofline, whole_step_mfma_fraction
-        out["roofline"] = dominant_kernel_roofline(net, args.batch, args.size, dt, b=trainer._static_bufs())
+        from bench_legs import whole_step_mfma_fraction
         out["config"]["step_mfma_frac_of_peak"] = whole_step_mfma_fraction(args.batch, args.size, dt_s / args.steps)
+    if rank == 0 and args.full and not args.no_roofline:
+        from bench_legs import dominant_kernel_roofline
+        out["roofline"] = dominant_kernel_roofline(net, args.batch, args.size, dt, b=trainer._static_bufs())
         from bench_legs import conv_wgrad_roofline
         out["roofline_wgrad"] = conv_wgrad_roofline(net, args.batch, args.size, dt, b=trainer._static_bufs())   # the largest family by time
         if dt == torch.bfloat16:
@@ -323,7 +354,7 @@ def main():
             # STEPS the trainer, and with more ranks a step contains the gradient exchange - rank 0 must not enter a collective alone
             if world == 1:
                 out["north_star_in_step"] = in_step_families(trainer, feats, labels, args.batch, args.size)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from bench_legs import cpu_baseline, decode_benchmark, render_benchmark, prn_benchmark
         from bench_legs import host_fed_rate
         out["host_fed"] = host_fed_rate(trainer, feats, labels)     # PCIe-inclusive rate (reported beside `value`, never as it)

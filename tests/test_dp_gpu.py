@@ -186,13 +186,13 @@ if __name__ == "__main__":
 
 
 def test_bench_two_rank_path_rehearsed_on_one_device(cuda):
-    """`bench.py --gpus 2 --rehearse-shared-device`: the launcher, both ranks of the REAL GPU path (four graphs around three
+    """`bench.py --gpus 2 --rehearse-shared-device --full`: the launcher, both ranks of the REAL GPU path (four graphs around three
     exchanges, barrier + max-over-ranks timing, per-rank step times) and every leg rank 0 runs alone after the timed region, with
     both ranks on device 0 and the exchange over gloo. A leg that stepped the trainer on rank 0 alone once entered the all-reduce
     there and would have hung the first real multi-rank run at the final barrier - this is the run that shows it."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-shared-device", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600,
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
