@@ -5,12 +5,12 @@ The reference keeps its state in TF checkpoints: `train_keypoints.py:55` warm-st
 `<var>/Adam`, `<var>/Adam_1`, `beta1_power`, `beta2_power`, `global_step`), `create_pb.py:170-185` freezes the variables
 into the graph. Reading a TF checkpoint needs TensorFlow, which is not in this image: `tools/tf_checkpoint_to_npz.py` is the
 one-off converter to run where it is (`tf.train.load_checkpoint` -> `np.savez`, names unchanged); everything here works on
-the resulting `.npz` - HWIO kernels, [3,3,C,1] depthwise kernels, f32 - for KeypointNet and PoseResidualNet alike.
+the resulting `.npz` - HWIO kernels, [3,3,C,1] depthwise kernels, f32 - for every model on model_state.ModelState
+(KeypointNet, PersonDetectorNet, PoseResidualNet) alike.
 """
 import os
 
 import numpy as np
-import torch
 
 ADAM_SLOTS = ("Adam", "Adam_1")   # tf.train.AdamOptimizer: first / second moment slot names
 
@@ -20,16 +20,14 @@ def slot_name(var, slot):
 
 
 def save_npz(path, net, with_optimizer=True, beta1=0.9, beta2=0.999):
-    """Everything `tf.train.Saver` would write for `net` (a KeypointNet or PoseResidualNet): variables, moving statistics,
-    and (with_optimizer) the Adam slots, beta powers and global_step."""
+    """Everything `tf.train.Saver` would write for `net` (a model_state.ModelState): variables, moving statistics, and
+    (with_optimizer) the Adam slots, beta powers and global_step."""
     out = dict(net.state_dict())
     if with_optimizer:
         step = int(net.global_step.item())
-        views = net._train_arena if hasattr(net, "_train_arena") else net._arena
         for slot, flat in enumerate((net.adam_m, net.adam_v)):
-            for k, v in views.views(flat).items():
-                v = net.unpad(k, v) if hasattr(net, "unpad") else v        # (reference shapes: net.internal_shapes)
-                out[slot_name(k, slot)] = v.detach().cpu().numpy().copy()
+            for k, v in net._train_arena.views(flat).items():
+                out[slot_name(k, slot)] = net.unpad(k, v).detach().cpu().numpy().copy()    # (reference shapes)
         out["global_step"] = np.int64(step)
         # tf.train.AdamOptimizer creates the powers as beta and multiplies them after every apply: after `step` applies the
         # checkpoint holds beta^(step+1) (consistent with csrc/optim.hip using t = global_step + 1)
@@ -54,7 +52,7 @@ def load_npz(path, net, scopes=None, strict=True, with_optimizer=True):
     warm start is scopes=("MobilenetV1/",), train_keypoints.py:55); strict applies to the selected variables only.
     Returns the list of restored names."""
     values = _read(path)
-    own = set(net.vars) | set(getattr(net, "stats", {}))
+    own = set(net.vars) | set(net.stats)
     sel = {k: v for k, v in values.items() if k in own and (scopes is None or any(k.startswith(s) for s in scopes))}
     if strict:
         want = [k for k in own if scopes is None or any(k.startswith(s) for s in scopes)]
@@ -64,18 +62,11 @@ def load_npz(path, net, scopes=None, strict=True, with_optimizer=True):
     net.load_state_dict(sel, strict=False)
     restored = sorted(sel)
     if with_optimizer and "global_step" in values:
-        views = net._train_arena if hasattr(net, "_train_arena") else net._arena
         for slot, flat in enumerate((net.adam_m, net.adam_v)):
-            for k, dst in views.views(flat).items():
+            for k, dst in net._train_arena.views(flat).items():
                 name = slot_name(k, slot)
                 if name in values and (scopes is None or any(k.startswith(s) for s in scopes)):
-                    v = np.asarray(values[name], np.float32)
-                    if hasattr(net, "unpad") and k in getattr(net, "_pads", {}):
-                        dst.zero_()
-                        dst = net.unpad(k, dst)
-                    if tuple(v.shape) != tuple(dst.shape):
-                        raise ValueError(f"{name}: shape {v.shape} != {tuple(dst.shape)}")
-                    dst.copy_(torch.from_numpy(v))
+                    net._copy_in(k, dst, values[name], label=name)
                     restored.append(name)
         if scopes is None:
             step = int(values["global_step"])

@@ -162,6 +162,5 @@ class Detector:
         return outs
 
     def _variable_versions(self):
-        prn = self.assigner.net if self.assigner is not None else None
         return (self.net.var_version, self.retinanet.var_version if self.retinanet is not None else -1,
-                getattr(prn, "var_version", -1))
+                self.assigner.net.var_version if self.assigner is not None else -1)

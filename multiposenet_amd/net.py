@@ -22,6 +22,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import ACT_NONE, ACT_RELU, ACT_RELU6
+from .model_state import ModelState, _Arena, is_trainable, resolve_device  # noqa: F401 (_Arena, is_trainable: bench.py, tests)
 
 NUM_KEYPOINTS = 17   # detector/constants.py:10
 DOWNSAMPLE = 4       # detector/constants.py:13
@@ -103,10 +104,6 @@ def internal_shapes(depth_multiplier=1.0):
     return shapes, pads
 
 
-def is_trainable(name):
-    return not (name.endswith("moving_mean") or name.endswith("moving_variance"))
-
-
 def initial_values(seed=0, depth_multiplier=1.0):
     """Seeded initial values following the reference's initialiser families: variance scaling for conv
     kernels (layer_utils.py:37), N(0,1e-4) `heatmaps/kernel` and bias -log(99)x17 + 0
@@ -140,35 +137,6 @@ def backbone_deep_begin_of(arena, first_block=DP_DEEP_FROM_BLOCK):
     return arena.offsets[f"MobilenetV1/Conv2d_{first_block}_depthwise/depthwise_weights"][0]
 
 
-class _Arena:
-    """Flat f32 device arena with named, 16-byte aligned views."""
-
-    def __init__(self, shapes, device):
-        self.offsets = OrderedDict()
-        off = 0
-        for name, shape in shapes.items():
-            n = int(np.prod(shape))
-            self.offsets[name] = (off, n, tuple(shape))
-            off += (n + 3) // 4 * 4
-        self.size = off
-        self.device = device
-
-    def new(self):
-        return torch.zeros(self.size, dtype=torch.float32, device=self.device)
-
-    def views(self, flat):
-        return OrderedDict((k, flat[o:o + n].view(shape)) for k, (o, n, shape) in self.offsets.items())
-
-
-class _Conv:
-    """One dense conv: reference variable + packed MFMA operands."""
-
-    def __init__(self, name, w, dw, dtype):
-        self.name, self.w, self.dw = name, w, dw
-        self.ksize, _, self.cin, self.cout = w.shape
-        self.packed = ops.PackedConv(w, dtype)
-
-
 def backbone_grad_end_of(arena):
     """Offset in a flat arena of the trainable variables where the backbone's (`MobilenetV1/*`) end."""
     end = 0
@@ -181,18 +149,15 @@ def backbone_grad_end_of(arena):
 @ops._lib.device_guarded("_init", "load_state_dict", "repack_weights", "prepare_inference", "forward", "predict",
                          "backbone_forward", "subnet_forward", "compute_losses", "backward", "add_weight_decay_gradients",
                          "add_weight_decay_loss", "optimizer_step")
-class KeypointNet:
+class KeypointNet(ModelState):
     def __init__(self, values=None, depth_multiplier=1.0, dtype=torch.bfloat16, device="cuda:0", seed=0):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.dtype, self.device, self.dm = dtype, dev, depth_multiplier
+        self.dtype, self.device, self.dm = dtype, resolve_device(device), depth_multiplier
         self._init(values, depth_multiplier, dtype, seed)
 
     def _init(self, values, depth_multiplier, dtype, seed):
-        shapes, self._pads = internal_shapes(depth_multiplier)
+        shapes, pads = internal_shapes(depth_multiplier)
         # every batch-norm width a multiple of 16 (the stem's is padded to one inside the arena): the matrix-core kernels are
         # exercised - end to end against the oracle - at such widths only (0.25, 0.5, 0.75, 1.0, ...); 0.375 would hand 24- and
         # 48-channel pointwise layers to them
@@ -200,18 +165,7 @@ class KeypointNet:
             if n.endswith("gamma") and (s[0] % 16 != 0):
                 raise ValueError(f"depth_multiplier={depth_multiplier}: {n} has {s[0]} channels; every layer behind the stem "
                                  f"must be a multiple of 16 channels wide (depth multipliers that are multiples of 0.25)")
-        self._train_arena = _Arena(OrderedDict((k, v) for k, v in shapes.items() if is_trainable(k)), self.device)
-        self._stat_arena = _Arena(OrderedDict((k, v) for k, v in shapes.items() if not is_trainable(k)), self.device)
-        self.theta = self._train_arena.new()
-        self.grad = self._train_arena.new()
-        self.adam_m = self._train_arena.new()
-        self.adam_v = self._train_arena.new()
-        self.moving = self._stat_arena.new()
-        self.vars = self._train_arena.views(self.theta)
-        self.grads = self._train_arena.views(self.grad)
-        self.stats = self._stat_arena.views(self.moving)
-        self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._init_state(shapes, pads=pads)
         self.load_state_dict(values if values is not None else initial_values(seed, depth_multiplier))
         self._build_layers()
         self._bufs = {}
@@ -219,65 +173,7 @@ class KeypointNet:
                                       # kernels already fill the chip, concurrent ones only contend; see backward)
         self._wstream = None
 
-    # ------------------------------------------------------------------ variables
-    def state_dict(self):
-        """{reference variable name: numpy array} (HWIO kernels, as in a TF checkpoint)."""
-        out = OrderedDict()
-        for k, v in list(self.vars.items()) + list(self.stats.items()):
-            out[k] = self.unpad(k, v).detach().cpu().numpy().copy()
-        return out
-
-    def unpad(self, name, t):
-        """The reference-shaped part of an arena view (variable, gradient or Adam slot) of `name` (internal_shapes)."""
-        if name in self._pads:
-            axis, n = self._pads[name]
-            return t.narrow(axis, 0, n)
-        return t
-
-    def load_state_dict(self, values, strict=True):
-        for k, v in values.items():
-            dst = self.vars.get(k, self.stats.get(k))
-            if dst is None:
-                if strict:
-                    raise KeyError(f"unknown variable {k}")
-                continue
-            v = np.asarray(v, dtype=np.float32)
-            if k in self._pads:
-                dst.zero_()                      # the pad: zeros, gamma included (see internal_shapes)
-                dst = self.unpad(k, dst)
-            if tuple(v.shape) != tuple(dst.shape):
-                raise ValueError(f"{k}: shape {v.shape} != {tuple(dst.shape)}")
-            dst.copy_(torch.from_numpy(v))
-        if strict:
-            missing = [k for k in list(self.vars) + list(self.stats) if k not in values]
-            if missing:
-                raise KeyError(f"missing variables: {missing[:5]}...")
-        self.mark_variables_changed()
-        if hasattr(self, "convs"):
-            self.repack_weights()
-
-    def mark_variables_changed(self):
-        """Variables or moving statistics changed: cached inference affines are stale and `var_version` moves (users that
-        replay captured device work - inference/detector.py - compare it). Every method of this object that changes them
-        calls this; so must whoever changes them from outside: a replayed hipGraph of a train step (train.Trainer.step does),
-        a direct write into `vars` / `stats`."""
-        self.var_version = getattr(self, "var_version", 0) + 1
-        self._infer_clean = False
-
-    def _bn(self, prefix, act):
-        bn = ops.BNState(self.vars[prefix + "/gamma"], self.vars[prefix + "/beta"], self.stats[prefix + "/moving_mean"],
-                         self.stats[prefix + "/moving_variance"], act)
-        bn.dgamma, bn.dbeta = self.grads[prefix + "/gamma"], self.grads[prefix + "/beta"]
-        bn.name = prefix
-        return bn
-
-    def _conv(self, name):
-        c = _Conv(name, self.vars[name], self.grads[name], self.dtype)
-        self.convs.append(c)
-        return c
-
     def _build_layers(self):
-        self.convs = []
         self.stem_w = self.vars["MobilenetV1/Conv2d_0/weights"]
         self.stem_dw = self.grads["MobilenetV1/Conv2d_0/weights"]
         self.stem_bn = self._bn("MobilenetV1/Conv2d_0/BatchNorm", ACT_RELU6)

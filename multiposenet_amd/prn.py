@@ -14,7 +14,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call, ptr, stream_ptr
-from .net import _Arena
+from .model_state import ModelState, resolve_device
 
 NUM_KEYPOINTS = 17
 CROP_SIZE = (56, 36)     # detector/constants.py
@@ -41,13 +41,15 @@ def initial_values(seed=0, **kw):
 
 @_lib.device_guarded("_init", "load_state_dict", "refresh_operands", "forward", "loss", "predict", "backward",
                      "optimizer_step", "train_step")
-class PoseResidualNet:
+class PoseResidualNet(ModelState):
+    ignore_unknown = True      # a PRN checkpoint may hold the Adam slots too (inference/detector.py loads it as variables)
+
     def __init__(self, values=None, batch=128, h=CROP_SIZE[0], w=CROP_SIZE[1], c=NUM_KEYPOINTS, hidden=HIDDEN,
                  dtype=torch.bfloat16, device="cuda:0", seed=0, share_variables_of=None):
         """share_variables_of: another PoseResidualNet of the same geometry and dtype - this instance then runs at ITS OWN
         batch size on the OTHER's variables, Adam slots, step counter and operand copies (one model, several batch
         sizes: a partial last batch, EVAL at batch 1 after TRAIN at batch 128)."""
-        self.device = torch.device(device) if share_variables_of is None else share_variables_of.device
+        self.device = resolve_device(device) if share_variables_of is None else share_variables_of.device
         self._init(values, batch, h, w, c, hidden, dtype, seed, share_variables_of)
 
     def for_batch(self, batch):
@@ -76,14 +78,7 @@ class PoseResidualNet:
         self.loss_scale = float(2 ** int(np.floor(np.log2(batch * h * w * c)))) if dtype == torch.float16 else 1.0
         dev, B, n = self.device, self.B, self.n
         if share is None:
-            shapes = variable_shapes(h, w, c, hidden)
-            self._arena = _Arena(shapes, self.device)
-            self.theta, self.grad = self._arena.new(), self._arena.new()
-            self.adam_m, self.adam_v = self._arena.new(), self._arena.new()
-            self.vars, self.grads = self._arena.views(self.theta), self._arena.views(self.grad)
-            self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
-            self.hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
-            self.load_state_dict(values if values is not None else initial_values(seed, h=h, w=w, c=c, hidden=hidden))
+            self._init_state(variable_shapes(h, w, c, hidden))
             W1, W2 = self.vars["PRN/fc1/weights"], self.vars["PRN/fc2/weights"]
             # operand copies in the storage dtype: W1 [n,1024] and W2 [1024,n] as stored (written by the Adam kernel itself,
             # mpn_adam_step_cast), W2^T [n,1024] (one transposing pass per step)
@@ -94,18 +89,18 @@ class PoseResidualNet:
             self.w2t_op = torch.empty((n, hidden), dtype=dtype, device=dev) if dtype == torch.float32 else None
             self._adam_cast = None
             if dtype != torch.float32:
-                o1, n1, _ = self._arena.offsets["PRN/fc1/weights"]
-                o2, n2, _ = self._arena.offsets["PRN/fc2/weights"]
+                o1, n1, _ = self._train_arena.offsets["PRN/fc1/weights"]
+                o2, n2, _ = self._train_arena.offsets["PRN/fc2/weights"]
                 self._adam_cast = ops.AdamCastJobs([(o1, n1, self.w1_op), (o2, n2, self.w2_op)])
-            self._siblings = {self.valid: self}
+            self._siblings = {}
+            # (and the operand copies from them: _variables_loaded)
+            self.load_state_dict(values if values is not None else initial_values(seed, h=h, w=w, c=c, hidden=hidden))
         else:
             if (share.h, share.w, share.c, share.hidden, share.dtype) != (h, w, c, hidden, dtype):
                 raise ValueError("share_variables_of: geometry / dtype differ")
-            for a in ("_arena", "theta", "grad", "adam_m", "adam_v", "vars", "grads", "global_step", "hyper", "w1_op",
-                      "w2_op", "w2t_op", "_adam_cast", "_siblings"):
-                setattr(self, a, getattr(share, a))
-            self._siblings[self.valid] = self
+            self.share_variables(share, "w1_op", "w2_op", "w2t_op", "_adam_cast", "_siblings")
             # the fp16 loss scale is a function of the batch size; Adam divides by the scale of the instance that steps
+        self._siblings[self.valid] = self
         f32 = torch.float32
         self.xt = torch.empty((n, B), dtype=dtype, device=dev)            # X^T
         self.x_op = torch.empty((B, n), dtype=dtype, device=dev)          # X in the storage dtype (fc1 wgrad operand)
@@ -133,26 +128,8 @@ class PoseResidualNet:
         # fc2 forward: K = 1024 rows, output [B, n] - one slab (the output itself) in the 16-bit builds; the f32 kernel splits K
         self._fc2_parts = ops.conv_wgrad_num_parts(1, 1, hidden, B, n, 1, dtype)
         self.fc2_slab = torch.empty(self._fc2_parts * B * n, dtype=f32, device=dev) if self._fc2_parts != 1 else None
-        if share is None:
-            self.refresh_operands()
 
     # ---------------------------------------------------------------- state
-    def state_dict(self):
-        return OrderedDict((k, v.detach().cpu().numpy().copy()) for k, v in self.vars.items())
-
-    def load_state_dict(self, values, strict=True):
-        for k, v in self.vars.items():
-            if k not in values:
-                if strict:
-                    raise KeyError(f"missing variable {k}")
-                continue
-            a = np.asarray(values[k], np.float32)
-            if a.shape != tuple(v.shape):
-                raise ValueError(f"{k}: shape {a.shape} != {tuple(v.shape)}")
-            v.copy_(torch.from_numpy(a))
-        if hasattr(self, "w2t_op"):
-            self.refresh_operands()
-
     def refresh_operands(self, casts=True):
         """Operand copies of the f32 masters. casts=False (after an optimizer step): the Adam kernel has already written the
         two plain casts (mpn_adam_step_cast) - in the 16-bit builds nothing remains to refresh."""
@@ -163,6 +140,9 @@ class PoseResidualNet:
             call("mpn_cast", ptr(W2), f32c, ptr(self.w2_op), dc, W2.numel(), stream_ptr())
         if self.w2t_op is not None:
             call("mpn_transpose_cast", ptr(W2), f32c, ptr(self.w2t_op), dc, self.hidden, self.n, stream_ptr())
+
+    def _variables_loaded(self):
+        self.refresh_operands()
 
     # ---------------------------------------------------------------- forward / loss / backward
     def _kgemm(self, at, bmat, out):
@@ -242,6 +222,7 @@ class PoseResidualNet:
                                grad_scale=1.0 / self.loss_scale, clip=float("inf"))
         else:
             ops.adam_step(self.theta, self.grad, self.adam_m, self.adam_v, self.hyper, grad_scale=1.0 / self.loss_scale, clip=float("inf"))
+        self.mark_variables_changed()
         self.refresh_operands(casts=False)
 
     def train_step(self, x, labels, initial_learning_rate, num_steps):

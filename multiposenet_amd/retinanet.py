@@ -22,7 +22,8 @@ import torch
 
 from . import _lib, ops
 from ._lib import ACT_RELU, call, ptr, stream_ptr
-from .net import KeypointNet, _Arena, depth
+from .model_state import ModelState, resolve_device
+from .net import KeypointNet, depth
 
 DEPTH = 128                 # retinanet.py:10
 TOWER_DEPTH = 64            # retinanet.py:46
@@ -64,10 +65,6 @@ def head_variable_shapes(depth_multiplier=1.0):
         s[f"{net}/{out_name}/kernel"] = (3, 3, TOWER_DEPTH, cout)
         s[f"{net}/{out_name}/bias"] = (cout,)
     return s
-
-
-def _trainable(name):
-    return not (name.endswith("moving_mean") or name.endswith("moving_variance"))
 
 
 _BN0 = tuple(f"{net}/batch_norm_0_for_level_" for net in ("box_net", "class_net"))
@@ -133,37 +130,6 @@ def generate_anchors(image_height, image_width):
     return anchors.astype(f), shapes
 
 
-class _Conv:
-    """A dense conv of the head: reference variable view (+ gradient view) and packed MFMA operands. `as1x1`: a 3x3 HWIO
-    kernel used as the [1,1,9*Cin,Cout] matrix behind mpn_patchify3x3s2 (the stride-2 convolutions)."""
-
-    def __init__(self, name, w, dw, dtype, as1x1=False, pad_cout=0):
-        self.name, self.w, self.dw = name, w, dw
-        k, _, cin, cout = w.shape
-        self.pad = None
-        if pad_cout:      # class_net/logits has 6 output channels: the kernels want multiples of 8 - two zero columns
-            self.pad = torch.zeros((k, k, cin, pad_cout), dtype=torch.float32, device=w.device)
-            self.dpad = torch.zeros_like(self.pad)
-            cout = pad_cout
-        src = self.pad if self.pad is not None else w
-        if as1x1:
-            src = src.view(1, 1, k * k * cin, cout)
-        self.ksize, self.cin, self.cout = src.shape[0], src.shape[2], src.shape[3]
-        self.src = src
-        self.refresh_pad()
-        self.packed = ops.PackedConv(src, dtype)
-
-    def refresh_pad(self):
-        if self.pad is not None:
-            self.pad[..., :self.w.shape[3]].copy_(self.w)
-
-    def repack(self):
-        if getattr(self, "packed_unused", False):
-            return
-        self.refresh_pad()
-        self.packed.repack()
-
-
 class _MergedConv:
     """The first convolutions of the two towers as one: HWIO kernels side by side along the output channels (a staging tensor
     refreshed with the variables), packed for the forward pass and for the data gradient. The weight gradients stay per tower."""
@@ -192,14 +158,12 @@ class _MergedConv:
 
 @_lib.device_guarded("_init", "load_state_dict", "repack_weights", "forward", "create_targets", "compute_losses", "backward",
                      "optimizer_step", "train_step", "predict", "nms", "head_forward")
-class PersonDetectorNet:
+class PersonDetectorNet(ModelState):
     def __init__(self, backbone_values=None, head_values=None, depth_multiplier=1.0, dtype=torch.bfloat16, device="cuda:0", seed=0,
                  backbone=None):
         """backbone: a KeypointNet whose MobileNet this detector SHARES (the joint inference graph of create_pb.py:64-71 runs
         one backbone under the keypoint subnet and the RetinaNet head) instead of building its own frozen copy."""
-        dev = torch.device(device) if backbone is None else backbone.device
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = resolve_device(device) if backbone is None else backbone.device
         if backbone is not None:
             dtype, depth_multiplier = backbone.dtype, backbone.dm
         self.device, self.dtype, self.dm = dev, dtype, depth_multiplier
@@ -211,21 +175,7 @@ class PersonDetectorNet:
         if backbone_values is not None:
             self.backbone.load_state_dict({k: v for k, v in backbone_values.items() if k.startswith("MobilenetV1/")}, strict=False)
         shapes = head_variable_shapes(self.dm)
-        order = _arena_order(shapes)
-        self._train_arena = _Arena(OrderedDict((k, v) for k, v in order.items() if _trainable(k)), self.device)
-        self._stat_arena = _Arena(OrderedDict((k, v) for k, v in order.items() if not _trainable(k)), self.device)
-        self.theta, self.grad = self._train_arena.new(), self._train_arena.new()
-        self.adam_m, self.adam_v = self._train_arena.new(), self._train_arena.new()
-        self.moving = self._stat_arena.new()
-
-        def named(arena, flat):      # (dictionaries in the reference's variable order, whatever the arena's)
-            v = arena.views(flat)
-            return OrderedDict((k, v[k]) for k in shapes if k in v)
-        self.vars, self.grads = named(self._train_arena, self.theta), named(self._train_arena, self.grad)
-        self.stats = named(self._stat_arena, self.moving)
-        self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._convs = []
+        self._init_state(shapes, order=_arena_order(shapes))
         self._wversion = 0
         self.fuse_conv_bn = True       # set before the first backward pass of a shape (the finalize tables are built once)
         # The first convolutions of the box and class towers read the same tensor (box_predictor.py:101-103 under both scopes): ONE
@@ -238,58 +188,13 @@ class PersonDetectorNet:
         # flag is host state, a replayed hipGraph of a train step cannot clear it
         self.cache_inference_affine = False
         self._infer_clean = False
-        self.var_version = 0
         self.backbone.cache_inference_affine = True     # frozen here: its inference affines change only with its variables
         self._l2 = None
         self._wd = None
-        self._built = False
         self.tower0m = None
         self.load_state_dict(head_values if head_values is not None else initial_head_values(seed, self.dm))
         self._build_layers()
         self._bufs = {}
-
-    # ------------------------------------------------------------------ variables
-    def state_dict(self):
-        out = OrderedDict()
-        for k, v in list(self.vars.items()) + list(self.stats.items()):
-            out[k] = v.detach().cpu().numpy().copy()
-        return out
-
-    def load_state_dict(self, values, strict=True):
-        for k, v in values.items():
-            dst = self.vars.get(k, self.stats.get(k))
-            if dst is None:
-                if strict:
-                    raise KeyError(f"unknown variable {k}")
-                continue
-            v = np.asarray(v, dtype=np.float32)
-            if tuple(v.shape) != tuple(dst.shape):
-                raise ValueError(f"{k}: shape {v.shape} != {tuple(dst.shape)}")
-            dst.copy_(torch.from_numpy(v))
-        if strict:
-            missing = [k for k in list(self.vars) + list(self.stats) if k not in values]
-            if missing:
-                raise KeyError(f"missing variables: {missing[:5]}...")
-        self.mark_variables_changed()
-        if self._built:
-            self.repack_weights()
-
-    def mark_variables_changed(self):
-        """The head's variables or moving statistics changed (see KeypointNet.mark_variables_changed)."""
-        self.var_version = getattr(self, "var_version", 0) + 1
-        self._infer_clean = False
-
-    def _bn(self, prefix, act=ACT_RELU):
-        bn = ops.BNState(self.vars[prefix + "/gamma"], self.vars[prefix + "/beta"], self.stats[prefix + "/moving_mean"],
-                         self.stats[prefix + "/moving_variance"], act)
-        bn.dgamma, bn.dbeta = self.grads[prefix + "/gamma"], self.grads[prefix + "/beta"]
-        bn.name = prefix
-        return bn
-
-    def _conv(self, name, **kw):
-        c = _Conv(name, self.vars[name], self.grads[name], self.dtype, **kw)
-        self._convs.append(c)
-        return c
 
     def _build_layers(self):
         self.lateral = {l: self._conv(f"fpn/lateral{l}/kernel") for l in (5, 4, 3)}
@@ -314,7 +219,6 @@ class PersonDetectorNet:
         self.all_bn = [self.pre_p7_bn] + [self.p_bn[l] for l in LEVELS] + \
             [self.tower_bn[net][i][l] for net, _, _ in NETS for i in range(4) for l in LEVELS]
         self.tower0m = _MergedConv([self.tower[net][0] for net, _, _ in NETS], self.dtype) if self.merge_tower0 else None
-        self._built = True
 
     def _bn_pair(self, l):
         """batch_norm_0_for_level_l of the two towers as ONE 128-channel layer (box channels first): views over adjacent variables."""
@@ -333,7 +237,7 @@ class PersonDetectorNet:
 
     def repack_weights(self):
         self._wversion += 1
-        for c in self._convs:
+        for c in self.convs:
             c.repack()
         if self.tower0m is not None:
             self.tower0m.repack()
@@ -439,7 +343,7 @@ class PersonDetectorNet:
         # weight-gradient slabs: a conv shared by the five levels owns five consecutive regions -> ONE reduction job
         sites = []   # (conv, [(key, nparts)], n)
         merged0 = [self.tower[net][0] for net, _, _ in NETS] if self.merge_tower0 else []
-        for c in [c for c in self._convs if c not in merged0] + ([self.tower0m] if self.merge_tower0 else []):
+        for c in [c for c in self.convs if c not in merged0] + ([self.tower0m] if self.merge_tower0 else []):
             n = c.src.numel()
             if c is self.tower0m or c in self.tower["box_net"] or c in self.tower["class_net"] or c in self.out_conv.values():
                 # (the five levels' weight gradients come from ONE grid: ops.conv_bwd_weight_grouped)
