@@ -459,6 +459,65 @@ int mpn_heatmap_render(const int32_t* keypoints, const float* boxes, const int32
                        int B, int total_persons, int width, int height, int downsample, float* out,
                        void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * L2  keypoint input augmentation (the per-pixel half of the training / evaluation input pipeline).
+ * Replaces the image and mask operations of detector/input_pipeline/keypoints_detector_pipeline.py
+ * `augmentation` (:191-197: random_rotation.py:68-77, `randomly_crop_and_resize` :275-400,
+ * color_augmentations.py:10-69, `random_flip_left_right` :403-450) and `resize_keeping_aspect_ratio`
+ * (:200-272) for a batch of RAGGED uint8 sources in one launch. The host draws every random decision
+ * and fills one descriptor per image (multiposenet_amd/detector/input_pipeline/keypoint_augment.py);
+ * per output pixel (y, x), with p = flip ? W-1-x : x the position before the flip:
+ *
+ *   valid      p < valid_w and y < valid_h, else 0                        (pad_to_bounding_box, :243)
+ *   resize     legacy bilinear over the crop: in = out * scale (f32 in/out), lo = floor(in),
+ *              hi = min(lo+1, crop-1), top + (bottom-top)*y_lerp           (resize_images, :241, :363)
+ *   tap        rotated image at (crop_y + row, crop_x + col): ImageProjectiveTransform BILINEAR of
+ *              u8 * float32(1/255) with `transform`, corners floor / floor+1, 0 outside  (random_rotation.py:69)
+ *   colour     clip(v + color[c], 0, 1)                                    (color_augmentations.py:19-33)
+ *   grayscale  0.2989 r + 0.5870 g + 0.1140 b on all channels              (:35-38)
+ *   scale      clip(v * (u * (1.1f - 0.9f) + 0.9f), 0, 1),
+ *              u = (fmix32(seed ^ (idx * 0x9E3779B1)) >> 8) * 2^-24, idx = (y*W + p)*3 + c,
+ *              fmix32 = murmur3's finaliser                                (color_augmentations.py:47-69)
+ *   masks      training: crop_and_resize nearest of `window` over the rotated mask
+ *              (in = y1*(mh-1) + y*(y2-y1)*(mh-1)/(H/4-1), roundf, 0 outside; the rotation is
+ *              NEAREST with `mask_transform`, fill 0); evaluation (MPN_AUGMENT_EVAL): legacy
+ *              resize_nearest_neighbor min(floor(out * mask_scale), in-1) inside valid_m*, 0 outside
+ * Every float step is one IEEE round-to-nearest operation in that order (no contraction).
+ *
+ *   sources    concatenated uint8 RGB images [src_h, src_w, 3]; image b starts at byte src_offset
+ *   masks      concatenated np.packbits of [ceil(src_h/4), ceil(src_w/4), 2] (0 loss, 1 segmentation)
+ *   descs      [B] mpn_keypoint_augment_desc, DEVICE, 16-byte aligned
+ *   images     [B,H,W,3] f32, 16-byte aligned; loss_masks, segmentation_masks [B,H/4,W/4] f32
+ * B >= 1, H % 4 == 0, W % 4 == 0. Every output element is written. Descriptor fields are the caller's
+ * to check (offsets and sizes inside the buffers); a source read outside an image's own rectangle
+ * returns 0. mpn_keypoint_augment_desc_bytes() = sizeof(mpn_keypoint_augment_desc), for bindings.
+ */
+enum {
+    MPN_AUGMENT_ROTATE = 1, MPN_AUGMENT_COLOR = 2, MPN_AUGMENT_GRAYSCALE = 4, MPN_AUGMENT_PIXEL_SCALE = 8,
+    MPN_AUGMENT_FLIP = 16, MPN_AUGMENT_EVAL = 32
+};
+#define MPN_KEYPOINT_AUGMENT_DESC_BYTES 192
+typedef struct mpn_keypoint_augment_desc {
+    int64_t src_offset, mask_offset;            /* byte offsets into sources / masks */
+    int32_t src_h, src_w, mask_h, mask_w;       /* mask_h = ceil(src_h/4), mask_w = ceil(src_w/4) */
+    int32_t crop_y, crop_x, crop_h, crop_w;     /* integer crop of the rotated image (begin, size) */
+    int32_t valid_h, valid_w, valid_mh, valid_mw; /* output region before the zero padding */
+    float transform[8], mask_transform[8];      /* inverse projective transforms (MPN_AUGMENT_ROTATE) */
+    float window[4];                            /* normalised crop window (ymin, xmin, ymax, xmax) for masks */
+    float scale_y, scale_x;                     /* f32(crop_h)/f32(valid_h), f32(crop_w)/f32(valid_w) */
+    float mask_scale_y, mask_scale_x;           /* f32(mask_h)/f32(valid_mh), likewise (MPN_AUGMENT_EVAL) */
+    float color[3];                             /* per-channel offsets (MPN_AUGMENT_COLOR) */
+    uint32_t seed;                              /* pixel-scale hash seed (MPN_AUGMENT_PIXEL_SCALE) */
+    int32_t flags;                              /* MPN_AUGMENT_* */
+    int32_t reserved[3];
+} mpn_keypoint_augment_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_keypoint_augment_desc) == MPN_KEYPOINT_AUGMENT_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_keypoint_augment_desc_bytes(void);
+int mpn_keypoint_augment(const uint8_t* sources, const uint8_t* masks, const void* descs, int B, int H, int W,
+                         float* images, float* loss_masks, float* segmentation_masks, mpn_stream_t stream);
+
 /* Skinny "NT" GEMM split over K: part[s][M][N] (f32, s < mpn_gemm_nt_num_parts(K)) = A[M][K] * B[N][K]^T over the s-th K range.
  * A, B 16-bit (MPN_BF16 / MPN_F16), row-major with K contiguous - the order the reference's variables already have for
  * dH = dPre2 * W2^T in the pose residual network (prn.py:11-33: fc2's data gradient), so no transposed copy of the weights is

@@ -8,3 +8,8 @@ DATA_FORMAT = 'channels_last'
 NUM_KEYPOINTS = 17
 # all heatmaps and masks are downsampled (detector/constants.py:13)
 DOWNSAMPLE = 4
+# if overlap of a box with an image is less than this value it is removed (detector/constants.py:37-38)
+OVERLAP_THRESHOLD = 0.1
+# input pipeline settings (detector/constants.py:21-25): record shuffle buffer and decode workers
+SHUFFLE_BUFFER_SIZE = 10000
+NUM_PARALLEL_CALLS = 12

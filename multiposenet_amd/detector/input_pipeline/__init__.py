@@ -1,2 +1,5 @@
-"""Label producers of the keypoint path (reference detector/input_pipeline/): only target-heatmap rendering is built."""
+"""The keypoint input pipeline (reference detector/input_pipeline/): TFRecord reading, host-side sampling of the
+augmentations, the on-device augmentation kernel and target-heatmap rendering."""
 from .heatmap_creation import get_heatmaps, get_heatmaps_batch, HeatmapRenderer  # noqa: F401
+from .tfrecord import read_records, parse_example, decode_keypoint_example  # noqa: F401
+from .keypoints_detector_pipeline import KeypointPipeline  # noqa: F401

@@ -4,11 +4,15 @@ steps/sec log every `log_step_count_steps`, evaluation every `throttle_secs`), r
 `model_dir` - on the HIP kernels, one process per GPU.
 
     python -m multiposenet_amd.train_keypoints [--synthetic] [--steps N] [--model-dir DIR] [--batch B] [--size S]
+                                               [--train-dataset DIR] [--val-dataset DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m multiposenet_amd.train_keypoints --synthetic
 
-Data: the reference reads TFRecords through tf.data (`KeypointPipeline`, out of scope here - SURVEY.md section 2); `train()`
-takes any iterator of (features, labels) dicts in the pipeline's output contract (keypoints_detector_pipeline.py:104-110),
-`--synthetic` feeds the on-device generator of multiposenet_amd.synthetic. Checkpoints are `.npz` files keyed by the TF
+Data: without `--synthetic` the TFRecord shards (`*.tfrecords`, else every file) of params['train_dataset'] /
+params['val_dataset'] (or --train-dataset / --val-dataset) are read by `KeypointPipeline`
+(multiposenet_amd.detector.input_pipeline: host-side decode and sampling, augmentation and heatmaps on the GPU), as in the
+reference's train_keypoints.py:26-45. `train()` takes any iterator of (features, labels) dicts in the pipeline's output
+contract (keypoints_detector_pipeline.py:104-110); `--synthetic` feeds the on-device generator of
+multiposenet_amd.synthetic. Checkpoints are `.npz` files keyed by the TF
 variable names (multiposenet_amd.checkpoint), `model.ckpt-<step>.npz`, like the estimator's `model.ckpt-<step>`.
 """
 import argparse
@@ -149,9 +153,19 @@ def synthetic_batches(batch_size, height, width, device=None, distinct=8):
         i += 1
 
 
+def dataset_files(path):
+    """The shards of a dataset directory: `*.tfrecords`, or every file when there are none."""
+    if os.path.isfile(path):
+        return [path]
+    files = sorted(glob.glob(os.path.join(path, "*.tfrecords")))
+    return files or sorted(f for f in glob.glob(os.path.join(path, "*")) if os.path.isfile(f))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--synthetic", action="store_true", help="train on generated batches (no TFRecord reader in this build)")
+    ap.add_argument("--synthetic", action="store_true", help="train on generated batches instead of TFRecords")
+    ap.add_argument("--train-dataset", default=None, help="directory of training TFRecords (default: PARAMS)")
+    ap.add_argument("--val-dataset", default=None, help="directory of evaluation TFRecords (default: PARAMS)")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--model-dir", default=None)
     ap.add_argument("--batch", type=int, default=None)
@@ -165,15 +179,29 @@ def main():
         params["batch_size"] = args.batch
     if args.size:
         params["image_size"] = (args.size, args.size)
+    if args.train_dataset:
+        params["train_dataset"] = args.train_dataset
+    if args.val_dataset:
+        params["val_dataset"] = args.val_dataset
     if not args.synthetic:
-        raise SystemExit("this build has no TFRecord reader (SURVEY.md section 2: input pipelines are out of scope): pass --synthetic, "
-                         "or call multiposenet_amd.train_keypoints.train(PARAMS, your_batch_iterator)")
+        train_files, val_files = dataset_files(params["train_dataset"]), dataset_files(params["val_dataset"])
+        if not train_files:
+            raise SystemExit(f"no TFRecord files under {params['train_dataset']!r}: pass --train-dataset DIR "
+                             "(tools/make_toy_tfrecords.py writes a small one), or --synthetic")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from .parallel import init_distributed
         _, local_rank, _ = init_distributed()
         torch.cuda.set_device(local_rank)
     h, w = params["image_size"]
-    train(params, lambda: synthetic_batches(params["batch_size"], h, w), max_steps=args.steps)
+    if args.synthetic:
+        train(params, lambda: synthetic_batches(params["batch_size"], h, w), max_steps=args.steps)
+    else:
+        from .detector.input_pipeline import KeypointPipeline
+        val = (lambda: KeypointPipeline(val_files, False, params).batches()) if val_files else None
+        step = train(params, lambda: KeypointPipeline(train_files, True, params).batches(), val_batches=val,
+                     max_steps=args.steps)
+        if val is not None:
+            evaluate(params, val, step=step)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
 
