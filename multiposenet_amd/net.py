@@ -169,9 +169,6 @@ class KeypointNet(ModelState):
         self.load_state_dict(values if values is not None else initial_values(seed, depth_multiplier))
         self._build_layers()
         self._bufs = {}
-        self.overlap_wgrad = False    # opt-in: weight gradients on a second HIP stream (measured 4% SLOWER at bs32: the
-                                      # kernels already fill the chip, concurrent ones only contend; see backward)
-        self._wstream = None
 
     def _build_layers(self):
         self.stem_w = self.vars["MobilenetV1/Conv2d_0/weights"]
@@ -212,12 +209,9 @@ class KeypointNet(ModelState):
         ob, nb, _ = self._train_arena.offsets["heatmaps/bias"]
         assert ob == ok + nk, "heatmaps/kernel and heatmaps/bias must be adjacent in the arena"
         self._head_grad = self.grad[ok:ob + nb]
-        self.fuse_dw_bn = True    # depthwise data gradients also reduce for the batch-norm they feed (mpn_dwconv_bwd_data_bn)
-        self.fuse_pw_wide = False # ... also on 128-channel layers (Conv2d_3_pointwise, lateral2): measured equal to the two-pass backward in the step
-        self.fuse_pw_apply = True # ... with the layer's own batch-norm apply pass folded in where the kernel takes it (Cin <= 32, Cout <= 64)
-        self.fuse_pw_bwd = True   # thin pointwise layers (Cin <= 64, Cout <= 128): weight + data gradient + reduction in one pass (mpn_conv1x1_bwd_fused)
-        self.fuse_dw_bwd_s2 = True  # ... and the stride-2 ones (even maps; the FPN lateral's gradient added inside: mpn_dwconv_bwd_fused_s2)
-        self.fuse_dw_bwd = True   # stride-1 depthwise layers: data gradient + that reduction + weight gradient in ONE walk (mpn_dwconv_bwd_fused)
+        # depthwise data gradients also reduce for the batch-norm they feed (mpn_dwconv_bwd_data_bn and the one-walk backward,
+        # mpn_dwconv_bwd_fused[_s2]); False: the separate reduction, the reference of the tests
+        self.fuse_dw_bn = True
         # ... and so do the subnet's 3x3 data gradients (mpn_conv_bwd_data_bn_grouped: bn1 under conv2's, p{l}_batch_norm under
         # conv1's); set before the first backward pass of a shape (the finalize tables are built once)
         self.fuse_conv_bn = True
@@ -231,7 +225,6 @@ class KeypointNet(ModelState):
         # wash (the separate 38 us statistics pass left the 134 MB stem output in the memory-side cache for the first depthwise
         # layer); behind the matrix-core kernel it is worth 15 us per step (same-box A/B, round 3)
         self.fuse_stem_stats = True
-        self.fuse_lateral_add = True   # ... and add the FPN lateral's gradient into c2..c4 (mpn_dwconv_bwd_data_add)
         self._build_pack_table()   # (outside any graph capture: it copies a small table to the device)
         self.all_bn = [self.stem_bn] + [b[k] for b in self.blocks for k in ("dw_bn", "pw_bn")] + \
             [self.p_bn[l] for l in (2, 3, 4, 5)] + [self.phi[l][k] for l in (2, 3, 4, 5) for k in ("bn1", "bn2")] + [self.final_bn]
@@ -562,18 +555,6 @@ class KeypointNet(ModelState):
         return ops.keypoint_loss(b["logits"], labels, ps, g["dlogits"] if g else None,
                                  [g["daux"][l] for l in (2, 3, 4, 5)] if g else None, b["loss_part"], b["losses"])
 
-    def _wgrad(self, fn):
-        """Run a weight-gradient launch sequence on the side stream: it only needs dy (just produced on the main stream)
-        and forward activations, so it overlaps the main stream's critical chain (bn_backward -> dgrad -> ...).
-        Captured into the hipGraph as a fork (event wait); `backward` joins once at the end."""
-        main = torch.cuda.current_stream()
-        if self._wstream is None:
-            fn()
-            return
-        self._wstream.wait_stream(main)
-        with torch.cuda.stream(self._wstream):
-            fn()
-
     @property
     def backbone_deep_begin(self):
         """Offset in the flat gradient arena where backbone block DP_DEEP_FROM_BLOCK begins (see backward)."""
@@ -589,27 +570,20 @@ class KeypointNet(ModelState):
         part=0: head + subnet + FPN only (their gradients are final when it returns); part=1: backbone blocks 13..7, after
         part 0; part=2: blocks 6..1 and the stem, after part 1; None: all three. Data-parallel training all-reduces the
         part-0 gradients while part 1 runs and the part-1 gradients (the bulk of the backbone's parameters) while part 2 runs.
-        Two HIP streams: the main one carries the activation-gradient chain, the side one all weight gradients
-        (MFMA split-K kernels + slab reductions), so HBM-bound batch-norm passes overlap MFMA-bound wgrad kernels."""
+        Every launch goes to the current stream. The weight gradients leave split-K slabs that one batched launch per part
+        reduces into the arena (a second stream for them measured slower: the kernels already fill the chip)."""
         b, feats, images = self._last
         g = self._grad_buffers(b)
         sp, slab = b["stat_part"], g["slab"]
-        if self.overlap_wgrad and self._wstream is None:
-            self._wstream = torch.cuda.Stream(device=self.device)
-        W = self._wgrad
         if part in (None, 0):
-            self._backward_head(b, g, feats, sp, slab, W)
-            if self._wstream is not None:
-                torch.cuda.current_stream().wait_stream(self._wstream)
+            self._backward_head(b, g, feats, sp, slab)
             g["reducer"][0].run()
         for ph in (1, 2):
             if part in (None, ph):
-                self._backward_backbone(b, g, images, sp, slab, W, ph)
-                if self._wstream is not None:
-                    torch.cuda.current_stream().wait_stream(self._wstream)   # join: every slab of this phase is written
+                self._backward_backbone(b, g, images, sp, slab, ph)
                 g["reducer"][ph].run()   # (after phase 2: every gradient is in the arena)
 
-    def _backward_head(self, b, g, feats, sp, slab, W):
+    def _backward_head(self, b, g, feats, sp, slab):
         # ---- head + final conv
         if self._fused_conv_bn() and ops.heatmap_head_bwd_bn_supported(b["final"].shape[3], self.dtype):
             # the head's backward kernel also reduces for final_bn (its input's batch-norm): one launch and one pass less
@@ -620,7 +594,7 @@ class KeypointNet(ModelState):
             ops.heatmap_head_bwd(b["final"], g["dlogits"], self.heat_w, self.final_bn.affine, g["final"], self._head_grad,
                                  slab[id(self._head_grad)], reduce=False)
             ops.bn_backward(self.final_bn, g["final"], b["final"], sp)
-        W(lambda: ops.conv_bwd_weight(b["concat"], g["final"], 3, self.concat_affine, self.final_conv.dw, slab[id(self.final_conv.dw)], reduce=False))
+        ops.conv_bwd_weight(b["concat"], g["final"], 3, self.concat_affine, self.final_conv.dw, slab[id(self.final_conv.dw)], reduce=False)
         ops.conv_fwd(g["final"], self.final_conv.packed.bwd, 4 * DEPTH, 3, None, out=g["concat"])
         # ---- phi subnets + p{l}_batch_norm, stage by stage over the four levels (see subnet_forward): reductions into
         # per-level scratch, ONE finalize launch per stage, then the applies and the convolutions' gradients
@@ -639,8 +613,7 @@ class KeypointNet(ModelState):
         none4 = [None] * 4
         fused = self._fused_conv_bn()
         ops.bn_bwd_apply_grouped(bn2s, gy2, by2)
-        W(lambda: ops.conv_bwd_weight_grouped(by1, gy2, 3, [self.phi[l]["bn1"].affine for l in LV],
-                                              [slab[id(self.phi[l]["conv2"].dw)] for l in LV]))
+        ops.conv_bwd_weight_grouped(by1, gy2, 3, [self.phi[l]["bn1"].affine for l in LV], [slab[id(self.phi[l]["conv2"].dw)] for l in LV])
         if fused:   # conv2's data gradient also reduces for bn1 (and writes the gradient masked by bn1's ReLU)
             ops.conv_bwd_data_bn_grouped(gy2, [self.phi[l]["conv2"].packed.bwd for l in LV], DEPTH, bn1s, by1, gy1, sps)
         else:
@@ -649,8 +622,7 @@ class KeypointNet(ModelState):
             ops.bn_bwd_reduce_grouped(bn1s, gy1, by1, sps)
         fin["dbn1"].run()
         ops.bn_bwd_apply_grouped(bn1s, gy1, by1)
-        W(lambda: ops.conv_bwd_weight_grouped(bp, gy1, 3, [self.p_bn[l].affine for l in LV],
-                                              [slab[id(self.phi[l]["conv1"].dw)] for l in LV]))
+        ops.conv_bwd_weight_grouped(bp, gy1, 3, [self.p_bn[l].affine for l in LV], [slab[id(self.phi[l]["conv1"].dw)] for l in LV])
         if fused:
             ops.conv_bwd_data_bn_grouped(gy1, [self.phi[l]["conv1"].packed.bwd for l in LV], DEPTH, pbns, bp, gp, sps)
         else:
@@ -662,118 +634,101 @@ class KeypointNet(ModelState):
         # the four 3x3 convolutions (fpn.py:39,52) are independent: ONE grid for their weight gradients, one for their data
         # gradients; the nearest-upsample gradients then chain the levels
         ops.bn_bwd_apply_grouped(pbns, gp, bp, [g["daux"][l] for l in LV])
-        W(lambda: ops.conv_bwd_weight_grouped([b["x"][l] for l in LV], gp, 3, none4, [slab[id(self.pconv[l].dw)] for l in LV]))
+        ops.conv_bwd_weight_grouped([b["x"][l] for l in LV], gp, 3, none4, [slab[id(self.pconv[l].dw)] for l in LV])
         ops.conv_fwd_grouped(gp, [self.pconv[l].packed.bwd for l in LV], DEPTH, 3, none4, [g["x"][l] for l in LV], none4)
+        # c5 has one consumer (lateral5): its data gradient also reduces for Conv2d_13_pointwise's batch-norm - the backbone's
+        # backward pass starts from that finalize (`sp` is not touched in between)
+        g["c5_reduced"] = 0
         for l in (2, 3, 4, 5):
             if l > 2:
                 ops.sumpool2x2(g["x"][l - 1], g["x"][l], accumulate=True)        # grad of nearest 2x upsample
             raw, aff = feats[f"c{l}"]
-            if self.fuse_pw_bwd and self.fuse_pw_wide and l < 5 and aff is not None and ops.conv1x1_bwd_fused_supported(raw.shape[3], DEPTH, self.dtype):
-                # (lateral2: both gradients in one pass over c2 and its gradient; no batch-norm below this one to reduce for here -
-                #  c2 has a second consumer, the sum is reduced by the backbone's backward)
-                ops.conv1x1_bwd_fused(raw, g["x"][l], self.lateral[l].w, aff, g["c"][f"c{l}"], slab[id(self.lateral[l].dw)], None)
-                continue
-            W(lambda: ops.conv_bwd_weight(raw, g["x"][l], 1, aff, self.lateral[l].dw, slab[id(self.lateral[l].dw)], reduce=False))
-            # c5 has one consumer (lateral5): its data gradient also reduces for Conv2d_13_pointwise's batch-norm - the backbone's
-            # backward pass starts from that finalize (`sp` is not touched in between)
-            g["c5_reduced"] = 0
+            ops.conv_bwd_weight(raw, g["x"][l], 1, aff, self.lateral[l].dw, slab[id(self.lateral[l].dw)], reduce=False)
             if l == 5 and self.fuse_conv_bn and ops.conv_bwd_data_bn_supported(DEPTH, raw.shape[3], 1, self.dtype):
                 g["c5_reduced"] = ops.conv_bwd_data_bn(g["x"][l], self.lateral[l].packed.bwd, raw.shape[3], 1, self.blocks[-1]["pw_bn"], raw,
                                                        g["c"][f"c{l}"], sp)
             else:
                 ops.conv_fwd(g["x"][l], self.lateral[l].packed.bwd, raw.shape[3], 1, None, out=g["c"][f"c{l}"])
 
-    def _backward_backbone(self, b, g, images, sp, slab, W, phase):
+    def _backward_backbone(self, b, g, images, sp, slab, phase):
         """phase 1: blocks 13 .. DP_DEEP_FROM_BLOCK; phase 2: the blocks below and the stem. The chain's state between the two
-        (the gradient tensor, whether the last data gradient already reduced for the next batch-norm, whether a lateral's
+        (the gradient tensor, the rows the last data gradient already reduced for the next batch-norm, whether a lateral's
         gradient is already added) is Python state handed over through `g` - static per shape, so both phases capture."""
-        first = DP_DEEP_FROM_BLOCK - 1            # index of the first deep block
+        first, last = DP_DEEP_FROM_BLOCK - 1, len(self.blocks) - 1      # (indices of the first deep block and of block 13)
         if phase == 1:
-            dA = g["c"]["c5"]
-            reduced, raw_sums = g.get("c5_reduced", 0), True   # (the lateral's data gradient may have reduced for the last batch-norm)
-            lateral_added = False
-            rng = range(len(self.blocks) - 1, first - 1, -1)
+            dA, reduced, lateral_added = g["c"]["c5"], g.get("c5_reduced", 0), False
+            rng = range(last, first - 1, -1)
         else:
-            dA, reduced, raw_sums, lateral_added = g["bb_chain"]
+            dA, reduced, lateral_added = g["bb_chain"]
             rng = range(first - 1, -1, -1)
         for i in rng:
-            blk = self.blocks[i]
-            if blk["i"] in FEATURE_BLOCKS and blk["i"] != 13 and not lateral_added:
-                ops.add_inplace(dA, g["c"][FEATURE_BLOCKS[blk["i"]]])
-            # the thin pointwise layers: weight gradient, data gradient and the reduction for the depthwise batch-norm below in ONE
-            # pass over the layer's input and dY (each tensor once instead of twice); on the thinnest one the layer's own batch-norm
-            # apply pass happens while dY is staged (two more passes over its output tensor less)
-            pw_fused = self.fuse_pw_bwd and self.fuse_conv_bn and ops.conv1x1_bwd_fused_supported(blk["pw"].cin, blk["pw"].cout, self.dtype) and \
-                (blk["pw"].cin <= 64 or self.fuse_pw_wide)
-            pw_apply = pw_fused and self.fuse_pw_apply and ops.conv1x1_bwd_fused_apply_supported(blk["pw"].cin, blk["pw"].cout, self.dtype)
-            ops.bn_backward(blk["pw_bn"], dA, b["pw"][i], sp, reduced_parts=reduced, raw=raw_sums and reduced > 0, apply=not pw_apply)
-            raw_sums = False                                    # (depthwise data gradients sum g * xhat themselves)
-            if pw_fused:
-                with _lib.tagged("pointwise"):
-                    rows = ops.conv1x1_bwd_fused(b["dw"][i], dA, blk["pw"].w, blk["dw_bn"], g["dw"][i], slab[id(blk["pw"].dw)], sp,
-                                                 apply_bn=blk["pw_bn"] if pw_apply else None, y_raw=b["pw"][i] if pw_apply else None)
-                ops.bn_backward(blk["dw_bn"], g["dw"][i], b["dw"][i], sp, reduced_parts=rows, raw=True)
-            else:
-                with _lib.tagged("pointwise"):
-                    W(lambda: ops.conv_bwd_weight(b["dw"][i], dA, 1, blk["dw_bn"].affine, blk["pw"].dw, slab[id(blk["pw"].dw)], reduce=False))
-                # the deep pointwise layers' data gradients also reduce for the depthwise batch-norm they feed
-                if self.fuse_conv_bn and ops.conv_bwd_data_bn_supported(blk["pw"].cout, blk["pw"].cin, 1, self.dtype):
-                    with _lib.tagged("pointwise"):
-                        rows = ops.conv_bwd_data_bn(dA, blk["pw"].packed.bwd, blk["pw"].cin, 1, blk["dw_bn"], b["dw"][i], g["dw"][i], sp)
-                    ops.bn_backward(blk["dw_bn"], g["dw"][i], b["dw"][i], sp, reduced_parts=rows, raw=True)
-                else:
-                    with _lib.tagged("pointwise"):
-                        ops.conv_fwd(dA, blk["pw"].packed.bwd, blk["pw"].cin, 1, None, out=g["dw"][i])
-                    ops.bn_backward(blk["dw_bn"], g["dw"][i], b["dw"][i], sp)
-            xin = b["pw"][i - 1] if i > 0 else b["stem"]
-            ain = self.blocks[i - 1]["pw_bn"].affine if i > 0 else self.stem_bn.affine
-            dst = g["pw"][i - 1] if i > 0 else g["stem"]
-            prev_feature = i > 0 and self.blocks[i - 1]["i"] in FEATURE_BLOCKS
-            # stride-1 layers whose input is not an FPN feature: both gradients and the reduction for the batch-norm below in one
-            # walk over dY, the raw input and dA (three tensor passes instead of five)
-            if self.fuse_dw_bwd and self.fuse_dw_bn and blk["stride"] == 1 and not prev_feature and \
-                    ops.dwconv_bwd_fused_supported(dst.shape[0], *b["hw"][i], dst.shape[3], 1, dst.dtype):
-                prev_bn = self.blocks[i - 1]["pw_bn"] if i > 0 else self.stem_bn
-                _, reduced = ops.dwconv_bwd_fused(xin, g["dw"][i], blk["dw_w"], prev_bn, None, out=dst, wpart=slab[id(blk["dw_dw"])],
-                                                  bn_part=sp, reduce=False)
-                lateral_added = False
-                dA = dst
-                continue
-            prev_bn = self.blocks[i - 1]["pw_bn"] if i > 0 else self.stem_bn
-            # stride-2 layers (even maps): the same in one walk, the FPN lateral's gradient into the feature map below added inside it
-            if self.fuse_dw_bwd and self.fuse_dw_bwd_s2 and self.fuse_dw_bn and self.fuse_lateral_add and blk["stride"] == 2 and \
-                    ops.dwconv_bwd_fused_supported(dst.shape[0], *b["hw"][i], dst.shape[3], 2, dst.dtype):
-                addend = g["c"][FEATURE_BLOCKS[self.blocks[i - 1]["i"]]] if prev_feature else None
-                _, reduced = ops.dwconv_bwd_fused(xin, g["dw"][i], blk["dw_w"], prev_bn, None, out=dst, wpart=slab[id(blk["dw_dw"])],
-                                                  bn_part=sp, reduce=False, stride=2, addend=addend)
-                lateral_added = addend is not None
-                dA = dst
-                continue
-            W(lambda: ops.dwconv_bwd_weight(xin, g["dw"][i], blk["stride"], ain, blk["dw_dw"], slab[id(blk["dw_dw"])], reduce=False))
-            # the data gradient also reduces for the batch-norm it feeds (one read of dA and one launch less), unless a
-            # lateral's gradient still has to be added to dA first
-            prev_x = b["pw"][i - 1] if i > 0 else b["stem"]
-            # c2..c4 have two consumers (the next depthwise conv and an FPN lateral, mobilenet_v1.py:76-79): the lateral's
-            # gradient is added inside the data-gradient kernel where it can be (stride-2 layers with even maps - all three
-            # at the reference's input sizes), otherwise by add_inplace at the top of the next iteration
-            addend = g["c"][FEATURE_BLOCKS[self.blocks[i - 1]["i"]]] if prev_feature else None
-            lateral_added = addend is not None and self.fuse_lateral_add and \
-                ops.dwconv_bwd_data_add_supported(dst.shape[0], *b["hw"][i], dst.shape[3], blk["stride"], dst.dtype)
-            if not lateral_added:
-                addend = None
-            reduced = 0
-            if self.fuse_dw_bn and (not prev_feature or lateral_added) and \
-                    ops.dwconv_bwd_data_bn_num_parts(dst.shape[0], *b["hw"][i], dst.shape[3], blk["stride"], dst.dtype) > 0:
-                _, reduced = ops.dwconv_bwd_data(g["dw"][i], blk["dw_w"], b["hw"][i], blk["stride"], out=dst, bn=prev_bn,
-                                                 x_bn=prev_x, part=sp, addend=addend)
-            else:
-                ops.dwconv_bwd_data(g["dw"][i], blk["dw_w"], b["hw"][i], blk["stride"], out=dst, addend=addend)
-            dA = dst
+            feature = FEATURE_BLOCKS.get(self.blocks[i]["i"])
+            if feature in ("c2", "c3", "c4") and not lateral_added:
+                ops.add_inplace(dA, g["c"][feature])
+            # (block 13's rows, if any, come from lateral5's data gradient, which sums g * x with the raw x; the depthwise data
+            #  gradients sum g * xhat themselves)
+            dY = self._backward_pointwise(b, g, sp, slab, i, dA, reduced, raw=i == last)
+            dA, reduced, lateral_added = self._backward_depthwise(b, g, sp, slab, i, dY)
         if phase == 1:
-            g["bb_chain"] = (dA, reduced, raw_sums, lateral_added)
+            g["bb_chain"] = (dA, reduced, lateral_added)
             return
         ops.bn_backward(self.stem_bn, g["stem"], b["stem"], sp, reduced_parts=reduced)
-        W(lambda: ops.stem_conv_bwd_weight(images, g["stem"], self.stem_dw, slab[id(self.stem_dw)], reduce=False))
+        ops.stem_conv_bwd_weight(images, g["stem"], self.stem_dw, slab[id(self.stem_dw)], reduce=False)
+
+    def _backward_pointwise(self, b, g, sp, slab, i, dA, reduced, raw):
+        """Block i's pointwise layer: dA (gradient w.r.t. its activated output; `reduced` rows of its batch-norm's reduction
+        already in `sp`, `raw` sums) -> the gradient w.r.t. the depthwise layer's raw output below, returned; the weight
+        gradient into its slab."""
+        blk = self.blocks[i]
+        pw, x, dY = blk["pw"], b["dw"][i], g["dw"][i]
+        # the thin layers: weight gradient, data gradient and the reduction for the depthwise batch-norm below in ONE pass over
+        # x and dA (each tensor once instead of twice); on the thinnest ones this layer's own batch-norm apply pass happens while
+        # dA is staged. Cin <= 64 is policy, not the kernel's limit (128): the 128-channel layers measured equal to two passes
+        fused = self.fuse_conv_bn and ops.conv1x1_bwd_fused_supported(pw.cin, pw.cout, self.dtype) and pw.cin <= 64
+        apply = fused and ops.conv1x1_bwd_fused_apply_supported(pw.cin, pw.cout, self.dtype)
+        ops.bn_backward(blk["pw_bn"], dA, b["pw"][i], sp, reduced_parts=reduced, raw=raw, apply=not apply)
+        rows = 0
+        with _lib.tagged("pointwise"):
+            if fused:
+                rows = ops.conv1x1_bwd_fused(x, dA, pw.w, blk["dw_bn"], dY, slab[id(pw.dw)], sp,
+                                             apply_bn=blk["pw_bn"] if apply else None, y_raw=b["pw"][i] if apply else None)
+            else:
+                ops.conv_bwd_weight(x, dA, 1, blk["dw_bn"].affine, pw.dw, slab[id(pw.dw)], reduce=False)
+                # the deep layers' data gradients also reduce for the depthwise batch-norm they feed
+                if self.fuse_conv_bn and ops.conv_bwd_data_bn_supported(pw.cout, pw.cin, 1, self.dtype):
+                    rows = ops.conv_bwd_data_bn(dA, pw.packed.bwd, pw.cin, 1, blk["dw_bn"], x, dY, sp)
+                else:
+                    ops.conv_fwd(dA, pw.packed.bwd, pw.cin, 1, None, out=dY)
+        ops.bn_backward(blk["dw_bn"], dY, x, sp, reduced_parts=rows, raw=True)
+        return dY
+
+    def _backward_depthwise(self, b, g, sp, slab, i, dY):
+        """Block i's depthwise layer: dY (gradient w.r.t. its raw output, through its batch-norm) -> the gradient w.r.t. the
+        activated output of the layer below; the weight gradient into its slab. Returns (that gradient, the rows already reduced
+        for the batch-norm below - 0: none, whether the FPN lateral's gradient is already added to it)."""
+        blk = self.blocks[i]
+        x, bn, dA = (b["pw"][i - 1], self.blocks[i - 1]["pw_bn"], g["pw"][i - 1]) if i > 0 else (b["stem"], self.stem_bn, g["stem"])
+        N, hw, C, s = dA.shape[0], b["hw"][i], dA.shape[3], blk["stride"]
+        # c2..c4 have two consumers (the next depthwise conv and an FPN lateral, mobilenet_v1.py:76-79): the lateral's gradient
+        # is added inside the data-gradient kernel where it can be (stride-2 layers with even maps - all three at the
+        # reference's input sizes), otherwise by add_inplace before the block below
+        lateral = g["c"][FEATURE_BLOCKS[self.blocks[i - 1]["i"]]] if i > 0 and self.blocks[i - 1]["i"] in FEATURE_BLOCKS else None
+        # both gradients and the reduction for the batch-norm below in one walk over dY, x and dA (three tensor passes instead
+        # of five); at stride 1 only where no lateral's gradient is to be added
+        if self.fuse_dw_bn and (s == 2 or lateral is None) and ops.dwconv_bwd_fused_supported(N, *hw, C, s, self.dtype):
+            _, reduced = ops.dwconv_bwd_fused(x, dY, blk["dw_w"], bn, None, out=dA, wpart=slab[id(blk["dw_dw"])], bn_part=sp,
+                                              reduce=False, stride=s, addend=lateral)
+            return dA, reduced, lateral is not None
+        ops.dwconv_bwd_weight(x, dY, s, bn.affine, blk["dw_dw"], slab[id(blk["dw_dw"])], reduce=False)
+        late = lateral is not None and not ops.dwconv_bwd_data_add_supported(N, *hw, C, s, self.dtype)
+        addend = None if late else lateral
+        # the data gradient also reduces for the batch-norm it feeds (one read of dA and one launch less), unless the lateral's
+        # gradient still has to be added to dA
+        if self.fuse_dw_bn and not late and ops.dwconv_bwd_data_bn_num_parts(N, *hw, C, s, self.dtype) > 0:
+            _, reduced = ops.dwconv_bwd_data(dY, blk["dw_w"], hw, s, out=dA, bn=bn, x_bn=x, part=sp, addend=addend)
+            return dA, reduced, addend is not None
+        ops.dwconv_bwd_data(dY, blk["dw_w"], hw, s, out=dA, addend=addend)
+        return dA, 0, addend is not None
 
     def add_weight_decay_gradients(self, weight_decay):
         """keypoints_model.py:129-138: + wd * l2_loss(k) for every 'weights'/'kernel' variable except depthwise."""
