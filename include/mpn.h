@@ -518,6 +518,62 @@ size_t mpn_keypoint_augment_desc_bytes(void);
 int mpn_keypoint_augment(const uint8_t* sources, const uint8_t* masks, const void* descs, int B, int H, int W,
                          float* images, float* loss_masks, float* segmentation_masks, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * L3  training examples of the pose residual network, from annotations alone (no image pixels).
+ * Replaces the per-record work of detector/input_pipeline/prn_pipeline.py `parse_and_preprocess`
+ * (:46-156: get_heatmaps through tf.py_func :91-95, tf.image.crop_and_resize :97-103, the label
+ * maps :105-151) and `random_flip_left_right` (:159-203) for a batch of N examples drawn from R
+ * source images of RAGGED sizes, in at most two launches (tables, examples) and without any host
+ * synchronisation. For example n = (image r, person q, flip), output pixel (y, x), part c, with
+ * xs = flip ? crop_w-1-x : x and cs = flip ? perm[c] : c, perm = [0,2,1,4,3,...,16,15]:
+ *
+ *   crops[n,y,x,c]  = crop_and_resize(M_r, boxes[q] / f32(H_r, W_r, H_r, W_r))[y, xs, cs]
+ *                     bilinear, extrapolation value 0, arithmetic and order of mpn_prn_crop
+ *                     (crop_and_resize_op.cc): in_y = y1*(h-1) + y*((y2-y1)*(h-1)/(crop_h-1)), 0 unless
+ *                     0 <= in_y <= h-1 (x likewise), top + (bottom-top)*y_lerp of the taps at floor / ceil
+ *   M_r             = get_heatmaps(persons of image r, W_r, H_r, downsample), [h, w, 17] with
+ *                     h = ceil(H_r/downsample), w likewise: the values mpn_heatmap_render writes (same
+ *                     f32 sigma / centre math, f64 window, f32 product, max over the image's visible
+ *                     persons, peaks exactly 1.0f). M_r is never stored: each tap is evaluated from
+ *                     the per-person tables, the candidate blobs culled per block in chunks of 60
+ *                     persons (no limit on the persons of an image).
+ *   labels[n,y,x,c] = 1 if keypoint cs of person q is visible (v > 0) and
+ *                     y  == clip(rintf((f32(ky) - ymin) * (f32(crop_h) / (ymax - ymin))), 0, crop_h-1),
+ *                     xs == clip(rintf((f32(kx) - xmin) * (f32(crop_w) / (xmax - xmin))), 0, crop_w-1),
+ *                     else 0 (rintf: half to even, as tf.round)
+ * Every float step is one IEEE round-to-nearest operation in that order (no contraction), so both
+ * outputs are bit-identical to the reference's numpy / TensorFlow-CPU sequence.
+ *
+ *   keypoints    [Q,17,3] int32 (y, x, visibility), persons of all R images concatenated, DEVICE
+ *   boxes        [Q,4] f32 (ymin, xmin, ymax, xmax), absolute, DEVICE
+ *   first_person [R+1] int32, DEVICE: persons of image r are first_person[r] .. first_person[r+1]-1
+ *   width,height [R] int32, DEVICE: size of image r (>= 2)
+ *   examples     [N] mpn_prn_example_desc, DEVICE, 16-byte aligned
+ *   crops,labels [N,crop_h,crop_w,17] f32, 16-byte aligned; EVERY element is written (no memset needed)
+ *   workspace    mpn_prn_examples_workspace_bytes(Q) bytes of scratch, 16-byte aligned, uninitialised
+ * Checked before any HIP call: N >= 0, crop_h, crop_w > 0, Q, R >= 0, downsample >= 1 (MPN_ERR_BAD_SHAPE);
+ * N == 0 then returns MPN_OK without a launch; null pointers (MPN_ERR_BAD_ARG), alignment
+ * (MPN_ERR_BAD_ALIGN), workspace size (MPN_ERR_WORKSPACE). The tables' contents are the caller's: an
+ * example whose image or person index is out of range yields zeros; a box of zero height or width
+ * divides by zero in the labels exactly as the reference does (the pipeline drops such persons).
+ */
+#define MPN_PRN_EXAMPLE_DESC_BYTES 16
+typedef struct mpn_prn_example_desc {
+    int32_t image;      /* r: index into first_person / width / height */
+    int32_t person;     /* q: GLOBAL index into keypoints / boxes (first_person[r] <= q < first_person[r+1]) */
+    int32_t flip;       /* nonzero: left-right flip with the left / right parts exchanged */
+    int32_t reserved;
+} mpn_prn_example_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_prn_example_desc) == MPN_PRN_EXAMPLE_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_prn_example_desc_bytes(void);
+size_t mpn_prn_examples_workspace_bytes(int total_persons);
+int mpn_prn_examples(const int32_t* keypoints, const float* boxes, int total_persons,
+                     const int32_t* first_person, const int32_t* width, const int32_t* height,
+                     int num_images, const void* examples, int N, int crop_h, int crop_w, int downsample,
+                     float* crops, float* labels, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
 /* Skinny "NT" GEMM split over K: part[s][M][N] (f32, s < mpn_gemm_nt_num_parts(K)) = A[M][K] * B[N][K]^T over the s-th K range.
  * A, B 16-bit (MPN_BF16 / MPN_F16), row-major with K contiguous - the order the reference's variables already have for
  * dH = dPre2 * W2^T in the pose residual network (prn.py:11-33: fc2's data gradient), so no transposed copy of the weights is

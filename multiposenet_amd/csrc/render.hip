@@ -8,70 +8,19 @@
 // rounding of the separable product), so the result is bit-identical to the numpy code; peaks are exactly 1.0.
 // HBM-bound: the kernel writes every output byte once (h*w*17*4 B per image) and reads a few hundred bytes.
 #include "common.h"
+#include "render_person.h"
 
 namespace {
 
-constexpr int kParts = 17;
-constexpr int kMaxHalf = 13;                 // sigma <= 4  ->  k = ceil(sqrt(2*16*ln 100)) = 13
-constexpr int kG = 16;                       // doubles per person in the window table (g[0..13], padded)
 constexpr int kTileH = 8, kTileW = 32, kThreads = kTileH * kTileW;
-constexpr int kChunk = 60;                   // persons per culling pass (60*17 = 1020 candidate blobs)
-constexpr int kInvisible = 0x7fffffff;
-
-struct RenderTables {
-    double* g;      // [P][kG]
-    int2* centre;   // [P][17]  (cy, cx); cy == kInvisible for an invisible keypoint
-    int* half;      // [P]
-};
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-inline RenderTables carve(void* ws, int P) {
-    RenderTables t;
-    unsigned char* p = reinterpret_cast<unsigned char*>(ws);
-    t.g = reinterpret_cast<double*>(p);
-    p += align16((size_t)P * kG * sizeof(double));
-    t.centre = reinterpret_cast<int2*>(p);
-    p += align16((size_t)P * kParts * sizeof(int2));
-    t.half = reinterpret_cast<int*>(p);
-    return t;
-}
 
 // heatmap_creation.py:30-37,78-84: per-person sigma, half window k and the 1-D window; :23-24,57,104-107: centres.
 __global__ void __launch_bounds__(256) render_prepare_kernel(const int32_t* __restrict__ keypoints,
                                                               const float* __restrict__ boxes, int P, float hm1,
                                                               float wm1, float oh1, float ow1, RenderTables t) {
-    // Every operation below is one IEEE-754 round-to-nearest step of the numpy code: no contraction into FMAs, and
-    // sqrtf / operator/ are the correctly rounded forms (the __f*_rn intrinsics map to the approximate native ops).
-#pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P * kParts) return;
-    const int p = i / kParts, j = i - p * kParts;
-    const float ymin = boxes[p * 4 + 0], xmin = boxes[p * 4 + 1], ymax = boxes[p * 4 + 2], xmax = boxes[p * 4 + 3];
-    const float area = (ymax - ymin) * (xmax - xmin);
-    float s = sqrtf(area) * 0.007f;
-    s = fminf(fmaxf(s, 1.0f), 4.0f);
-    const float s2 = s * s;
-    // k = ceil(sqrt(float32(-2 s^2) * ln(0.01)))  in float64
-    const double arg = (double)(-2.0f * s2) * -0x1.26bb1bbb55515p+2;
-    int k = (int)ceil(sqrt(arg));
-    k = k > kMaxHalf ? kMaxHalf : k;
-    if (j == 0) t.half[p] = k;
-    if (j <= kMaxHalf) {
-        const double sig2 = (double)((2.0f * s) * s);
-        t.g[p * kG + j] = j <= k ? exp(-(double)(j * j) / sig2) : 0.0;
-    }
-    const int32_t* kp = keypoints + (size_t)i * 3;   // (y, x, visibility)
-    int2 c;
-    if (kp[2] > 0) {
-        const float ny = (float)kp[0] / hm1, nx = (float)kp[1] / wm1;
-        c.x = (int)rintf(ny * oh1);
-        c.y = (int)rintf(nx * ow1);
-    } else {
-        c.x = kInvisible;
-        c.y = 0;
-    }
-    t.centre[i] = c;
+    render_prepare_entry(keypoints, boxes, i, hm1, wm1, oh1, ow1, t);
 }
 
 __global__ void __launch_bounds__(kThreads) render_kernel(const int32_t* __restrict__ first_person, int h, int w,
@@ -148,9 +97,7 @@ __global__ void __launch_bounds__(kThreads) render_kernel(const int32_t* __restr
 }  // namespace
 
 extern "C" size_t mpn_heatmap_render_workspace_bytes(int total_persons) {
-    if (total_persons <= 0) return 16;
-    const size_t P = (size_t)total_persons;
-    return align16(P * kG * sizeof(double)) + align16(P * kParts * sizeof(int2)) + align16(P * sizeof(int));
+    return render_tables_bytes(total_persons);
 }
 
 extern "C" int mpn_heatmap_render(const int32_t* keypoints, const float* boxes, const int32_t* first_person, int B,

@@ -18,7 +18,7 @@ import struct
 import numpy as np
 
 __all__ = ["crc32c", "masked_crc32c", "read_records", "parse_example", "encode_example", "frame_record",
-           "decode_keypoint_example", "unpack_masks", "decode_jpeg"]
+           "decode_keypoint_example", "unpack_masks", "decode_jpeg", "jpeg_shape"]
 
 
 def _crc_table():
@@ -226,6 +226,38 @@ def decode_jpeg(data):
     import io
     with Image.open(io.BytesIO(bytes(data))) as im:
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def jpeg_shape(data):
+    """(height, width) of a JPEG stream without decoding it (tf.image.extract_jpeg_shape, prn_pipeline.py:63): the frame
+    header SOF0..SOF15 (markers 0xC0-0xCF except DHT 0xC4, JPG 0xC8 and DAC 0xCC) holds precision u8, height u16, width u16,
+    big endian. Raises ValueError on a stream without one."""
+    buf = memoryview(data).cast("B") if not isinstance(data, (bytes, bytearray)) else data
+    n = len(buf)
+    if n < 4 or buf[0] != 0xFF or buf[1] != 0xD8:
+        raise ValueError("not a JPEG stream (no SOI marker)")
+    pos = 2
+    while pos + 4 <= n:
+        if buf[pos] != 0xFF:
+            raise ValueError(f"JPEG: marker expected at byte {pos}")
+        m = buf[pos + 1]
+        if m == 0xFF:                                   # fill byte
+            pos += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD8:              # TEM, RSTn, SOI: no length
+            pos += 2
+            continue
+        if m == 0xD9 or m == 0xDA:                      # EOI, or the scan began before any frame header
+            break
+        length = (buf[pos + 2] << 8) | buf[pos + 3]
+        if length < 2:
+            raise ValueError(f"JPEG: bad segment length at byte {pos}")
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            if length < 7 or pos + 9 > n:
+                raise ValueError("JPEG: truncated frame header")
+            return (buf[pos + 5] << 8) | buf[pos + 6], (buf[pos + 7] << 8) | buf[pos + 8]
+        pos += 2 + length
+    raise ValueError("JPEG: no frame header (SOF) found")
 
 
 def decode_keypoint_example(data, decode_image=True):
