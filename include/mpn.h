@@ -519,6 +519,60 @@ int mpn_keypoint_augment(const uint8_t* sources, const uint8_t* masks, const voi
                          float* images, float* loss_masks, float* segmentation_masks, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * L2b person-detector input augmentation (the per-pixel half of the detector's input pipeline).
+ * Replaces the image operations of detector/input_pipeline/person_detector_pipeline.py `augmentation`
+ * (:109-116: `randomly_crop_and_resize` :119-138, `randomly_pad` :141-180, color_augmentations.py:10-69,
+ * `random_flip_left_right` :245-257) and `resize_keeping_aspect_ratio` (:183-242) for a batch of RAGGED
+ * uint8 sources in one launch. The host draws every random decision and fills one descriptor per image
+ * (multiposenet_amd/detector/input_pipeline/detector_augment.py); per output pixel (y, x), with
+ * p = flip ? W-1-x : x the position before the flip:
+ *
+ *   S2(sy,sx)  stage-2 canvas [H,W]: 0 unless sy < valid_h and sx < valid_w (pad_to_bounding_box, :225), else
+ *              the legacy bilinear resize of the crop of u8 * float32(1/255): in = out * scale (f32 in/out),
+ *              lo = floor(in), hi = min(lo+1, crop-1), top + (bottom-top)*y_lerp    (resize_images, :137, :221)
+ *   pad        MPN_AUGMENT_PAD: 0 unless pad_y <= y < pad_y+pad_h and pad_x <= p < pad_x+pad_w, else the same
+ *              legacy bilinear resize of S2 (in size H x W) sampled at (y-pad_y, p-pad_x) with pad_scale:
+ *              4 taps of S2, each computed on the fly (S2 is never stored). Without the flag: S2(y, p).
+ *   colour     clip(v + color[c], 0, 1), over the whole canvas, zero padding included   (:19-33)
+ *   grayscale  0.2989 r + 0.5870 g + 0.1140 b on all channels                           (:35-38)
+ *   scale      clip(v * (u * (maxval - minval) + minval), 0, 1),
+ *              u = (fmix32(seed ^ (idx * 0x9E3779B1)) >> 8) * 2^-24, idx = (y*W + p)*3 + c  (:47-69)
+ * Every float step is one IEEE round-to-nearest operation in that order (no contraction).
+ * MPN_AUGMENT_EVAL marks a descriptor of the evaluation path (valid_h x valid_w smaller than H x W, no other
+ * flag); the pixel arithmetic does not depend on it. The flag values are those of the keypoint kernel;
+ * MPN_AUGMENT_ROTATE has no meaning here and is ignored.
+ *
+ *   sources    concatenated uint8 RGB images [src_h, src_w, 3]; image b starts at byte src_offset
+ *   descs      [B] mpn_detector_augment_desc, DEVICE, 16-byte aligned
+ *   images     [B,H,W,3] f32, 16-byte aligned
+ * 1 <= B <= 65535, H % 4 == 0, W % 4 == 0, both <= 16384. Every output element is written. Descriptor fields are
+ * the caller's to check (offsets and sizes inside the buffer); a source read outside an image's own rectangle
+ * returns 0. mpn_detector_augment_desc_bytes() = sizeof(mpn_detector_augment_desc), for bindings.
+ */
+enum { MPN_AUGMENT_PAD = 64 };
+#define MPN_DETECTOR_AUGMENT_DESC_BYTES 112
+typedef struct mpn_detector_augment_desc {
+    int64_t src_offset;                         /* byte offset into sources */
+    int32_t src_h, src_w;
+    int32_t crop_y, crop_x, crop_h, crop_w;     /* integer crop of the source (begin, size) */
+    int32_t valid_h, valid_w;                   /* stage-2 size: H, W in training; new_h, new_w in evaluation */
+    int32_t pad_y, pad_x, pad_h, pad_w;         /* placed rectangle (MPN_AUGMENT_PAD): offset and scaled size */
+    float scale_y, scale_x;                     /* f32(crop_h)/f32(valid_h), f32(crop_w)/f32(valid_w) */
+    float pad_scale_y, pad_scale_x;             /* f32(H)/f32(pad_h), f32(W)/f32(pad_w) (MPN_AUGMENT_PAD) */
+    float color[3];                             /* per-channel offsets (MPN_AUGMENT_COLOR) */
+    float minval, maxval;                       /* pixel-scale range (MPN_AUGMENT_PIXEL_SCALE) */
+    uint32_t seed;                              /* pixel-scale hash seed (MPN_AUGMENT_PIXEL_SCALE) */
+    int32_t flags;                              /* MPN_AUGMENT_* */
+    int32_t reserved[3];
+} mpn_detector_augment_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_detector_augment_desc) == MPN_DETECTOR_AUGMENT_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_detector_augment_desc_bytes(void);
+int mpn_detector_augment(const uint8_t* sources, const void* descs, int B, int H, int W, float* images,
+                         mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * L3  training examples of the pose residual network, from annotations alone (no image pixels).
  * Replaces the per-record work of detector/input_pipeline/prn_pipeline.py `parse_and_preprocess`
  * (:46-156: get_heatmaps through tf.py_func :91-95, tf.image.crop_and_resize :97-103, the label

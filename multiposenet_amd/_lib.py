@@ -32,6 +32,8 @@ SIGNATURES = {
     "mpn_heatmap_render": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     "mpn_keypoint_augment_desc_bytes": (_Z, []),
     "mpn_keypoint_augment": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "mpn_detector_augment_desc_bytes": (_Z, []),
+    "mpn_detector_augment": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "mpn_prn_example_desc_bytes": (_Z, []),
     "mpn_prn_examples_workspace_bytes": (_Z, [_I]),
     "mpn_prn_examples": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
