@@ -733,6 +733,37 @@ int mpn_retina_nms(const void* const* logits, const void* const* boxes, const in
                    float iou_threshold, int max_detections, float* out_boxes, float* out_scores, int* out_num,
                    void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Result packing of the batched joint inference graph (create_pb.py:53-61 for b images; the score filter of
+ * inference/detector.py:54-59 and the live-slot gather of create_pb.py:96-104 without leaving the device).
+ *
+ *   mpn_pose_gather   boxes f32 [B,max_boxes,4] normalised (ymin,xmin,ymax,xmax), scores f32 [B,max_boxes], num_boxes int32 [B]
+ *                     (mpn_retina_nms's outputs), keypoint_scores f32 [B*max_boxes,17], keypoint_positions f32
+ *                     [B*max_boxes,17,2] = (y, x) normalised to the box (mpn_prn_decode's outputs; either may be NULL: its
+ *                     fields and what derives from them are zero), overflow: the NMS overflow word (may be NULL: 0)
+ *                     -> ONE record of mpn_pose_gather_record_bytes(B, max_boxes) bytes, in 32-bit words:
+ *                       header  int32: total, counts[B], num_boxes[B] (copied through: the count BEFORE the filter),
+ *                               overflow; zero words up to the next multiple of 16 bytes
+ *                       rows    B*max_boxes of them, row r at byte mpn_pose_gather_row_offset(B, max_boxes, r); a row is
+ *                               int32 image_index, f32 box[4], score, keypoint_scores[17], keypoint_positions[17][2],
+ *                               keypoints[17][3] = (x, y, score) in image pixels:
+ *                                 x = xmin*width + pos_x * (xmax*width - xmin*width), y likewise with height
+ *                               (inference/predict.ipynb, draw_everything; plain IEEE f32 in that order, no contraction).
+ *                     A slot is KEPT iff slot < num_boxes[image] and score > score_threshold (strict). Kept slots fill rows
+ *                     0 .. total-1 in (image, slot) order; every other row is zero. Slots >= num_boxes are never read.
+ *                     One block: B * max_boxes <= 4096 (MPN_ERR_BAD_SHAPE above; record_bytes then returns 0).
+ *                     Checked before any HIP call: null boxes / scores / num_boxes / record (MPN_ERR_BAD_ARG), B, max_boxes,
+ *                     height, width >= 1 and the row count (MPN_ERR_BAD_SHAPE), record 16-byte aligned (MPN_ERR_BAD_ALIGN),
+ *                     record_bytes (MPN_ERR_WORKSPACE).
+ *   mpn_pose_gather_row_offset   row in [0, B*max_boxes]; the last is the record's size; the difference of two neighbours is
+ *                                the row stride. 0 for arguments out of range.
+ */
+size_t mpn_pose_gather_record_bytes(int B, int max_boxes);
+size_t mpn_pose_gather_row_offset(int B, int max_boxes, int row);
+int mpn_pose_gather(const float* boxes, const float* scores, const int* num_boxes, const float* keypoint_scores,
+                    const float* keypoint_positions, const int* overflow, int B, int max_boxes, float score_threshold,
+                    int height, int width, void* record, size_t record_bytes, mpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

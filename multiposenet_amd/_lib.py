@@ -138,6 +138,9 @@ SIGNATURES = {
     "mpn_l2_loss_accumulate": (_I, [_L, _P, _F, _P, _P]),
     "mpn_l2_loss_batched_workspace_bytes": (_Z, [_I, _P]),
     "mpn_l2_loss_batched": (_I, [_I, _P, _P, _F, _P, _P, _Z, _P]),
+    "mpn_pose_gather_record_bytes": (_Z, [_I, _I]),
+    "mpn_pose_gather_row_offset": (_Z, [_I, _I, _I]),
+    "mpn_pose_gather": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _Z, _P]),
 }
 
 _lib = None

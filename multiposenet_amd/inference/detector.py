@@ -10,6 +10,7 @@ files keyed by the reference's variable names (multiposenet_amd.checkpoint)."""
 import numpy as np
 import torch
 
+from .. import _lib
 from ..net import KeypointNet
 
 # create_pb.py:31-36: the thresholds frozen into the graph
@@ -22,6 +23,73 @@ def _load(path):
         return path
     with np.load(path) as z:
         return {k: z[k] for k in z.files}
+
+
+NUM_KEYPOINTS = 17
+# a row of mpn_pose_gather's record (include/mpn.h names the fields in this order; offsets and stride come from the library)
+_ROW = np.dtype([('image_index', np.int32), ('box', np.float32, (4,)), ('score', np.float32),
+                 ('keypoint_scores', np.float32, (NUM_KEYPOINTS,)), ('keypoint_positions', np.float32, (NUM_KEYPOINTS, 2)),
+                 ('keypoints', np.float32, (NUM_KEYPOINTS, 3))])
+
+
+def check_batch(images):
+    """The argument checks of `Detector.predict_batch`, before any device work: (b, height, width) of a uint8 [b, h, w, 3]
+    array or a list of b equally sized uint8 [h, w, 3] arrays; the errors of `Detector.__call__` for a bad size or dtype."""
+    if isinstance(images, np.ndarray):
+        if images.ndim != 4:
+            raise ValueError("images must be an array [b, height, width, 3] or a list of [height, width, 3] arrays")
+        items = [images]
+        b, shape = images.shape[0], tuple(images.shape[1:])
+    else:
+        items = list(images)
+        if any(not isinstance(im, np.ndarray) for im in items):
+            raise ValueError("images must be numpy arrays")
+        shapes = {tuple(im.shape) for im in items}
+        if len(shapes) > 1:
+            raise ValueError(f"the images of a batch must have one size (got {sorted(shapes)})")
+        b, shape = len(items), (shapes.pop() if shapes else ())
+    if b < 1:
+        raise ValueError("empty batch")
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"an image must be [height, width, 3] (got {shape})")
+    h, w, _ = shape
+    assert h % 128 == 0 and w % 128 == 0                          # inference/detector.py:45
+    if any(im.dtype != np.uint8 for im in items):
+        raise ValueError("image must be uint8")
+    return b, h, w
+
+
+def _no_persons(num_boxes=0):
+    return {'boxes': np.zeros([0, 4], np.float32), 'scores': np.zeros([0], np.float32), 'num_boxes': np.int32(num_boxes),
+            'keypoint_scores': np.zeros([0, NUM_KEYPOINTS], np.float32), 'keypoint_positions': np.zeros([0, NUM_KEYPOINTS, 2], np.float32),
+            'keypoints': np.zeros([0, NUM_KEYPOINTS, 3], np.float32)}
+
+
+def unpack_record(record, b, max_boxes, with_keypoints=True):
+    """A host copy of mpn_pose_gather's record (uint8 array) -> a list of b dicts: 'boxes' [n,4], 'scores' [n], 'num_boxes',
+    'keypoint_scores' [n,17], 'keypoint_positions' [n,17,2], 'keypoints' [n,17,3] (the three keypoint arrays empty when the
+    graph has no PRN). Raises like `check_nms` when the record carries a set NMS overflow word."""
+    lib = _lib.lib()
+    first, stride = lib.mpn_pose_gather_row_offset(b, max_boxes, 0), lib.mpn_pose_gather_row_offset(b, max_boxes, 1)
+    stride -= first
+    if stride != _ROW.itemsize or len(record) < lib.mpn_pose_gather_record_bytes(b, max_boxes):
+        raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
+    header = record[:first].view(np.int32)
+    total, counts, num_boxes, overflow = int(header[0]), header[1:1 + b], header[1 + b:1 + 2 * b], int(header[1 + 2 * b])
+    if overflow != 0:
+        raise RuntimeError("mpn_retina_nms: a candidate list overflowed its workspace (MPN_ERR_WORKSPACE); the detections are incomplete")
+    rows = record[first:first + total * stride].copy().view(_ROW)      # (the pinned buffer is reused by the next call)
+    out, s = [], 0
+    for i in range(b):
+        e = s + int(counts[i])
+        r = rows[s:e]
+        p = _no_persons(num_boxes[i])
+        p.update({'boxes': np.ascontiguousarray(r['box']), 'scores': np.ascontiguousarray(r['score'])})
+        if with_keypoints:
+            p.update({k: np.ascontiguousarray(r[k]) for k in ('keypoint_scores', 'keypoint_positions', 'keypoints')})
+        out.append(p)
+        s = e
+    return out
 
 
 class Detector:
@@ -50,6 +118,7 @@ class Detector:
         self.net.cache_inference_affine = True      # inference only: the batch-norm affines change with the variables alone
         self.use_graph = True                       # the device side of a call replays from a hipGraph per image shape
         self._graphs = {}
+        self._eager_batches, self._batch_assigners = {}, {}         # predict_batch: buffers of the eager path, PRN per slot count
         self.retinanet = None
         if detector_path is not None:
             from ..retinanet import PersonDetectorNet
@@ -160,6 +229,115 @@ class Detector:
             ent[3] = ver
         graph.replay()
         return outs
+
+    # ------------------------------------------------------------------ batched inference
+    def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True):
+        """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
+
+        Arguments:
+            images: a numpy uint8 array [b, height, width, 3], or a list of b equally sized [height, width, 3] arrays.
+            score_threshold: a float number (part of the captured graph: one graph per (b, height, width, threshold)).
+            return_heatmaps: False omits 'keypoint_heatmaps' and 'segmentation_masks'; they then never leave the device.
+        Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
+        'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
+        """
+        b, h, w = check_batch(images)
+        thr = float(score_threshold)
+        ent = self._batch_entry(b, h, w, thr)
+        stage = ent['stage'].numpy()
+        if isinstance(images, np.ndarray):
+            stage[...] = images
+        else:
+            for i, im in enumerate(images):
+                stage[i] = im
+        ent['x'].copy_(ent['stage'], non_blocking=True)             # ONE host-to-device copy
+        ver = self._variable_versions()
+        if ent['graph'] is None:
+            outs = self._device_side_batch(ent['x'], thr)
+        else:
+            if ent['ver'] != ver:      # as in _replay: the host-cached affines / operand casts the captured launches read
+                self._device_side_batch(ent['x'], thr)
+                ent['ver'] = ver
+            ent['graph'].replay()
+            outs = ent['outs']
+        copies = [('record', outs.get('record'))]
+        if return_heatmaps:
+            copies += [('heat', outs['heat']), ('seg', outs['seg'])]
+        for name, src in copies:                                    # ONE device-to-host copy each, into pinned memory
+            if src is None:
+                continue
+            if name not in ent['host']:
+                ent['host'][name] = torch.empty(src.shape, dtype=src.dtype).pin_memory()
+            ent['host'][name].copy_(src, non_blocking=True)
+        torch.cuda.current_stream(self.net.device).synchronize()
+        host = ent['host']
+        if 'record' in outs:
+            persons = unpack_record(host['record'].numpy(), b, self.params['max_boxes'], self.assigner is not None)
+        else:                                                       # no detector_path: no boxes are detected
+            persons = [_no_persons() for _ in range(b)]
+        if return_heatmaps:
+            heat, seg = host['heat'].numpy().copy(), host['seg'].numpy().copy()
+            for i, p in enumerate(persons):
+                p['keypoint_heatmaps'], p['segmentation_masks'] = heat[i], seg[i]
+        return persons
+
+    def _batch_entry(self, b, h, w, thr):
+        """The persistent state of one (b, h, w, threshold): pinned staging, the device input, the captured graph and its
+        outputs. use_graph False: the same buffers, the device side runs eagerly on every call."""
+        key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
+        store = self._graphs if self.use_graph else self._eager_batches
+        ent = store.get(key)
+        if ent is not None:
+            return ent
+        dev = self.net.device
+        ent = {'stage': torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory(),
+               'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        if self.use_graph:
+            ent['x'].zero_()
+            self._device_side_batch(ent['x'], thr)                  # eager warm-up: sizes the buffers, sets kernel attributes
+            torch.cuda.synchronize(dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                ent['outs'] = self._device_side_batch(ent['x'], thr)
+            ent['graph'], ent['ver'] = graph, self._variable_versions()
+        store[key] = ent
+        return ent
+
+    def _device_side_batch(self, x, score_threshold):
+        """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
+        b * max_boxes slots (an instance of that batch size on the shared variables)."""
+        net = self.net
+        b, h, w, _ = x.shape
+        bufs = net._buffers(b, h, w)
+        feats = net.backbone_forward(x, False, bufs)
+        heat, seg = net.subnet_forward(feats, False, bufs, inference_outputs=True)
+        dev = {'heat': heat, 'seg': seg}
+        if self.retinanet is None:
+            return dev
+        pred = self._detect(feats, b, h, w)
+        max_boxes = pred['boxes'].shape[1]
+        kscore = kpos = None
+        if self.assigner is not None:
+            a = self._assigner_for(b * max_boxes)
+            crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
+            kscore, kpos = a.decode(a.net.predict(crops))
+        lib = _lib.lib()
+        nbytes = lib.mpn_pose_gather_record_bytes(b, max_boxes)
+        if nbytes == 0:
+            raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
+        record = torch.empty(nbytes, dtype=torch.uint8, device=net.device)
+        _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
+                  _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
+                  _lib.stream_ptr())
+        dev['record'] = record
+        return dev
+
+    def _assigner_for(self, n):
+        a = self._batch_assigners.get(n)
+        if a is None:
+            from ..prn_inference import KeypointAssigner
+            a = self._batch_assigners[n] = KeypointAssigner(self.assigner.net.for_batch(n), self.assigner.threshold)
+        return a
 
     def _variable_versions(self):
         return (self.net.var_version, self.retinanet.var_version if self.retinanet is not None else -1,
