@@ -763,6 +763,69 @@ size_t mpn_pose_gather_row_offset(int B, int max_boxes, int row);
 int mpn_pose_gather(const float* boxes, const float* scores, const int* num_boxes, const float* keypoint_scores,
                     const float* keypoint_positions, const int* overflow, int B, int max_boxes, float score_threshold,
                     int height, int width, void* record, size_t record_bytes, mpn_stream_t stream);
+/*   mpn_pose_gather_sized   mpn_pose_gather for images that were resized onto the network canvas: in place of the by-value
+ *                     height, width it takes extent f32 [B,4] on the DEVICE, per image (box_scale_y, box_scale_x,
+ *                     pixel_height, pixel_width). The record's box is box * (box_scale_y, box_scale_x, box_scale_y,
+ *                     box_scale_x) (one f32 multiply each), its keypoints are computed from THAT box and (pixel_height,
+ *                     pixel_width) with the arithmetic above in the same order. Same record layout, keep rule, one-block
+ *                     limit and checks (extent: MPN_ERR_BAD_ARG when null). With extent (1, 1, height, width) the record
+ *                     equals mpn_pose_gather's bit for bit. The values reach the kernel through device memory, so a
+ *                     captured graph serves any later extents. */
+int mpn_pose_gather_sized(const float* boxes, const float* scores, const int* num_boxes, const float* keypoint_scores,
+                          const float* keypoint_positions, const int* overflow, int B, int max_boxes, float score_threshold,
+                          const float* extent, void* record, size_t record_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Resize of a batch of RAGGED uint8 RGB sources onto the network canvas, equal byte for byte to Pillow's
+ * `Image.resize` of an 8-bit RGB image with its default filter (antialiased bicubic), the host step of the reference's
+ * inference/predict.ipynb (cell 6), with the top-left placement of `pad_to_bounding_box`
+ * (person_detector_pipeline.py:229-233) when an image is resized to less than the canvas.
+ *
+ * Pillow's resize is two separable passes of integer arithmetic over coefficient tables. The HOST builds the tables
+ * (multiposenet_amd/inference/resample.py: bicubic a = -0.5, support 2*max(in/out, 1), float64 weights normalised by
+ * their sum, fixed point with 22 fractional bits); the device computes, per pass and per byte,
+ *     clip8((sum_k pixel[first + k] * coeff[k] + 2^21) >> 22)         in int32
+ * horizontal pass first, its result ROUNDED TO uint8 (the intermediate), then the vertical pass. A pass whose input
+ * and output sizes are equal is a copy (Pillow skips it: the same bytes).
+ *
+ *   sources    concatenated uint8 images [src_h, src_w, 3]; image b starts at byte src_offset. A pixel is read as one
+ *              (unaligned) dword: the buffer must be readable 1 byte past its last image.
+ *   tables     int32 words; of an axis with `out` outputs: bounds [out,2] = (first tap, tap count) at word bounds_*,
+ *              coeffs [out,ksize_*] at word coeffs_*. 16-byte aligned.
+ *   descs      [B] mpn_image_resize_desc, DEVICE, 16-byte aligned
+ *   out_u8     [B,H,W,3] uint8, 16-byte aligned. EVERY byte is written: zero outside new_h x new_w.
+ *   workspace  the uint8 intermediates: image b's [src_h rows of tmp_stride bytes] at byte tmp_offset (a multiple of 16;
+ *              tmp_stride = new_w*3 rounded up to 16). 16-byte aligned. An image whose intermediate does not fit
+ *              workspace_bytes, or whose new_h x new_w exceeds H x W, or whose ksize exceeds the maximum, is written as
+ *              zeros: no descriptor makes the kernels WRITE outside workspace or out_u8. What they READ (offsets and
+ *              sizes inside sources and tables) is the caller's to check.
+ * Two launches (horizontal, vertical). Grid and block sizes depend on (B, H, W) alone; source sizes, tap counts and
+ * offsets reach the kernels through device memory, so a captured graph serves any later mix of sources that fits its
+ * buffers. Tap loops are bounded by the descriptor, up to MPN_IMAGE_RESIZE_MAX_KSIZE taps (a 16x reduction).
+ * mpn_image_resize_workspace_bytes(B, H, W, src_rows): bytes that hold the intermediates of B images whose src_h sum to
+ * src_rows (0 for arguments out of range).
+ * Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535, H, W >= 1, W*3 a multiple of 16
+ * (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); workspace_bytes >= 16 (MPN_ERR_WORKSPACE).
+ */
+#define MPN_IMAGE_RESIZE_MAX_KSIZE 65
+#define MPN_IMAGE_RESIZE_DESC_BYTES 64
+typedef struct mpn_image_resize_desc {
+    int64_t src_offset;                         /* byte offset into sources */
+    int64_t tmp_offset;                         /* byte offset of the intermediate in workspace, multiple of 16 */
+    int32_t src_h, src_w, new_h, new_w;
+    int32_t bounds_x, coeffs_x;                 /* word offsets into tables: src_w -> new_w */
+    int32_t bounds_y, coeffs_y;                 /* src_h -> new_h */
+    int32_t ksize_x, ksize_y;                   /* row lengths of coeffs_x / coeffs_y */
+    int32_t tmp_stride;                         /* bytes of an intermediate row: new_w*3 rounded up to 16 */
+    int32_t reserved;
+} mpn_image_resize_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_image_resize_desc) == MPN_IMAGE_RESIZE_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_image_resize_desc_bytes(void);
+size_t mpn_image_resize_workspace_bytes(int B, int H, int W, long long src_rows);
+int mpn_image_resize(const uint8_t* sources, const int32_t* tables, const void* descs, int B, int H, int W,
+                     uint8_t* out_u8, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
 #ifdef __cplusplus
 }

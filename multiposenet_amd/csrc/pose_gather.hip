@@ -3,6 +3,8 @@
 //   mpn_pose_gather   padded per-slot outputs of B images (NMS boxes / scores / counts, PRN keypoint scores / positions)
 //                     -> ONE contiguous record: int32 header {total, counts[B], num_boxes[B], overflow} and B * max_boxes
 //                     rows in (image, slot) order, kept rows first and dense, the rest zero.
+//   mpn_pose_gather_sized   the same kernel body (template flag) for images resized onto the network canvas: per-image box
+//                     scales and pixel sizes come from device memory (`extent`), the box is scaled to the source image first.
 // A row is kept iff slot < num_boxes[image] and score > score_threshold. B * max_boxes is small (25 x 64 = 1 600 at the largest
 // batch worth supporting): ONE block; a ballot / popcount exclusive scan over the keep flags (wave totals through LDS, in wave
 // order: the destination of a row is a function of the flags alone - no atomics), then a cooperative copy in 16-byte stores.
@@ -32,14 +34,24 @@ struct GatherArgs {
     const float* kscores;
     const float* kpos;
     const int* overflow;
+    const float* extent;        // kSized: [B,4] (box_scale_y, box_scale_x, pixel_height, pixel_width); else height / width below
     float threshold, height, width;
     int B, max_boxes, header_words;
 };
 
+// coordinate j (ymin, xmin, ymax, xmax) of the record's box of slot r: mpn_pose_gather_sized scales it to the source image
+template <bool kSized>
+__device__ __forceinline__ float box_out(const GatherArgs& a, int r, int j) {
+    const float v = a.boxes[r * 4 + j];
+    if (!kSized) return v;
+    return v * a.extent[(r / a.max_boxes) * 4 + (j & 1)];
+}
+
 // word f of the record row of source slot r
+template <bool kSized>
 __device__ __forceinline__ unsigned row_word(const GatherArgs& a, int r, int f) {
     if (f == 0) return (unsigned)(r / a.max_boxes);
-    if (f < kOffScore) return __float_as_uint(a.boxes[r * 4 + (f - kOffBox)]);
+    if (f < kOffScore) return __float_as_uint(box_out<kSized>(a, r, f - kOffBox));
     if (f == kOffScore) return __float_as_uint(a.scores[r]);
     if (f < kOffKPos) return a.kscores ? __float_as_uint(a.kscores[r * kK + (f - kOffKScore)]) : 0u;
     if (f < kOffKeypoints) return a.kpos ? __float_as_uint(a.kpos[r * 2 * kK + (f - kOffKPos)]) : 0u;
@@ -47,15 +59,16 @@ __device__ __forceinline__ unsigned row_word(const GatherArgs& a, int r, int f) 
     if (c == 2) return a.kscores ? __float_as_uint(a.kscores[r * kK + k]) : 0u;
     if (!a.kpos) return 0u;
     // inference/predict.ipynb, draw_everything: x = xmin * width + pos_x * (xmax * width - xmin * width); positions are (y, x)
-    const float size = c == 0 ? a.width : a.height;
-    const float lo = a.boxes[r * 4 + (1 - c)] * size;
-    const float hi = a.boxes[r * 4 + (3 - c)] * size;
+    const float size = kSized ? a.extent[(r / a.max_boxes) * 4 + 3 - c] : (c == 0 ? a.width : a.height);
+    const float lo = box_out<kSized>(a, r, 1 - c) * size;
+    const float hi = box_out<kSized>(a, r, 3 - c) * size;
     const float p = a.kpos[(r * kK + k) * 2 + (1 - c)];
     const float span = hi - lo;
     const float off = p * span;
     return __float_as_uint(lo + off);
 }
 
+template <bool kSized>
 __global__ __launch_bounds__(kThreads) void pose_gather_kernel(GatherArgs a, int* __restrict__ header, uint4* __restrict__ rows) {
     __shared__ int before[kMaxRows + 1];    // kept rows ahead of row r (exclusive scan; [n] = total)
     __shared__ int source[kMaxRows];        // record row j <- source slot
@@ -105,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void pose_gather_kernel(GatherArgs a, int
         uint4 o = make_uint4(0u, 0u, 0u, 0u);
         if (j < total) {
             const int r = source[j];
-            o = make_uint4(row_word(a, r, f), row_word(a, r, f + 1), row_word(a, r, f + 2), row_word(a, r, f + 3));
+            o = make_uint4(row_word<kSized>(a, r, f), row_word<kSized>(a, r, f + 1), row_word<kSized>(a, r, f + 2), row_word<kSized>(a, r, f + 3));
         }
         rows[v] = o;
     }
@@ -133,11 +146,31 @@ extern "C" int mpn_pose_gather(const float* boxes, const float* scores, const in
     MPN_REQUIRE(mpn_aligned16(record), MPN_ERR_BAD_ALIGN, "pose_gather: record must be 16-byte aligned");
     MPN_REQUIRE(record_bytes >= mpn_pose_gather_record_bytes(B, max_boxes), MPN_ERR_WORKSPACE,
                 "pose_gather: record of %zu bytes, %zu needed", record_bytes, mpn_pose_gather_record_bytes(B, max_boxes));
-    GatherArgs a = {boxes, scores, num_boxes, keypoint_scores, keypoint_positions, overflow, score_threshold, (float)height,
+    GatherArgs a = {boxes, scores, num_boxes, keypoint_scores, keypoint_positions, overflow, nullptr, score_threshold, (float)height,
                     (float)width, B, max_boxes, (int)header_words(B)};
     int* header = (int*)record;
     uint4* rows = (uint4*)((char*)record + mpn_pose_gather_row_offset(B, max_boxes, 0));
-    pose_gather_kernel<<<1, kThreads, 0, (hipStream_t)stream>>>(a, header, rows);
+    pose_gather_kernel<false><<<1, kThreads, 0, (hipStream_t)stream>>>(a, header, rows);
+    MPN_LAUNCH_CHECK();
+    return MPN_OK;
+}
+
+extern "C" int mpn_pose_gather_sized(const float* boxes, const float* scores, const int* num_boxes, const float* keypoint_scores,
+                                     const float* keypoint_positions, const int* overflow, int B, int max_boxes,
+                                     float score_threshold, const float* extent, void* record, size_t record_bytes,
+                                     mpn_stream_t stream) {
+    MPN_REQUIRE(boxes && scores && num_boxes && record && extent, MPN_ERR_BAD_ARG, "pose_gather_sized: null pointer");
+    MPN_REQUIRE(B >= 1 && max_boxes >= 1, MPN_ERR_BAD_SHAPE, "pose_gather_sized: bad shape");
+    MPN_REQUIRE((long long)B * max_boxes <= kMaxRows, MPN_ERR_BAD_SHAPE,
+                "pose_gather_sized: B * max_boxes = %lld rows, the single block covers %d", (long long)B * max_boxes, kMaxRows);
+    MPN_REQUIRE(mpn_aligned16(record), MPN_ERR_BAD_ALIGN, "pose_gather_sized: record must be 16-byte aligned");
+    MPN_REQUIRE(record_bytes >= mpn_pose_gather_record_bytes(B, max_boxes), MPN_ERR_WORKSPACE,
+                "pose_gather_sized: record of %zu bytes, %zu needed", record_bytes, mpn_pose_gather_record_bytes(B, max_boxes));
+    GatherArgs a = {boxes, scores, num_boxes, keypoint_scores, keypoint_positions, overflow, extent, score_threshold, 0.f, 0.f,
+                    B, max_boxes, (int)header_words(B)};
+    int* header = (int*)record;
+    uint4* rows = (uint4*)((char*)record + mpn_pose_gather_row_offset(B, max_boxes, 0));
+    pose_gather_kernel<true><<<1, kThreads, 0, (hipStream_t)stream>>>(a, header, rows);
     MPN_LAUNCH_CHECK();
     return MPN_OK;
 }

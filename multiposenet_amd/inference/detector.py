@@ -12,6 +12,7 @@ import torch
 
 from .. import _lib
 from ..net import KeypointNet
+from . import resample
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -119,6 +120,7 @@ class Detector:
         self.use_graph = True                       # the device side of a call replays from a hipGraph per image shape
         self._graphs = {}
         self._eager_batches, self._batch_assigners = {}, {}         # predict_batch: buffers of the eager path, PRN per slot count
+        self._image_capacity = {}                                   # predict_images: buffer capacities per (b, h, w, threshold)
         self.retinanet = None
         if detector_path is not None:
             from ..retinanet import PersonDetectorNet
@@ -260,6 +262,11 @@ class Detector:
                 ent['ver'] = ver
             ent['graph'].replay()
             outs = ent['outs']
+        return self._finish(ent, outs, b, return_heatmaps)
+
+    def _finish(self, ent, outs, b, return_heatmaps):
+        """The host side behind the device side of predict_batch / predict_images: the record (and the maps) into pinned
+        memory, one synchronise, the record unpacked into b dicts."""
         copies = [('record', outs.get('record'))]
         if return_heatmaps:
             copies += [('heat', outs['heat']), ('seg', outs['seg'])]
@@ -303,9 +310,10 @@ class Detector:
         store[key] = ent
         return ent
 
-    def _device_side_batch(self, x, score_threshold):
+    def _device_side_batch(self, x, score_threshold, extent=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
-        b * max_boxes slots (an instance of that batch size on the shared variables)."""
+        b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
+        the device; the last launch is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images."""
         net = self.net
         b, h, w, _ = x.shape
         bufs = net._buffers(b, h, w)
@@ -326,11 +334,111 @@ class Detector:
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
         record = torch.empty(nbytes, dtype=torch.uint8, device=net.device)
-        _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
-                  _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
-                  _lib.stream_ptr())
+        if extent is None:
+            _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
+                      _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
+                      _lib.stream_ptr())
+        else:
+            _lib.call("mpn_pose_gather_sized", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']),
+                      _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
+                      _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
         dev['record'] = record
         return dev
+
+    # ------------------------------------------------------------------ ragged frames: on-device resize
+    def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False):
+        """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
+        Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
+        byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
+
+        Arguments:
+            images: a list of b >= 1 uint8 arrays [h_i, w_i, 3]; the sizes may all differ and need not be multiples of anything.
+            size: (height, width) of the network input, both multiples of 128.
+            keep_aspect_ratio: False resizes every image to exactly `size` (the notebook). True resizes image i to
+                new_h x new_w, s = min(height / h_i, width / w_i), new_h = max(1, round(h_i * s)), new_w = max(1, round(w_i * s))
+                (float64, Python's `round`), placed at the top left of a zero canvas (`pad_to_bounding_box`).
+            score_threshold: a float number (part of the captured graph).
+            return_heatmaps: True adds 'keypoint_heatmaps' [height/4, width/4, 17] and 'segmentation_masks' of the network
+                CANVAS and 'resized_size': (new_h, new_w), the part of the canvas the image covers.
+        Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
+        (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
+        them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
+        raises ValueError.
+        """
+        items = resample.check_images(images)
+        height, width = resample.check_size(size)
+        plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
+        b, thr = len(items), float(score_threshold)
+        ent = self._images_entry(b, height, width, thr, plan)
+        stage = ent['stage'].numpy()
+        for im, at in zip(items, plan.src_offsets):
+            stage[at:at + im.size] = im.reshape(-1)
+        ent['meta_stage'].numpy()[:plan.meta_words] = plan.meta
+        nb, nw = plan.stage_bytes, plan.meta_words                  # this batch's bytes, not the buffers' capacity
+        ent['sources'][:nb].copy_(ent['stage'][:nb], non_blocking=True)      # ONE host-to-device copy of the frames,
+        ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)    # one of the descriptors, extents and tables
+        ver = self._variable_versions()
+        if not self.use_graph:
+            outs = self._device_side_images(ent, thr)
+        else:
+            if ent['graph'] is None:   # captured over THIS call's descriptors: the warm-up runs the kernels for real
+                self._device_side_images(ent, thr)
+                torch.cuda.synchronize(self.net.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    ent['outs'] = self._device_side_images(ent, thr)
+                ent['graph'], ent['ver'] = graph, ver
+            elif ent['ver'] != ver:    # as in predict_batch
+                self._device_side_images(ent, thr)
+                ent['ver'] = ver
+            ent['graph'].replay()
+            outs = ent['outs']
+        persons = self._finish(ent, outs, b, return_heatmaps)
+        if return_heatmaps:
+            for p, new_size in zip(persons, plan.new_sizes):
+                p['resized_size'] = new_size
+        return persons
+
+    def _images_entry(self, b, h, w, thr, plan):
+        """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
+        of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
+        graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
+        exceeds it gets larger buffers and a new graph."""
+        store = self._graphs if self.use_graph else self._eager_batches
+        need = (plan.stage_bytes, plan.meta_words, plan.work_bytes)
+        base = ('images', b, h, w, thr)
+        cap = self._image_capacity.get((base, self.use_graph))
+        if cap is None or any(n > c for n, c in zip(need, cap)):
+            if cap is not None:
+                store.pop(base + (cap,), None)      # superseded: its buffers and graph are never looked up again
+            cap = tuple(resample.capacity_for(max(n, c)) for n, c in zip(need, cap or (0, 0, 0)))
+            self._image_capacity[(base, self.use_graph)] = cap
+        key = base + (cap,)
+        ent = store.get(key)
+        if ent is not None:
+            return ent
+        dev = self.net.device
+        stage_bytes, meta_words, work_bytes = cap
+        if _lib.lib().mpn_image_resize_desc_bytes() != resample.DESC_WORDS * 4:
+            raise _lib.MpnError("mpn_image_resize: the descriptor's layout is not the one this binding was written against")
+        ent = {'stage': torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
+               'sources': torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
+               'meta_stage': torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
+               'meta': torch.zeros(meta_words, dtype=torch.int32, device=dev),
+               'work': torch.empty(work_bytes, dtype=torch.uint8, device=dev),
+               'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        store[key] = ent
+        return ent
+
+    def _device_side_images(self, ent, thr):
+        """mpn_image_resize (ragged sources -> the uint8 canvas batch) -> _device_side_batch with mpn_pose_gather_sized last."""
+        x, meta = ent['x'], ent['meta']
+        b, h, w, _ = x.shape
+        extent = meta[b * resample.DESC_WORDS:b * (resample.DESC_WORDS + 4)].view(torch.float32).view(b, 4)
+        tables = meta[b * (resample.DESC_WORDS + 4):]
+        _lib.call("mpn_image_resize", _lib.ptr(ent['sources']), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
+                  _lib.ptr(ent['work']), ent['work'].numel(), _lib.stream_ptr())
+        return self._device_side_batch(x, thr, extent)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)
