@@ -827,6 +827,64 @@ size_t mpn_image_resize_workspace_bytes(int B, int H, int W, long long src_rows)
 int mpn_image_resize(const uint8_t* sources, const int32_t* tables, const void* descs, int B, int H, int W,
                      uint8_t* out_u8, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Annotated frames: `draw_everything` of the reference's inference/predict.ipynb (cells 10 and 12) for a batch of RAGGED
+ * uint8 RGB frames and the persons of mpn_pose_gather[_sized]'s record, equal byte for byte to what Pillow draws there.
+ *
+ * out = the frame as RGBA with alpha 255; then per KEPT person of the record, in record order: the box outline in red
+ * (255,0,0,255), the 16 skeleton lines in white (255,255,255,255), one pixel wide, and the 17 keypoints as red dots, each an
+ * opaque overwrite of what was drawn before, clipped to the frame per pixel. Coordinates are the notebook's numpy arithmetic,
+ * recomputed from the record's box and keypoint_positions (NOT its float32 `keypoints`, which round differently):
+ *     (ymin, xmin, ymax, xmax) = (h, w, h, w) * box                               float64
+ *     x = f32(f64(f32(f64(pos_x) * (xmax - xmin))) + xmin), y likewise            float64 results rounded to float32
+ *     dot corners  x - 2, x + 2 (float32)
+ * each converted to int by truncation toward zero (Pillow). Integer rasterisation:
+ *     rectangle  rows y0 and y1 over x0..x1, columns x0 and x1 between them; a box with y1 == y0 also sets (x0, y0+1) and
+ *                (x1, y0+1), as Pillow does; a box with x1 < x0 or y1 < y0 (Pillow raises) is not drawn
+ *     line       Bresenham from the first point, end point included: at step i of the major axis the minor axis has moved
+ *                floor((2*m*i + n) / (2*n)) steps, n = max(|dx|, |dy|), m = min(|dx|, |dy|)
+ *     dot        over corners (x0,y0)-(x1,y1), x1-x0 and y1-y0 in {3, 4}: row j = bits MPN_DRAW_DOT_STAMPS
+ *                [(x1-x0-3)*2 + (y1-y0-3)][j], bit i = pixel x0+i (mpn_draw_dot_stamp; -1 outside the table). Other
+ *                differences need |x| beyond 2^22 and are not drawn.
+ * Coordinates are clamped to +-2^29 first.
+ *
+ *   sources     concatenated uint8 images [h, w, 3]; image b starts at byte src_offset (no alignment needed). A [B,h,w,3]
+ *               batch is the same with src_offset = b*h*w*3.
+ *   descs       [B] mpn_draw_desc, DEVICE, 16-byte aligned
+ *   record      mpn_pose_gather's record for (B, max_boxes), DEVICE, 16-byte aligned: the header's total and counts and
+ *               the rows' image_index, box and keypoint_positions are read (clamped to the record's capacity)
+ *   with_keypoints  0: boxes only (a record made without keypoint positions)
+ *   out_rgba    image b's uint8 [h, w, 4] at byte out_offset, a multiple of 16; written in 16-byte vectors: h*w*4 rounded
+ *               up to 16 bytes are written. 16-byte aligned.
+ *   workspace   mpn_draw_detections_workspace_bytes(B, max_boxes) bytes (0 for arguments out of range), 16-byte aligned
+ * An image whose descriptor reaches outside sources_bytes / out_bytes, or has h, w outside [1, 65536] or h*w > 2^29, is left
+ * unwritten: no descriptor makes the kernels read outside sources or write outside out_rgba.
+ * Two launches: the primitives of every kept person (one thread each), then a gather - a pixel's colour is the last
+ * primitive in draw order that covers it, else the source; nothing scatters, the output is deterministic. Grid and block
+ * sizes depend on (B, max_boxes) alone, so a captured graph serves any later batch that fits its buffers.
+ * Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535, 1 <= max_boxes <= MPN_DRAW_MAX_BOXES,
+ * B*max_boxes <= 4096 (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); record_bytes, workspace_bytes, sources_bytes >= 3,
+ * out_bytes >= 16 (MPN_ERR_WORKSPACE).
+ */
+#define MPN_DRAW_MAX_BOXES 128
+#define MPN_DRAW_DESC_BYTES 32
+#define MPN_DRAW_DOT_STAMPS {{6, 15, 15, 6, 0}, {6, 15, 15, 15, 6}, {14, 31, 31, 14, 0}, {14, 31, 31, 31, 14}}
+typedef struct mpn_draw_desc {
+    int64_t src_offset;                         /* byte offset into sources */
+    int64_t out_offset;                         /* byte offset into out_rgba, multiple of 16 */
+    int32_t h, w;
+    int32_t reserved[2];
+} mpn_draw_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_draw_desc) == MPN_DRAW_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_draw_desc_bytes(void);
+int mpn_draw_dot_stamp(int dw, int dh, int row);
+size_t mpn_draw_detections_workspace_bytes(int B, int max_boxes);
+int mpn_draw_detections(const uint8_t* sources, size_t sources_bytes, const void* descs, const void* record,
+                        size_t record_bytes, int B, int max_boxes, int with_keypoints, uint8_t* out_rgba, size_t out_bytes,
+                        void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

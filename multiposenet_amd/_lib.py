@@ -145,6 +145,10 @@ SIGNATURES = {
     "mpn_image_resize_desc_bytes": (_Z, []),
     "mpn_image_resize_workspace_bytes": (_Z, [_I, _I, _I, _L]),
     "mpn_image_resize": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "mpn_draw_desc_bytes": (_Z, []),
+    "mpn_draw_dot_stamp": (_I, [_I, _I, _I]),
+    "mpn_draw_detections_workspace_bytes": (_Z, [_I, _I]),
+    "mpn_draw_detections": (_I, [_P, _Z, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _Z, _P]),
 }
 
 _lib = None

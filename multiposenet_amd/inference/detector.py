@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib
 from ..net import KeypointNet
-from . import resample
+from . import draw, resample
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -233,19 +233,22 @@ class Detector:
         return outs
 
     # ------------------------------------------------------------------ batched inference
-    def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True):
+    def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
             images: a numpy uint8 array [b, height, width, 3], or a list of b equally sized [height, width, 3] arrays.
             score_threshold: a float number (part of the captured graph: one graph per (b, height, width, threshold)).
             return_heatmaps: False omits 'keypoint_heatmaps' and 'segmentation_masks'; they then never leave the device.
+            annotate: True adds 'annotated', a uint8 [height, width, 4] RGBA array: the image with that dict's persons drawn on
+                it as inference/predict.ipynb's `draw_everything` draws them under Pillow, byte for byte (drawn on the device
+                inside the captured graph: a graph of its own per (b, height, width, threshold)).
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         b, h, w = check_batch(images)
         thr = float(score_threshold)
-        ent = self._batch_entry(b, h, w, thr)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate))
         stage = ent['stage'].numpy()
         if isinstance(images, np.ndarray):
             stage[...] = images
@@ -255,10 +258,10 @@ class Detector:
         ent['x'].copy_(ent['stage'], non_blocking=True)             # ONE host-to-device copy
         ver = self._variable_versions()
         if ent['graph'] is None:
-            outs = self._device_side_batch(ent['x'], thr)
+            outs = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
         else:
             if ent['ver'] != ver:      # as in _replay: the host-cached affines / operand casts the captured launches read
-                self._device_side_batch(ent['x'], thr)
+                self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
                 ent['ver'] = ver
             ent['graph'].replay()
             outs = ent['outs']
@@ -276,6 +279,11 @@ class Detector:
             if name not in ent['host']:
                 ent['host'][name] = torch.empty(src.shape, dtype=src.dtype).pin_memory()
             ent['host'][name].copy_(src, non_blocking=True)
+        if 'annotated' in outs:                                     # this batch's bytes of the packed frames, not the capacity
+            if 'annotated' not in ent['host']:
+                ent['host']['annotated'] = torch.empty(outs['annotated'].shape, dtype=torch.uint8).pin_memory()
+            nb = ent['draw'].out_bytes
+            ent['host']['annotated'][:nb].copy_(outs['annotated'][:nb], non_blocking=True)
         torch.cuda.current_stream(self.net.device).synchronize()
         host = ent['host']
         if 'record' in outs:
@@ -286,12 +294,17 @@ class Detector:
             heat, seg = host['heat'].numpy().copy(), host['seg'].numpy().copy()
             for i, p in enumerate(persons):
                 p['keypoint_heatmaps'], p['segmentation_masks'] = heat[i], seg[i]
+        if 'annotated' in outs:
+            for p, frame in zip(persons, ent['draw'].unpack(host['annotated'].numpy())):
+                p['annotated'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr):
-        """The persistent state of one (b, h, w, threshold): pinned staging, the device input, the captured graph and its
-        outputs. use_graph False: the same buffers, the device side runs eagerly on every call."""
+    def _batch_entry(self, b, h, w, thr, annotate=False):
+        """The persistent state of one (b, h, w, threshold[, annotate]): pinned staging, the device input, the captured graph and
+        its outputs. use_graph False: the same buffers, the device side runs eagerly on every call."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
+        if annotate:
+            key += ('annotate',)
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -299,28 +312,37 @@ class Detector:
         dev = self.net.device
         ent = {'stage': torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory(),
                'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        if annotate:                                                # the frames are the batch itself: fixed descriptors
+            ent['draw'] = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
+            ent['draw'].place([(h, w)] * b, [i * h * w * 3 for i in range(b)])
         if self.use_graph:
             ent['x'].zero_()
-            self._device_side_batch(ent['x'], thr)                  # eager warm-up: sizes the buffers, sets kernel attributes
+            self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))    # eager warm-up: sizes the buffers, sets kernel attributes
             torch.cuda.synchronize(dev)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                ent['outs'] = self._device_side_batch(ent['x'], thr)
+                ent['outs'] = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
             ent['graph'], ent['ver'] = graph, self._variable_versions()
         store[key] = ent
         return ent
 
-    def _device_side_batch(self, x, score_threshold, extent=None):
+    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
-        the device; the last launch is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images."""
+        the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
+        draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat uint8; default:
+        the batch x itself) -> 'annotated', the packed RGBA frames."""
         net = self.net
         b, h, w, _ = x.shape
         bufs = net._buffers(b, h, w)
         feats = net.backbone_forward(x, False, bufs)
         heat, seg = net.subnet_forward(feats, False, bufs, inference_outputs=True)
         dev = {'heat': heat, 'seg': seg}
+        if annotate is not None and frames is None:
+            frames = x.view(-1)
         if self.retinanet is None:
+            if annotate is not None:                                # no detector: the frames with alpha 255
+                dev['annotated'] = annotate.launch(frames, None, False)
             return dev
         pred = self._detect(feats, b, h, w)
         max_boxes = pred['boxes'].shape[1]
@@ -343,10 +365,13 @@ class Detector:
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
         dev['record'] = record
+        if annotate is not None:
+            dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
         return dev
 
     # ------------------------------------------------------------------ ragged frames: on-device resize
-    def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False):
+    def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
+                       annotate=False):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -360,6 +385,9 @@ class Detector:
             score_threshold: a float number (part of the captured graph).
             return_heatmaps: True adds 'keypoint_heatmaps' [height/4, width/4, 17] and 'segmentation_masks' of the network
                 CANVAS and 'resized_size': (new_h, new_w), the part of the canvas the image covers.
+            annotate: True adds 'annotated', a uint8 [h_i, w_i, 4] RGBA array: the SOURCE frame at its own size with that
+                dict's persons drawn on it as inference/predict.ipynb's `draw_everything` draws them under Pillow, byte for
+                byte (drawn on the device inside the captured graph, from the frames already uploaded for the resize).
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -369,7 +397,7 @@ class Detector:
         height, width = resample.check_size(size)
         plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
         b, thr = len(items), float(score_threshold)
-        ent = self._images_entry(b, height, width, thr, plan)
+        ent = self._images_entry(b, height, width, thr, plan, bool(annotate))
         stage = ent['stage'].numpy()
         for im, at in zip(items, plan.src_offsets):
             stage[at:at + im.size] = im.reshape(-1)
@@ -377,6 +405,8 @@ class Detector:
         nb, nw = plan.stage_bytes, plan.meta_words                  # this batch's bytes, not the buffers' capacity
         ent['sources'][:nb].copy_(ent['stage'][:nb], non_blocking=True)      # ONE host-to-device copy of the frames,
         ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)    # one of the descriptors, extents and tables
+        if annotate:
+            ent['draw'].place(plan.sizes, plan.src_offsets)
         ver = self._variable_versions()
         if not self.use_graph:
             outs = self._device_side_images(ent, thr)
@@ -399,21 +429,24 @@ class Detector:
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
-        exceeds it gets larger buffers and a new graph."""
+        exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
+        output sized from the capacity of the sources - it grows with them."""
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes)
         base = ('images', b, h, w, thr)
-        cap = self._image_capacity.get((base, self.use_graph))
+        tail = ('annotate',) if annotate else ()
+        cap_key = (base, self.use_graph) + tail
+        cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
             if cap is not None:
-                store.pop(base + (cap,), None)      # superseded: its buffers and graph are never looked up again
+                store.pop(base + (cap,) + tail, None)      # superseded: its buffers and graph are never looked up again
             cap = tuple(resample.capacity_for(max(n, c)) for n, c in zip(need, cap or (0, 0, 0)))
-            self._image_capacity[(base, self.use_graph)] = cap
-        key = base + (cap,)
+            self._image_capacity[cap_key] = cap
+        key = base + (cap,) + tail
         ent = store.get(key)
         if ent is not None:
             return ent
@@ -427,6 +460,8 @@ class Detector:
                'meta': torch.zeros(meta_words, dtype=torch.int32, device=dev),
                'work': torch.empty(work_bytes, dtype=torch.uint8, device=dev),
                'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        if annotate:
+            ent['draw'] = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
         store[key] = ent
         return ent
 
@@ -438,7 +473,7 @@ class Detector:
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent['sources']), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent['work']), ent['work'].numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent)
+        return self._device_side_batch(x, thr, extent, annotate=ent.get('draw'), frames=ent['sources'])
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

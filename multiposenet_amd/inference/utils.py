@@ -1,9 +1,11 @@
-"""Heatmap peak decode - same surface as the reference's `inference/utils.py`.
+"""Heatmap peak decode and detection drawing - the surface of the reference's `inference/utils.py`.
 
 `get_keypoints(heatmaps, box, threshold)` keeps the signature and result of
 inference/utils.py:29-52; the arithmetic (per-channel max, first-occurrence argmax,
 threshold, scaling into the box) runs in the HIP kernel `mpn_heatmap_decode`.
 `get_keypoints_batch` is the batched device-resident form the training/serving loop uses.
+`draw_everything(image, outputs)` is the drawing of inference/predict.ipynb (the version that runs; utils.py's own variant
+composites an undefined `Image` and cannot) through the HIP kernel `mpn_draw_detections`.
 """
 import numpy as np
 
@@ -123,3 +125,48 @@ def get_keypoints(heatmaps, box, threshold):
         raise ValueError(f"heatmaps must have shape [h, w, 17], got {heatmaps.shape}")
     xyv = get_keypoints_batch(heatmaps[None], np.asarray(box)[None], threshold)
     return xyv[0].cpu().numpy()
+
+
+def draw_everything(image, outputs):
+    """
+    The notebook's `draw_everything` (inference/predict.ipynb, cells 10 and 12) for one frame, drawn on the device: equal byte
+    for byte to what the notebook draws with Pillow.
+
+    Arguments:
+        image: a uint8 array with shape [height, width, 3], or anything `np.asarray` turns into one (a PIL image).
+        outputs: a dict with 'boxes' [n, 4] (normalised ymin, xmin, ymax, xmax) and 'keypoint_positions' [n, 17, 2] ((y, x)
+            normalised to the box; no rows at all: boxes only), as `Detector.__call__` returns them.
+    Returns:
+        a numpy uint8 array with shape [height, width, 4]: RGBA, alpha 255.
+    """
+    import torch
+    from . import draw
+    from .detector import _ROW
+    image = np.ascontiguousarray(np.asarray(image))
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"image must be uint8 [height, width, 3] (got {image.dtype} {tuple(image.shape)})")
+    boxes = np.asarray(outputs['boxes'], np.float32).reshape(-1, 4)
+    pos = np.asarray(outputs['keypoint_positions'], np.float32).reshape(-1, NUM_KEYPOINTS, 2)
+    n = len(boxes)
+    if len(pos) not in (0, n):
+        raise ValueError(f"{n} boxes but {len(pos)} rows of keypoint_positions")
+    if n > draw.MAX_BOXES:
+        raise ValueError(f"draw_everything draws at most {draw.MAX_BOXES} persons (got {n})")
+    lib = _lib.lib()
+    slots = max(n, 1)
+    first, size = lib.mpn_pose_gather_row_offset(1, slots, 0), lib.mpn_pose_gather_record_bytes(1, slots)
+    if size != first + slots * _ROW.itemsize:
+        raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
+    record = np.zeros(size, np.uint8)
+    record[:8].view(np.int32)[:] = (n, n)                                   # total, counts[0]
+    rows = record[first:].view(_ROW)
+    rows['box'][:n] = boxes
+    if len(pos):
+        rows['keypoint_positions'][:n] = pos
+    device = _lib.current_device()
+    with torch.cuda.device(device):
+        h, w = image.shape[:2]
+        buffers = draw.Buffers(1, slots, h * w * 3, device)
+        buffers.place([(h, w)], [0])
+        out = buffers.launch(torch.from_numpy(image.reshape(-1)).to(device), torch.from_numpy(record).to(device), len(pos) > 0)
+        return buffers.unpack(out[:buffers.out_bytes].cpu().numpy())[0]
