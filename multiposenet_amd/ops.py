@@ -420,7 +420,10 @@ def _bn_group_args(bns, dAs, xs):
     PA, LA, IA = ctypes.c_void_p * n, ctypes.c_longlong * n, ctypes.c_int * n
     C = xs[0].shape[-1]
     Ms = [x.numel() // x.shape[-1] for x in xs]
-    strides = (IA(*[_row_stride(t, C) for t in dAs]), IA(*[_row_stride(t, C) for t in xs]))   # channel slices allowed
+    sd, sx = [_row_stride(t, C) for t in dAs], [_row_stride(t, C) for t in xs]                # channel slices allowed
+    # all dense: no stride tables - channel counts the shared grid does not cover (24: kThreads % (C / vector) != 0) then take the
+    # library's per-layer launches instead of being refused for strides nobody asked for
+    strides = (None, None) if all(s == C for s in sd + sx) else (IA(*sd), IA(*sx))
     return n, PA, PA(*[ptr(t) for t in dAs]), PA(*[ptr(t) for t in xs]), LA(*Ms), C, _lib.dtype_code(xs[0].dtype), strides
 
 
