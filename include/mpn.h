@@ -37,7 +37,8 @@ enum {
     MPN_ERR_BAD_ALIGN = -3,
     MPN_ERR_HIP = -4,
     MPN_ERR_BAD_ARG = -5,
-    MPN_ERR_WORKSPACE = -6
+    MPN_ERR_WORKSPACE = -6,
+    MPN_ERR_BAD_DATA = -7   /* host stages that parse a byte stream: the stream is damaged or not supported */
 };
 
 /* activation applied after the batch-norm affine */
@@ -884,6 +885,94 @@ size_t mpn_draw_detections_workspace_bytes(int B, int max_boxes);
 int mpn_draw_detections(const uint8_t* sources, size_t sources_bytes, const void* descs, const void* record,
                         size_t record_bytes, int B, int max_boxes, int with_keypoints, uint8_t* out_rgba, size_t out_bytes,
                         void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * JPEG decode, split in two: the serial part on the HOST, the parallel part on the device. The result equals what
+ * libjpeg(-turbo) - and so Pillow's `Image.open(...).convert("RGB")` - returns for the same bytes, byte for byte.
+ *
+ * Supported (mpn_jpeg_info sets supported = 1): SOF0 / SOF1, 8-bit, Huffman coded, ONE interleaved scan; one component
+ * (grayscale, R = G = B) or three components in YCbCr (JFIF, or what libjpeg guesses as YCbCr) with luma sampling 1x1, 2x1
+ * or 2x2 and chroma 1x1; restart intervals; custom Huffman tables; any size from 1x1 to 65535 per side and 2^28 pixels.
+ * Everything else is CLASSIFIED (supported = 0 and a reason) and left to a library: progressive, arithmetic, lossless /
+ * hierarchical frames, 12-bit precision, 2 or 4 components (CMYK / YCCK), an Adobe marker with a transform other than 1
+ * or 'R','G','B' component ids, other sampling (4:4:0, 4:1:1, ...), several scans, 16-bit quantisation tables.
+ *
+ * HOST (no HIP call, no global state: thread-safe and re-entrant; nothing is read past nbytes or written past coef_bytes):
+ *   mpn_jpeg_info            scans the markers up to the first scan. MPN_OK for every stream it can classify (supported or
+ *                            not); MPN_ERR_BAD_DATA (reason MPN_JPEG_MALFORMED) when the headers are damaged.
+ *   mpn_jpeg_entropy_decode  Huffman-decodes the scan of a SUPPORTED stream into `coefs` (host): every 8x8 block of every
+ *                            component as 64 RAW (not dequantised) int16 coefficients in natural (row-major) order, one
+ *                            plane per component behind each other, blocks in raster order over the component's PADDED
+ *                            block grid blocks_h x blocks_w (whole MCUs). Fills `desc` (host) except its three offsets.
+ *                            MPN_ERR_WORKSPACE when coef_bytes < total_blocks * 128; MPN_ERR_BAD_DATA for an unsupported
+ *                            stream, a truncated or damaged scan, a missing restart marker.
+ *
+ * DEVICE: mpn_jpeg_decode decodes one ragged batch per call, two launches:
+ *   1. dequantise + inverse DCT, libjpeg's default "slow integer" method (jidctint.c: 13-bit constants, 2 extra bits kept
+ *      after pass 1, columns first, then rows, descale (x + 2^(n-1)) >> n; +128 and the range limit through the low 10
+ *      bits, as the library's table is indexed) -> uint8 component planes [blocks_h*8, blocks_w*8] in `work`;
+ *   2. "fancy" chroma upsampling (jdsample.c: the triangle filter of h2v1 / h2v2 with its alternating rounding constants;
+ *      edges at the component's true down-sampled size ceil(width / h_samp) x ceil(height / v_samp); a chroma component at
+ *      most 2 samples wide is replicated instead, as the library does) and YCbCr -> RGB (jdcolor.c: 16-bit fixed point)
+ *      -> packed uint8 [height, width, 3] at byte src_offset of sources_out. Only the image's bytes are written.
+ *
+ *   coefs        the coefficients of the batch, DEVICE, 16-byte aligned; image b's planes start at byte coef_offset
+ *   descs        [B] mpn_jpeg_desc, DEVICE, 16-byte aligned
+ *   sources_out  uint8, DEVICE, 16-byte aligned: the packed ragged source buffer mpn_keypoint_augment, mpn_detector_augment
+ *                and mpn_image_resize read
+ *   work         mpn_jpeg_decode_workspace_bytes(B, sum of total_blocks) bytes (64 per block; 0 for arguments out of range),
+ *                16-byte aligned; image b's planes at byte work_offset
+ * src_offset, coef_offset and work_offset are multiples of 16. The kernels recompute an image's geometry from (width,
+ * height, components, h_samp, v_samp) and skip an image whose descriptor is out of range, misaligned, or reaches outside
+ * coef_bytes / work_bytes / sources_bytes: no descriptor makes them read or write outside the four buffers.
+ * Grid and block sizes depend on B alone. Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535
+ * (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); coef_bytes >= 128, work_bytes >= 64, sources_bytes >= 3
+ * (MPN_ERR_WORKSPACE).
+ */
+enum {
+    MPN_JPEG_SUPPORTED = 0,
+    MPN_JPEG_MALFORMED = 1,     /* not a JPEG, or damaged / truncated headers */
+    MPN_JPEG_PROGRESSIVE = 2,
+    MPN_JPEG_ARITHMETIC = 3,
+    MPN_JPEG_FRAME_TYPE = 4,    /* lossless or hierarchical */
+    MPN_JPEG_PRECISION = 5,     /* not 8 bits */
+    MPN_JPEG_COMPONENTS = 6,    /* neither 1 nor 3: CMYK / YCCK */
+    MPN_JPEG_COLORSPACE = 7,    /* three components that libjpeg does not read as YCbCr */
+    MPN_JPEG_SAMPLING = 8,
+    MPN_JPEG_MULTISCAN = 9,
+    MPN_JPEG_DQT16 = 10,
+    MPN_JPEG_TOO_LARGE = 11     /* more than 2^28 pixels */
+};
+typedef struct mpn_jpeg_header {               /* what mpn_jpeg_info reports (host) */
+    int32_t width, height, components;
+    int32_t h_samp, v_samp;                     /* sampling of the first component (1, 1 for grayscale) */
+    int32_t restart_interval;                   /* in MCUs; 0 = none */
+    int32_t supported, reason;                  /* reason: MPN_JPEG_* */
+    int32_t blocks_w[3], blocks_h[3];           /* padded block grid of each component (supported streams only) */
+    int32_t total_blocks, reserved;             /* sum of blocks_w * blocks_h */
+    int64_t coef_bytes;                         /* total_blocks * 128 */
+} mpn_jpeg_header;
+#define MPN_JPEG_DESC_BYTES 512
+typedef struct mpn_jpeg_desc {
+    int64_t src_offset;                         /* CALLER: byte offset of the image in sources_out, multiple of 16 */
+    int64_t coef_offset;                        /* CALLER: byte offset of its coefficients in coefs, multiple of 16 */
+    int64_t work_offset;                        /* CALLER: byte offset of its planes in work, multiple of 16 */
+    int32_t width, height, components, h_samp, v_samp;
+    int32_t total_blocks;
+    int32_t blocks_w[3], blocks_h[3];
+    int32_t reserved[14];
+    uint16_t quant[3][64];                      /* per component, natural order (the 8-bit tables widened) */
+} mpn_jpeg_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_jpeg_desc) == MPN_JPEG_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_jpeg_desc_bytes(void);
+int mpn_jpeg_info(const uint8_t* data /* host */, size_t nbytes, mpn_jpeg_header* out /* host */);
+int mpn_jpeg_entropy_decode(const uint8_t* data /* host */, size_t nbytes, int16_t* coefs /* host */, size_t coef_bytes,
+                            mpn_jpeg_desc* desc /* host */);
+size_t mpn_jpeg_decode_workspace_bytes(int B, long long total_blocks);
+int mpn_jpeg_decode(const int16_t* coefs, size_t coef_bytes, const void* descs, int B, uint8_t* sources_out,
+                    size_t sources_bytes, void* work, size_t work_bytes, mpn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,11 @@ SIGNATURES = {
     "mpn_draw_dot_stamp": (_I, [_I, _I, _I]),
     "mpn_draw_detections_workspace_bytes": (_Z, [_I, _I]),
     "mpn_draw_detections": (_I, [_P, _Z, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _Z, _P]),
+    "mpn_jpeg_desc_bytes": (_Z, []),
+    "mpn_jpeg_info": (_I, [_P, _Z, _P]),
+    "mpn_jpeg_entropy_decode": (_I, [_P, _Z, _P, _Z, _P]),
+    "mpn_jpeg_decode_workspace_bytes": (_Z, [_I, _L]),
+    "mpn_jpeg_decode": (_I, [_P, _Z, _P, _I, _P, _Z, _P, _Z, _P]),
 }
 
 _lib = None
@@ -194,13 +199,13 @@ def last_error():
     return buf.value.decode("utf-8", "replace")
 
 
-_ERR_NAMES = {-1: "BAD_SHAPE", -2: "BAD_DTYPE", -3: "BAD_ALIGN", -4: "HIP", -5: "BAD_ARG", -6: "WORKSPACE"}
+_ERR_NAMES = {-1: "BAD_SHAPE", -2: "BAD_DTYPE", -3: "BAD_ALIGN", -4: "HIP", -5: "BAD_ARG", -6: "WORKSPACE", -7: "BAD_DATA"}
 
 
 def check(rc):
     if rc != 0:
         msg = f"MPN_ERR_{_ERR_NAMES.get(rc, rc)}: {last_error()}"
-        if rc in (-1, -2, -3, -5):
+        if rc in (-1, -2, -3, -5, -7):
             raise ValueError(msg)
         raise MpnError(msg)
 

@@ -22,6 +22,11 @@ yielded batch is valid until the next one is requested. Otherwise the pipeline a
 a batch stays valid until the next-but-one is requested. Evaluation batches (batch size 1, size from
 `resize_keeping_aspect_ratio`) get buffers per distinct image size.
 
+`decode='device'` (default 'host') moves the pixel half of the JPEG decode to the device: the pool runs only the marker scan and
+the Huffman decode (inference/jpeg.py), the coefficients are copied on the side stream and `mpn_jpeg_decode` writes the
+uint8 sources there, byte for byte what PIL decodes - so a seed gives the same batches in both modes. Streams the device path
+does not support (progressive, CMYK, ...) are decoded by PIL per image, inside the same batch.
+
 `filenames` may also be an in-memory sequence of decoded examples, dicts with 'image' (uint8 [H,W,3]), 'boxes'
 (f32 [P,4] absolute), 'keypoints' (int [P,17,3]) and 'masks' (np.packbits bytes of [ceil(H/4), ceil(W/4), 2]) - no PIL is
 needed for those. Randomness follows the reference's distributions, not TensorFlow's streams (keypoint_augment.py).
@@ -34,10 +39,20 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...inference import jpeg
 from ..constants import DIVISOR, DOWNSAMPLE, NUM_KEYPOINTS, NUM_PARALLEL_CALLS, SHUFFLE_BUFFER_SIZE
 from . import keypoint_augment as ka
 from .heatmap_creation import HeatmapRenderer
 from .tfrecord import decode_jpeg, decode_keypoint_example, read_records
+
+
+DECODE_MODES = ('host', 'device')
+
+
+def check_decode_mode(decode):
+    if decode not in DECODE_MODES:
+        raise ValueError(f"decode must be one of {DECODE_MODES} (got {decode!r})")
+    return decode
 
 
 def _align(n, a=256):
@@ -52,6 +67,7 @@ class _Slot:
         self.host, self.dev = {}, {}
         self.copied = torch.cuda.Event()
         self.consumed = None
+        self.jpeg = None                     # decode='device': this slot's JpegBatchDecoder (its own staging)
 
     def reserve(self, name, nbytes):
         if name not in self.host or self.host[name].numel() < nbytes:
@@ -65,11 +81,13 @@ class _Slot:
 
 class KeypointPipeline:
     def __init__(self, filenames, is_training, params, device=None, buffers=None, num_threads=NUM_PARALLEL_CALLS,
-                 depth=2):
+                 depth=2, decode='host'):
         """filenames: paths of TFRecord files, or a sequence of decoded examples. params: 'batch_size', 'image_size'
         (width, height) for training, 'min_dimension' for evaluation; optional 'seed' (default 0) and
         'shuffle_buffer_size' (default SHUFFLE_BUFFER_SIZE). Under WORLD_SIZE > 1 rank r reads shards i with
-        i % world == r (records i % world == r when there are fewer shards than ranks)."""
+        i % world == r (records i % world == r when there are fewer shards than ranks). decode: 'host' (PIL on the
+        thread pool) or 'device' (Huffman decode on the pool, inverse DCT and colour on the device)."""
+        self.decode = check_decode_mode(decode)
         self.is_training = bool(is_training)
         if self.is_training:
             self.batch_size = int(params["batch_size"])
@@ -147,14 +165,20 @@ class KeypointPipeline:
             yield rec
 
     @staticmethod
-    def _decode(rec):
-        ex = decode_keypoint_example(rec) if isinstance(rec, (bytes, bytearray, memoryview)) else dict(rec)
+    def _decode(rec, device=False):
+        """device: a JPEG stays coefficients (jpeg.Coefficients, which has the image's .shape) when the device path
+        supports its stream."""
+        if isinstance(rec, (bytes, bytearray, memoryview)):
+            ex = decode_keypoint_example(rec, decode_image=not device)
+        else:
+            ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = decode_jpeg(img)
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
+            img = jpeg.prepare(img) if device else decode_jpeg(img)
+        if not isinstance(img, jpeg.Coefficients):
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
         p = np.asarray(ex["boxes"]).size // 4
         return {"image": img, "boxes": np.asarray(ex["boxes"], np.float32).reshape(p, 4),
                 "keypoints": np.asarray(ex["keypoints"]).astype(np.int32).reshape(p, NUM_KEYPOINTS, 3),
@@ -224,8 +248,9 @@ class KeypointPipeline:
         src = slot.reserve("src", src_total)
         msk = slot.reserve("masks", mask_total)
         for d, ex in zip(descs, examples):
-            so, n = int(d["src_offset"]), ex["image"].size
-            src[so:so + n] = ex["image"].reshape(-1)
+            if self.decode == 'host':
+                so, n = int(d["src_offset"]), ex["image"].size
+                src[so:so + n] = ex["image"].reshape(-1)
             mo, nb = int(d["mask_offset"]), (int(d["mask_h"]) * int(d["mask_w"]) * 2 + 7) // 8
             msk[mo:mo + nb] = ex["masks"][:nb]
         ka.check_descriptors(descs, src_total, mask_total, H, W)
@@ -250,7 +275,10 @@ class KeypointPipeline:
             cs.wait_event(slot.consumed)            # the launch that read this slot's device copy has done so
         with torch.cuda.stream(cs):
             for name, n in (("src", src_total), ("masks", mask_total), ("meta", nb_off + B * 4)):
-                slot.dev[name][:max(n, 1)].copy_(slot.host[name][:max(n, 1)], non_blocking=True)
+                if name != "src" or self.decode == 'host':
+                    slot.dev[name][:max(n, 1)].copy_(slot.host[name][:max(n, 1)], non_blocking=True)
+            if self.decode == 'device':
+                self._decode_sources(slot, descs, examples, cs)
             slot.copied.record(cs)
         main.wait_event(slot.copied)
         feats, labels = self._outputs(H, W)
@@ -268,6 +296,13 @@ class KeypointPipeline:
         slot.consumed = ev
         return feats, labels
 
+    def _decode_sources(self, slot, descs, examples, stream):
+        """decode='device': fills slot.dev["src"] on `stream` - mpn_jpeg_decode for the coefficient entries, a copy for the
+        entries that are pixels already."""
+        if slot.jpeg is None:
+            slot.jpeg = jpeg.JpegBatchDecoder(self.device)
+        slot.jpeg.decode([ex["image"] for ex in examples], slot.dev["src"], [int(d["src_offset"]) for d in descs], stream)
+
     def batches(self):
         """Generator of (features, labels); endless for training, one pass for evaluation (drop_remainder)."""
         shuffle_rng, rng = self.generators()
@@ -281,7 +316,7 @@ class KeypointPipeline:
                 for rec in records:
                     raw.append(rec)
                     if len(raw) == self.batch_size:
-                        return [pool.submit(self._decode, r) for r in raw]
+                        return [pool.submit(self._decode, r, self.decode == 'device') for r in raw]
                 return None
             pending = next_batch()
             while pending is not None:

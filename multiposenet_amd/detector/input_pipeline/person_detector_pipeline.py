@@ -31,9 +31,10 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...inference import jpeg
 from ..constants import NUM_PARALLEL_CALLS
 from . import detector_augment as da
-from .keypoints_detector_pipeline import KeypointPipeline, _align, _Slot
+from .keypoints_detector_pipeline import DECODE_MODES, KeypointPipeline, _align, _Slot, check_decode_mode  # noqa: F401
 from .tfrecord import decode_jpeg, parse_example, read_records
 
 
@@ -55,12 +56,12 @@ def decode_detector_example(data, decode_image=True):
 
 class DetectorPipeline(KeypointPipeline):
     def __init__(self, filenames, is_training, params, device=None, buffers=None, num_threads=NUM_PARALLEL_CALLS, seed=0,
-                 depth=2):
+                 depth=2, decode='host'):
         """filenames: paths of TFRecord files, or a sequence of decoded examples. params: 'batch_size', 'image_size'
         (width, height) for training, 'min_dimension' for evaluation; optional 'seed' (overrides `seed`) and
-        'shuffle_buffer_size'."""
+        'shuffle_buffer_size'. decode: 'host' or 'device', as for `KeypointPipeline`."""
         super().__init__(filenames, is_training, params, device=device, buffers=buffers, num_threads=num_threads,
-                         depth=depth)
+                         depth=depth, decode=decode)
         self.seed = int(params.get("seed", seed))
         self._num_examples = None
 
@@ -73,14 +74,18 @@ class DetectorPipeline(KeypointPipeline):
         return self._num_examples
 
     @staticmethod
-    def _decode(rec):
-        ex = decode_detector_example(rec) if isinstance(rec, (bytes, bytearray, memoryview)) else dict(rec)
+    def _decode(rec, device=False):
+        if isinstance(rec, (bytes, bytearray, memoryview)):
+            ex = decode_detector_example(rec, decode_image=not device)
+        else:
+            ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = decode_jpeg(img)
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
+            img = jpeg.prepare(img) if device else decode_jpeg(img)
+        if not isinstance(img, jpeg.Coefficients):
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
         return {"image": img, "boxes": np.asarray(ex["boxes"], np.float32).reshape(-1, 4)}
 
     # ---------------------------------------------------------------- host sampling
@@ -135,9 +140,10 @@ class DetectorPipeline(KeypointPipeline):
         # a slot's pinned arrays may be rewritten only once its previous copy has left them
         slot.copied.synchronize()
         src = slot.reserve("src", src_total)
-        for d, ex in zip(descs, examples):
-            so, n = int(d["src_offset"]), ex["image"].size
-            src[so:so + n] = ex["image"].reshape(-1)
+        if self.decode == 'host':
+            for d, ex in zip(descs, examples):
+                so, n = int(d["src_offset"]), ex["image"].size
+                src[so:so + n] = ex["image"].reshape(-1)
         da.check_descriptors(descs, src_total, H, W)
         padded = np.zeros((B, M, 4), np.float32)
         for i, b in enumerate(boxes):
@@ -156,7 +162,10 @@ class DetectorPipeline(KeypointPipeline):
             cs.wait_event(slot.consumed)            # the launch that read this slot's device copy has done so
         with torch.cuda.stream(cs):
             for name, n in (("src", src_total), ("meta", nb_off + B * 4)):
-                slot.dev[name][:n].copy_(slot.host[name][:n], non_blocking=True)
+                if name != "src" or self.decode == 'host':
+                    slot.dev[name][:n].copy_(slot.host[name][:n], non_blocking=True)
+            if self.decode == 'device':
+                self._decode_sources(slot, descs, examples, cs)
             slot.copied.record(cs)
         main.wait_event(slot.copied)
         feats, labels = self._outputs(H, W, M)
@@ -183,7 +192,7 @@ class DetectorPipeline(KeypointPipeline):
                 for rec in records:
                     raw.append(rec)
                     if len(raw) == self.batch_size:
-                        return [pool.submit(self._decode, r) for r in raw]
+                        return [pool.submit(self._decode, r, self.decode == 'device') for r in raw]
                 return None
             pending = next_batch()
             while pending is not None:

@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib
 from ..net import KeypointNet
-from . import draw, resample
+from . import draw, jpeg, resample
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -419,6 +419,68 @@ class Detector:
                     ent['outs'] = self._device_side_images(ent, thr)
                 ent['graph'], ent['ver'] = graph, ver
             elif ent['ver'] != ver:    # as in predict_batch
+                self._device_side_images(ent, thr)
+                ent['ver'] = ver
+            ent['graph'].replay()
+            outs = ent['outs']
+        persons = self._finish(ent, outs, b, return_heatmaps)
+        if return_heatmaps:
+            for p, new_size in zip(persons, plan.new_sizes):
+                p['resized_size'] = new_size
+        return persons
+
+    # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
+    def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
+                      annotate=False):
+        """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
+        Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
+        and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
+        `predict_images([pillow_decode(j) for j in jpegs], ...)`. A stream outside the supported set (progressive, CMYK, ...)
+        is decoded by Pillow and uploaded as pixels, inside the same batch.
+
+        Arguments:
+            jpegs: a list of b >= 1 `bytes`, one JPEG file each; the image sizes may all differ.
+            size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate: as for `predict_images` (annotate=True draws on
+                the decoded frames).
+        Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
+        one `predict_images` replays: keyed by capacity, not by the batch's sizes.
+        """
+        if isinstance(jpegs, (bytes, bytearray, memoryview)):
+            raise ValueError("jpegs must be a list of bytes (got one bytes object)")
+        items = list(jpegs)
+        if len(items) < 1:
+            raise ValueError("empty batch")
+        if any(not isinstance(j, (bytes, bytearray, memoryview)) for j in items):
+            raise ValueError("a JPEG must be bytes")
+        infos = [jpeg.jpeg_info(j) for j in items]
+        height, width = resample.check_size(size)
+        plan = resample.Plan([(i['height'], i['width']) for i in infos], height, width, keep_aspect_ratio, align=16)
+        entries = [jpeg.prepare(j) for j in items]
+        for e, (h, w) in zip(entries, plan.sizes):
+            if tuple(e.shape) != (h, w, 3):
+                raise ValueError(f"a JPEG decodes to {tuple(e.shape)}, its header says {(h, w, 3)}")
+        b, thr = len(items), float(score_threshold)
+        ent = self._images_entry(b, height, width, thr, plan, bool(annotate))
+        if 'jpeg' not in ent:
+            ent['jpeg'] = jpeg.JpegBatchDecoder(self.net.device)
+        ent['meta_stage'].numpy()[:plan.meta_words] = plan.meta
+        nw = plan.meta_words
+        ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)
+        ent['jpeg'].decode(entries, ent['sources'], plan.src_offsets, torch.cuda.current_stream(self.net.device))
+        if annotate:
+            ent['draw'].place(plan.sizes, plan.src_offsets)
+        ver = self._variable_versions()
+        if not self.use_graph:
+            outs = self._device_side_images(ent, thr)
+        else:
+            if ent['graph'] is None:   # as in predict_images: captured over this call's descriptors
+                self._device_side_images(ent, thr)
+                torch.cuda.synchronize(self.net.device)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    ent['outs'] = self._device_side_images(ent, thr)
+                ent['graph'], ent['ver'] = graph, ver
+            elif ent['ver'] != ver:
                 self._device_side_images(ent, thr)
                 ent['ver'] = ver
             ent['graph'].replay()

@@ -127,7 +127,8 @@ class Plan:
     work_bytes   of the uint8 intermediates [src_h, stride(new_w * 3 -> 16)] behind each other
     """
 
-    def __init__(self, shapes, height, width, keep_aspect_ratio=False):
+    def __init__(self, shapes, height, width, keep_aspect_ratio=False, align=1):
+        """align: every source starts at a multiple of it (16 for sources that mpn_jpeg_decode writes)."""
         b = len(shapes)
         self.b, self.height, self.width = b, height, width
         self.sizes = [(int(h), int(w)) for h, w in shapes]
@@ -156,6 +157,7 @@ class Plan:
             bx, cx, kx = place(w, nw)
             by, cy, ky = place(h, nh)
             stride = _round16(nw * 3)
+            src_at = (src_at + align - 1) // align * align
             d64[i, 0], d64[i, 1] = src_at, tmp_at
             desc[i, 4:15] = (h, w, nh, nw, bx, cx, by, cy, kx, ky, stride)
             self.src_offsets.append(src_at)
