@@ -974,6 +974,79 @@ size_t mpn_jpeg_decode_workspace_bytes(int B, long long total_blocks);
 int mpn_jpeg_decode(const int16_t* coefs, size_t coef_bytes, const void* descs, int B, uint8_t* sources_out,
                     size_t sources_bytes, void* work, size_t work_bytes, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * JPEG encode, all of it on the device: baseline, three components (YCbCr), luma sampling 1x1, 2x1 or 2x2 with chroma 1x1,
+ * the standard (Annex K) Huffman tables, no restart intervals. The entropy-coded scan equals, byte for byte, the one
+ * libjpeg(-turbo) - and so Pillow's `save(buf, "JPEG", quality=q, subsampling=s)` - writes for the same pixels and tables;
+ * the headers in front of it are host bytes (multiposenet_amd.inference.jpeg.jpeg_headers). Two entry points, both over a
+ * ragged batch described by [B] mpn_jpeg_enc_desc on the DEVICE, no host synchronisation, no allocation: capturable.
+ *
+ * mpn_jpeg_forward: pixels -> quantised coefficients in the layout mpn_jpeg_entropy_decode produces (int16, natural order,
+ * one plane of blocks per component on the padded whole-MCU grid), image b's planes at byte coef_offset. One launch.
+ *   sources   packed uint8 images; image b at byte src_offset as [height, width, channels], channels 3 (RGB) or 4 (RGBA,
+ *             alpha ignored: the layout mpn_draw_detections writes)
+ *   colour    RGB -> YCbCr in 16-bit fixed point (jccolor.c): constants (int)(x * 65536 + 0.5); Y adds 32768, Cb and Cr add
+ *             (128 << 16) + 32767, then >> 16
+ *   edges     columns: the source's right column is replicated (luma to the block grid, chroma - before downsampling - to
+ *             the MCU width). Rows: the last source row is replicated up to a multiple of v_samp only; after downsampling
+ *             the last DOWNSAMPLED row is replicated to the block grid
+ *   chroma    h2v2: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2, ... by output column; h2v1: (a + b + bias) >> 1, bias 0, 1, ...
+ *   DCT       slow integer (jfdctint.c): samples - 128, 13-bit constants, rows first keeping 2 extra bits, then columns,
+ *             descale (x + 2^(n-1)) >> n; the result is 8x the DCT
+ *   quantise  q8 = 8 * quant: sign(c) * ((|c| + (q8 >> 1)) / q8)
+ *   dummy blocks (luma blocks of the padded grid beyond ceil(width/8) x ceil(height/8)): 63 zero AC terms and the DC of the
+ *             preceding block in MCU order (jccoefct.c)
+ *
+ * mpn_jpeg_entropy_encode: coefficients -> image b's scan at byte out_offset of `out`: MCU-interleaved Huffman coding, the
+ * last byte padded with 1-bits, a 0x00 stuffed behind every 0xFF, then FF D9. `records` [B] mpn_jpeg_stream_record receives
+ * (out_offset, size, status) per image:
+ *   MPN_JPEG_ENC_OK           size bytes were written at out_offset
+ *   MPN_JPEG_ENC_NO_FIT       size > capacity: nothing was written; size is the size the stream needs
+ *   MPN_JPEG_ENC_NO_FIT_RAW   even the unstuffed stream exceeds capacity: nothing was written; size is a LOWER bound
+ *   MPN_JPEG_ENC_SKIPPED      the descriptor is out of range (below); size 0
+ * Seven launches: bit count per block (the DC predictor is the previous block of the component in scan order), a scan of
+ * the counts (chunk sums; one workgroup per image scans the chunks), zeroing of the bit buffer, the emit pass (each block's
+ * bits are ORed into the buffer with global atomics), the count of 0xFF bytes per chunk, its scan (which also writes the
+ * record), and the scatter of the stuffed bytes and the trailer.
+ *   work      image b's share at byte work_offset: mpn_jpeg_entropy_encode_workspace_bytes(total blocks of the image,
+ *             capacity) bytes (0 for arguments out of range); nothing in it needs initialising
+ * src_offset, coef_offset, out_offset and work_offset are multiples of 16. The kernels recompute an image's geometry from
+ * (width, height, h_samp, v_samp) and skip an image whose descriptor is out of range (sides in [1, 65535], at most
+ * MPN_JPEG_ENC_MAX_BLOCKS blocks, channels 3 or 4, one of the three samplings, capacity in [16, 2^30]), misaligned, or that
+ * reaches outside sources_bytes / coef_bytes / out_bytes / work_bytes: no descriptor makes them read or write outside the
+ * buffers, and nothing outside [out_offset, out_offset + capacity) is written for an image. A quantisation entry of 0 is
+ * taken as 1. Grid and block sizes depend on B alone. Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <=
+ * 65535 (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); sources_bytes >= 3, coef_bytes >= 128, out_bytes >= 16,
+ * work_bytes >= 16 (MPN_ERR_WORKSPACE).
+ */
+enum { MPN_JPEG_ENC_OK = 0, MPN_JPEG_ENC_NO_FIT = 1, MPN_JPEG_ENC_NO_FIT_RAW = 2, MPN_JPEG_ENC_SKIPPED = 3 };
+#define MPN_JPEG_ENC_MAX_BLOCKS (1 << 21)       /* keeps every bit offset of a scan in 32 bits */
+#define MPN_JPEG_ENC_DESC_BYTES 512
+typedef struct mpn_jpeg_enc_desc {
+    int64_t src_offset;                         /* byte offset of the pixels in sources */
+    int64_t coef_offset;                        /* byte offset of the coefficients in coefs */
+    int64_t out_offset;                         /* byte offset of the scan in out (entropy encode) */
+    int64_t capacity;                           /* bytes the scan may take at out_offset */
+    int64_t work_offset;                        /* byte offset of the image's share of work (entropy encode) */
+    int32_t width, height, channels, h_samp, v_samp;
+    int32_t reserved[17];
+    uint16_t quant[3][64];                      /* per component, natural order */
+} mpn_jpeg_enc_desc;
+typedef struct mpn_jpeg_stream_record {
+    int64_t offset, size;
+    int32_t status, reserved[3];
+} mpn_jpeg_stream_record;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_jpeg_enc_desc) == MPN_JPEG_ENC_DESC_BYTES, "descriptor size is fixed");
+static_assert(sizeof(mpn_jpeg_stream_record) == 32, "record size is fixed");
+#endif
+size_t mpn_jpeg_enc_desc_bytes(void);
+int mpn_jpeg_forward(const uint8_t* sources, size_t sources_bytes, const void* descs, int B, int16_t* coefs, size_t coef_bytes,
+                     mpn_stream_t stream);
+size_t mpn_jpeg_entropy_encode_workspace_bytes(long long total_blocks, long long capacity);
+int mpn_jpeg_entropy_encode(const int16_t* coefs, size_t coef_bytes, const void* descs, int B, uint8_t* out, size_t out_bytes,
+                            void* records, void* work, size_t work_bytes, mpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

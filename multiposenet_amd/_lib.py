@@ -154,6 +154,10 @@ SIGNATURES = {
     "mpn_jpeg_entropy_decode": (_I, [_P, _Z, _P, _Z, _P]),
     "mpn_jpeg_decode_workspace_bytes": (_Z, [_I, _L]),
     "mpn_jpeg_decode": (_I, [_P, _Z, _P, _I, _P, _Z, _P, _Z, _P]),
+    "mpn_jpeg_enc_desc_bytes": (_Z, []),
+    "mpn_jpeg_forward": (_I, [_P, _Z, _P, _I, _P, _Z, _P]),
+    "mpn_jpeg_entropy_encode_workspace_bytes": (_Z, [_L, _L]),
+    "mpn_jpeg_entropy_encode": (_I, [_P, _Z, _P, _I, _P, _Z, _P, _P, _Z, _P]),
 }
 
 _lib = None

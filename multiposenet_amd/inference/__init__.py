@@ -1,2 +1,3 @@
 from .utils import get_keypoints, get_keypoints_batch, KeypointDecoder, draw_everything  # noqa: F401
 from .detector import Detector  # noqa: F401
+from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401

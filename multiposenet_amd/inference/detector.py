@@ -60,6 +60,23 @@ def check_batch(images):
     return b, h, w
 
 
+def check_annotate(annotate, jpeg_quality, jpeg_subsampling):
+    """The `annotate` argument of the predict_* methods: False or True -> None; 'jpeg' -> (quality, subsampling), checked."""
+    if not isinstance(annotate, str):
+        return None
+    if annotate != 'jpeg':
+        raise ValueError(f"annotate must be False, True or 'jpeg' (got {annotate!r})")
+    jpeg.quality_tables(jpeg_quality)
+    jpeg._sampling(jpeg_subsampling)
+    return int(jpeg_quality), jpeg_subsampling
+
+
+def _encode_plan(sizes, src_offsets, jp):
+    """The encode of the annotated frames where mpn_draw_detections writes them (RGBA, draw.layout's offsets)."""
+    _, frames, _ = draw.layout(sizes, src_offsets)
+    return jpeg.EncodePlan([(h, w) for _, h, w in frames], [at for at, _, _ in frames], 4, *jp)
+
+
 def _no_persons(num_boxes=0):
     return {'boxes': np.zeros([0, 4], np.float32), 'scores': np.zeros([0], np.float32), 'num_boxes': np.int32(num_boxes),
             'keypoint_scores': np.zeros([0, NUM_KEYPOINTS], np.float32), 'keypoint_positions': np.zeros([0, NUM_KEYPOINTS, 2], np.float32),
@@ -233,7 +250,8 @@ class Detector:
         return outs
 
     # ------------------------------------------------------------------ batched inference
-    def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False):
+    def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
+                      jpeg_subsampling='4:2:0'):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -242,13 +260,21 @@ class Detector:
             return_heatmaps: False omits 'keypoint_heatmaps' and 'segmentation_masks'; they then never leave the device.
             annotate: True adds 'annotated', a uint8 [height, width, 4] RGBA array: the image with that dict's persons drawn on
                 it as inference/predict.ipynb's `draw_everything` draws them under Pillow, byte for byte (drawn on the device
-                inside the captured graph: a graph of its own per (b, height, width, threshold)).
+                inside the captured graph: a graph of its own per (b, height, width, threshold)). 'jpeg' adds
+                'annotated_jpeg' instead: that frame (its RGB) as the `bytes` of the JPEG file Pillow writes for it with
+                `save(buf, "JPEG", quality=jpeg_quality, subsampling=jpeg_subsampling)`, encoded on the device inside the
+                graph where the frame lies; only the compressed bytes are copied to the host.
+            jpeg_quality, jpeg_subsampling: 1..100 and '4:4:4', '4:2:2' or '4:2:0'. The quality travels in descriptors: another
+                quality replays the same graph; the sampling is part of the graph's key.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
+        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
         b, h, w = check_batch(images)
         thr = float(score_threshold)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate))
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp)
+        if jp and ent['encode_plan'].quality != jp[0]:              # the frames are fixed: only another quality needs new descriptors
+            self._place_encode(ent, _encode_plan([(h, w)] * b, [i * h * w * 3 for i in range(b)], jp))
         stage = ent['stage'].numpy()
         if isinstance(images, np.ndarray):
             stage[...] = images
@@ -258,14 +284,20 @@ class Detector:
         ent['x'].copy_(ent['stage'], non_blocking=True)             # ONE host-to-device copy
         ver = self._variable_versions()
         if ent['graph'] is None:
-            outs = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
+            outs = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
         else:
             if ent['ver'] != ver:      # as in _replay: the host-cached affines / operand casts the captured launches read
-                self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
+                self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
                 ent['ver'] = ver
             ent['graph'].replay()
             outs = ent['outs']
         return self._finish(ent, outs, b, return_heatmaps)
+
+    @staticmethod
+    def _place_encode(ent, plan):
+        """This call's encode descriptors (geometry, offsets, quantisation tables) go to the device: one small copy."""
+        ent['encode_plan'] = plan
+        ent['encode'].upload(plan)
 
     def _finish(self, ent, outs, b, return_heatmaps):
         """The host side behind the device side of predict_batch / predict_images: the record (and the maps) into pinned
@@ -286,6 +318,7 @@ class Detector:
             ent['host']['annotated'][:nb].copy_(outs['annotated'][:nb], non_blocking=True)
         torch.cuda.current_stream(self.net.device).synchronize()
         host = ent['host']
+        files = ent['encode'].collect(ent['encode_plan'], outs['encoded']) if 'encoded' in outs else None
         if 'record' in outs:
             persons = unpack_record(host['record'].numpy(), b, self.params['max_boxes'], self.assigner is not None)
         else:                                                       # no detector_path: no boxes are detected
@@ -297,14 +330,17 @@ class Detector:
         if 'annotated' in outs:
             for p, frame in zip(persons, ent['draw'].unpack(host['annotated'].numpy())):
                 p['annotated'] = frame
+        if files is not None:
+            for p, data in zip(persons, files):
+                p['annotated_jpeg'] = data
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False):
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None):
         """The persistent state of one (b, h, w, threshold[, annotate]): pinned staging, the device input, the captured graph and
         its outputs. use_graph False: the same buffers, the device side runs eagerly on every call."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
         if annotate:
-            key += ('annotate',)
+            key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -315,23 +351,29 @@ class Detector:
         if annotate:                                                # the frames are the batch itself: fixed descriptors
             ent['draw'] = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
             ent['draw'].place([(h, w)] * b, [i * h * w * 3 for i in range(b)])
+        if jp:                                                      # the frames lie where the drawing writes them: fixed sizes
+            plan = _encode_plan([(h, w)] * b, [i * h * w * 3 for i in range(b)], jp)
+            ent['encode'] = jpeg.JpegBatchEncoder(dev)
+            ent['encode'].reserve(b, *plan.need)
+            self._place_encode(ent, plan)
         if self.use_graph:
             ent['x'].zero_()
-            self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))    # eager warm-up: sizes the buffers, sets kernel attributes
+            self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))    # eager warm-up: sizes the buffers, sets kernel attributes
             torch.cuda.synchronize(dev)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                ent['outs'] = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'))
+                ent['outs'] = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
             ent['graph'], ent['ver'] = graph, self._variable_versions()
         store[key] = ent
         return ent
 
-    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None):
+    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
         draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat uint8; default:
-        the batch x itself) -> 'annotated', the packed RGBA frames."""
+        the batch x itself) -> 'annotated', the packed RGBA frames. encode (a jpeg.JpegBatchEncoder whose descriptors are in
+        place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'."""
         net = self.net
         b, h, w, _ = x.shape
         bufs = net._buffers(b, h, w)
@@ -343,7 +385,7 @@ class Detector:
         if self.retinanet is None:
             if annotate is not None:                                # no detector: the frames with alpha 255
                 dev['annotated'] = annotate.launch(frames, None, False)
-            return dev
+            return self._encode_frames(dev, encode)
         pred = self._detect(feats, b, h, w)
         max_boxes = pred['boxes'].shape[1]
         kscore = kpos = None
@@ -367,11 +409,18 @@ class Detector:
         dev['record'] = record
         if annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
+        return self._encode_frames(dev, encode)
+
+    @staticmethod
+    def _encode_frames(dev, encode):
+        if encode is not None:
+            dev['encoded'] = dev.pop('annotated')
+            encode.launch(dev['encoded'])
         return dev
 
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                       annotate=False):
+                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -388,16 +437,20 @@ class Detector:
             annotate: True adds 'annotated', a uint8 [h_i, w_i, 4] RGBA array: the SOURCE frame at its own size with that
                 dict's persons drawn on it as inference/predict.ipynb's `draw_everything` draws them under Pillow, byte for
                 byte (drawn on the device inside the captured graph, from the frames already uploaded for the resize).
+                'jpeg' adds 'annotated_jpeg' instead, as `predict_batch` does: the file Pillow writes for that frame.
+            jpeg_quality, jpeg_subsampling: as for `predict_batch`.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
         raises ValueError.
         """
+        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
         items = resample.check_images(images)
         height, width = resample.check_size(size)
         plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
         b, thr = len(items), float(score_threshold)
-        ent = self._images_entry(b, height, width, thr, plan, bool(annotate))
+        eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
+        ent = self._images_entry(b, height, width, thr, plan, bool(annotate), eplan)
         stage = ent['stage'].numpy()
         for im, at in zip(items, plan.src_offsets):
             stage[at:at + im.size] = im.reshape(-1)
@@ -407,6 +460,8 @@ class Detector:
         ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)    # one of the descriptors, extents and tables
         if annotate:
             ent['draw'].place(plan.sizes, plan.src_offsets)
+        if jp:
+            self._place_encode(ent, eplan)
         ver = self._variable_versions()
         if not self.use_graph:
             outs = self._device_side_images(ent, thr)
@@ -431,7 +486,7 @@ class Detector:
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                      annotate=False):
+                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -440,11 +495,12 @@ class Detector:
 
         Arguments:
             jpegs: a list of b >= 1 `bytes`, one JPEG file each; the image sizes may all differ.
-            size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate: as for `predict_images` (annotate=True draws on
-                the decoded frames).
+            size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling: as for
+                `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
+        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
         if isinstance(jpegs, (bytes, bytearray, memoryview)):
             raise ValueError("jpegs must be a list of bytes (got one bytes object)")
         items = list(jpegs)
@@ -460,7 +516,8 @@ class Detector:
             if tuple(e.shape) != (h, w, 3):
                 raise ValueError(f"a JPEG decodes to {tuple(e.shape)}, its header says {(h, w, 3)}")
         b, thr = len(items), float(score_threshold)
-        ent = self._images_entry(b, height, width, thr, plan, bool(annotate))
+        eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
+        ent = self._images_entry(b, height, width, thr, plan, bool(annotate), eplan)
         if 'jpeg' not in ent:
             ent['jpeg'] = jpeg.JpegBatchDecoder(self.net.device)
         ent['meta_stage'].numpy()[:plan.meta_words] = plan.meta
@@ -469,6 +526,8 @@ class Detector:
         ent['jpeg'].decode(entries, ent['sources'], plan.src_offsets, torch.cuda.current_stream(self.net.device))
         if annotate:
             ent['draw'].place(plan.sizes, plan.src_offsets)
+        if jp:
+            self._place_encode(ent, eplan)
         ver = self._variable_versions()
         if not self.use_graph:
             outs = self._device_side_images(ent, thr)
@@ -491,29 +550,30 @@ class Detector:
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
         exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
-        output sized from the capacity of the sources - it grows with them."""
+        output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
+        capacity also covers the encoder's coefficients, streams and workspace."""
         store = self._graphs if self.use_graph else self._eager_batches
-        need = (plan.stage_bytes, plan.meta_words, plan.work_bytes)
+        need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
         base = ('images', b, h, w, thr)
-        tail = ('annotate',) if annotate else ()
+        tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
             if cap is not None:
                 store.pop(base + (cap,) + tail, None)      # superseded: its buffers and graph are never looked up again
-            cap = tuple(resample.capacity_for(max(n, c)) for n, c in zip(need, cap or (0, 0, 0)))
+            cap = tuple(resample.capacity_for(max(n, c)) for n, c in zip(need, cap or (0,) * len(need)))
             self._image_capacity[cap_key] = cap
         key = base + (cap,) + tail
         ent = store.get(key)
         if ent is not None:
             return ent
         dev = self.net.device
-        stage_bytes, meta_words, work_bytes = cap
+        stage_bytes, meta_words, work_bytes = cap[:3]
         if _lib.lib().mpn_image_resize_desc_bytes() != resample.DESC_WORDS * 4:
             raise _lib.MpnError("mpn_image_resize: the descriptor's layout is not the one this binding was written against")
         ent = {'stage': torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
@@ -524,6 +584,9 @@ class Detector:
                'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
         if annotate:
             ent['draw'] = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
+        if eplan:
+            ent['encode'] = jpeg.JpegBatchEncoder(dev)
+            ent['encode'].reserve(b, *cap[3:])
         store[key] = ent
         return ent
 
@@ -535,7 +598,7 @@ class Detector:
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent['sources']), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent['work']), ent['work'].numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent, annotate=ent.get('draw'), frames=ent['sources'])
+        return self._device_side_batch(x, thr, extent, annotate=ent.get('draw'), frames=ent['sources'], encode=ent.get('encode'))
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

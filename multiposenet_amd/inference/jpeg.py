@@ -2,7 +2,9 @@
 stage (marker scan and Huffman decode in C++, the GIL released: a thread pool runs them in parallel), `JpegBatchDecoder` ships
 the coefficients of a batch and launches `mpn_jpeg_decode`, which writes uint8 RGB into a packed source buffer - the bytes Pillow
 returns for the same file. Streams outside the supported set (progressive, CMYK, ...) are decoded by Pillow per image and
-copied as pixels, inside the same batch."""
+copied as pixels, inside the same batch.
+
+JPEG encode is the second half of the file: `quality_tables`, `jpeg_headers`, `JpegBatchEncoder`, `encode_jpegs`."""
 import ctypes
 import io
 
@@ -217,3 +219,275 @@ class JpegBatchDecoder:
                 sources[offsets[i]:offsets[i] + size].copy_(self._dev[at:at + size], non_blocking=True)
             self._done = torch.cuda.Event()
             self._done.record(stream)
+
+
+# ------------------------------------------------------------------------------------------------ encode
+# All of it on the device (include/mpn.h, "JPEG encode"): `mpn_jpeg_forward` turns packed RGB / RGBA frames into quantised
+# coefficients, `mpn_jpeg_entropy_encode` into the finished scan; the host adds the headers, which depend on nothing but the
+# geometry and the tables. The files equal Pillow's `save(buf, "JPEG", quality=q, subsampling=s)` byte for byte.
+
+ENC_DESC_BYTES = 512                    # MPN_JPEG_ENC_DESC_BYTES (checked against the library)
+RECORD_BYTES = 32                       # mpn_jpeg_stream_record
+ENC_OK, ENC_NO_FIT, ENC_NO_FIT_RAW, ENC_SKIPPED = 0, 1, 2, 3
+SAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
+BYTES_PER_SAMPLE = 2                    # an image's capacity: blocks * 64 * this + 256 (a stream beyond it takes the fallback)
+
+ENC_DESC = np.dtype([('src_offset', np.int64), ('coef_offset', np.int64), ('out_offset', np.int64), ('capacity', np.int64),
+                     ('work_offset', np.int64), ('width', np.int32), ('height', np.int32), ('channels', np.int32),
+                     ('h_samp', np.int32), ('v_samp', np.int32), ('reserved', np.int32, (17,)), ('quant', np.uint16, (3, 64))])
+RECORD = np.dtype([('offset', np.int64), ('size', np.int64), ('status', np.int32), ('reserved', np.int32, (3,))])
+assert ENC_DESC.itemsize == ENC_DESC_BYTES and RECORD.itemsize == RECORD_BYTES
+
+# Annex K.1 / K.2 (natural order) and K.3 - K.6 as Pillow's DHT segments hold them: (class, id, 16 counts, symbols)
+_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87,
+              80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92,
+              95, 98, 112, 100, 103, 99)
+_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99,
+                99, 99, 99) + (99,) * 32
+_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35,
+           42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+_DHT = tuple(bytes.fromhex(s) for s in (
+    "00" "00010501010101010100000000000000" "000102030405060708090a0b",
+    "10" "0002010303020403050504040000017d" "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a"
+    "25262728292a3435363738393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999a"
+    "a2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa",
+    "01" "00030101010101010101010000000000" "000102030405060708090a0b",
+    "11" "00020102040403040705040400010277" "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f1"
+    "1718191a262728292a35363738393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a9293949596"
+    "9798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+
+
+def quality_tables(quality):
+    """The two 8-bit quantisation tables (luma, chroma; uint16 [64], natural order) libjpeg derives from the Annex K tables
+    for `quality` in 1..100: scale = 5000 / q below 50, else 200 - 2q; entry = (base * scale + 50) / 100 clamped to 1..255."""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError(f"quality must be in 1..100 (got {quality})")
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.asarray(base, np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16) for base in (_BASE_LUMA, _BASE_CHROMA))
+
+
+def _sampling(subsampling):
+    try:
+        return SAMPLING[subsampling]
+    except (KeyError, TypeError):
+        raise ValueError(f"subsampling must be one of {sorted(SAMPLING)} (got {subsampling!r})")
+
+
+def _segment(marker, payload):
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, 'big') + payload
+
+
+def jpeg_headers(width, height, sampling, tables):
+    """The bytes from SOI through the SOS header as Pillow writes them for an RGB image with no extra `info`: APP0 (JFIF 1.1,
+    no density), two DQT, SOF0, four DHT (the standard tables), SOS. sampling: '4:4:4', '4:2:2' or '4:2:0'; tables: the two
+    8-bit tables of `quality_tables` (natural order)."""
+    hs, vs = _sampling(sampling)
+    if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+        raise ValueError(f"a JPEG is 1..65535 pixels per side (got {height} x {width})")
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\0\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for i, t in enumerate(tables):
+        t = np.asarray(t).reshape(64)
+        out += _segment(0xDB, bytes((i,)) + bytes(int(t[n]) for n in _ZIGZAG))
+    out += _segment(0xC0, b"\x08" + int(height).to_bytes(2, 'big') + int(width).to_bytes(2, 'big') + b"\x03"
+                    + bytes((1, (hs << 4) | vs, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    for table in _DHT:
+        out += _segment(0xC4, table)
+    return out + _segment(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def pillow_encode(pixels, quality=75, subsampling='4:2:0'):
+    """What the device path must equal, and the per-image fallback: Pillow's file for a uint8 [h, w, 3 or 4] array."""
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(pixels[..., :3])).save(buf, "JPEG", quality=int(quality),
+                                                                subsampling={'4:4:4': 0, '4:2:2': 1, '4:2:0': 2}[subsampling])
+    return buf.getvalue()
+
+
+def total_blocks(height, width, sampling):
+    hs, vs = _sampling(sampling)
+    return -(-int(width) // (8 * hs)) * -(-int(height) // (8 * vs)) * (hs * vs + 2)
+
+
+class EncodePlan:
+    """Host arithmetic of one batch: `.descs` (ENC_DESC [b]), where every image's coefficients, scan and workspace lie (each
+    at a multiple of 16), the three buffer sizes `.need` = (coef_bytes, out_bytes, work_bytes), and the headers."""
+
+    def __init__(self, shapes, offsets, channels, quality=75, subsampling='4:2:0', capacities=None):
+        hs, vs = _sampling(subsampling)
+        tables = quality_tables(quality)
+        if len(shapes) != len(offsets) or not len(shapes):
+            raise ValueError("encode: one offset per image, at least one image")
+        if channels not in (3, 4):
+            raise ValueError(f"encode: channels must be 3 (RGB) or 4 (RGBA) (got {channels})")
+        lib = _lib.lib()
+        b = len(shapes)
+        self.quality, self.subsampling, self.channels = int(quality), subsampling, channels
+        self.shapes = [(int(h), int(w)) for h, w in shapes]
+        self.offsets = [int(o) for o in offsets]
+        self.descs = np.zeros(b, ENC_DESC)
+        self.headers = []
+        coef = out = work = 0
+        for i, ((h, w), off) in enumerate(zip(self.shapes, self.offsets)):
+            if off % 16:
+                raise ValueError(f"encode: the offset of an image must be a multiple of 16 (got {off})")
+            blocks = total_blocks(h, w, subsampling)
+            cap = _round16(blocks * 64 * BYTES_PER_SAMPLE + 256) if capacities is None else int(capacities[i])
+            share = lib.mpn_jpeg_entropy_encode_workspace_bytes(blocks, cap)
+            if share == 0:
+                raise ValueError(f"encode: an image of {h} x {w} with a capacity of {cap} bytes is outside what mpn_jpeg_entropy_encode takes")
+            d = self.descs[i]
+            d['src_offset'], d['coef_offset'], d['out_offset'], d['capacity'], d['work_offset'] = off, coef, out, cap, work
+            d['width'], d['height'], d['channels'], d['h_samp'], d['v_samp'] = w, h, channels, hs, vs
+            d['quant'][0], d['quant'][1], d['quant'][2] = tables[0], tables[1], tables[1]
+            self.headers.append(jpeg_headers(w, h, subsampling, tables))
+            coef += blocks * 128
+            out += _round16(cap)
+            work += _round16(share)
+        self.need = (coef, out, work)
+
+
+class JpegBatchEncoder:
+    """Encodes a batch of frames that lie in a packed uint8 buffer on the device.
+
+        encoder = JpegBatchEncoder(device)
+        files = encoder.encode(sources, offsets, shapes, channels, quality=75, subsampling='4:2:0')
+
+    sources: a uint8 device tensor; image i is [h_i, w_i, channels] at byte offsets[i], a multiple of 16; channels 3 (RGB) or
+    4 (RGBA as mpn_draw_detections writes it; alpha is ignored). One descriptor upload, the two device calls, one small copy
+    of the records, then one copy per image of exactly the bytes its stream used, packed into one pinned buffer behind a
+    single synchronise; buffers grow to the largest batch seen. An image whose stream does not fit
+    its capacity (blocks * 64 * BYTES_PER_SAMPLE + 256 bytes) is fetched as pixels and encoded by Pillow: the same bytes.
+    The steps are also there one by one (`reserve`, `upload`, `launch`, `collect`) for a caller that captures `launch` in a
+    graph: the Detector."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if _lib.lib().mpn_jpeg_enc_desc_bytes() != ENC_DESC_BYTES:
+            raise _lib.MpnError("mpn_jpeg_forward: the descriptor's layout is not the one this binding was written against")
+        self.b = self.n = 0                                     # descriptors allocated; images of the batch in place
+        self.capacity = (0, 0, 0)
+        self.fallbacks = 0                                      # images the last `collect` left to Pillow
+        self.copied_bytes = 0                                   # bytes its record and stream copies brought to the host
+        self._coefs = self._out = self._work = self._descs = self._desc_stage = self._records = self._record_host = None
+        self._out_host = None
+
+    def reserve(self, b, coef_bytes, out_bytes, work_bytes):
+        """Buffers for batches of up to b images within the three sizes; True when anything was (re)allocated."""
+        import torch
+        need = (coef_bytes, out_bytes, work_bytes)
+        grow = any(n > c for n, c in zip(need, self.capacity))
+        if not grow and b <= self.b:
+            return False
+        if self._coefs is not None:
+            torch.cuda.synchronize(self.device)                 # (rare) growth: no queued launch still uses the old buffers
+        dev = self.device
+        if grow:
+            self.capacity = tuple(max(_capacity(n), c) for n, c in zip(need, self.capacity))
+            self._coefs = torch.empty(self.capacity[0], dtype=torch.uint8, device=dev)
+            self._out = torch.empty(self.capacity[1], dtype=torch.uint8, device=dev)
+            self._work = torch.empty(self.capacity[2], dtype=torch.uint8, device=dev)
+            self._out_host = torch.empty(self.capacity[1], dtype=torch.uint8).pin_memory()
+        if b > self.b:
+            self.b = b
+            self._desc_stage = torch.zeros(b * ENC_DESC_BYTES, dtype=torch.uint8).pin_memory()
+            self._descs = torch.zeros(b * ENC_DESC_BYTES, dtype=torch.uint8, device=dev)
+            self._records = torch.zeros(b * RECORD_BYTES, dtype=torch.uint8, device=dev)
+            self._record_host = torch.zeros(b * RECORD_BYTES, dtype=torch.uint8).pin_memory()
+        return True
+
+    def upload(self, plan):
+        """This call's descriptors to the device: one small copy on the current stream, ordered before the launch."""
+        n = len(plan.descs)
+        if n > self.b or any(need > c for need, c in zip(plan.need, self.capacity)):
+            raise ValueError("encode: the batch exceeds the reserved buffers")
+        self.n = n
+        self._desc_stage.numpy()[:n * ENC_DESC_BYTES] = plan.descs.view(np.uint8)
+        self._descs[:n * ENC_DESC_BYTES].copy_(self._desc_stage[:n * ENC_DESC_BYTES], non_blocking=True)
+
+    def launch(self, sources):
+        """The two device calls on the current stream (no host synchronisation: capturable)."""
+        st = _lib.stream_ptr()
+        _lib.call("mpn_jpeg_forward", _lib.ptr(sources), sources.numel(), _lib.ptr(self._descs), self.n, _lib.ptr(self._coefs),
+                  self._coefs.numel(), st)
+        _lib.call("mpn_jpeg_entropy_encode", _lib.ptr(self._coefs), self._coefs.numel(), _lib.ptr(self._descs), self.n,
+                  _lib.ptr(self._out), self._out.numel(), _lib.ptr(self._records), _lib.ptr(self._work), self._work.numel(), st)
+
+    def collect(self, plan, sources):
+        """The records, then the bytes used -> the files. Only [offset, offset + size) of every written stream is copied: one
+        asynchronous copy per image into a PACKED pinned buffer, then one synchronise (`.copied_bytes`: records + streams). An
+        image that did not fit is fetched as pixels and left to Pillow."""
+        import torch
+        stream = torch.cuda.current_stream(self.device)
+        n = len(plan.descs)
+        self._record_host[:n * RECORD_BYTES].copy_(self._records[:n * RECORD_BYTES], non_blocking=True)
+        stream.synchronize()
+        records = self._record_host.numpy().view(RECORD)[:n].copy()
+        packed, at = [], 0
+        for r in records:
+            packed.append(at)
+            if r['status'] == ENC_OK:                            # (size <= capacity, and the capacities fit the buffer)
+                off, size = int(r['offset']), int(r['size'])
+                self._out_host[at:at + size].copy_(self._out[off:off + size], non_blocking=True)
+                at += size
+        if at:
+            stream.synchronize()
+        self.copied_bytes = n * RECORD_BYTES + at
+        host = self._out_host.numpy()
+        files, self.fallbacks = [], 0
+        for i, r in enumerate(records):
+            if r['status'] == ENC_OK:
+                files.append(plan.headers[i] + host[packed[i]:packed[i] + int(r['size'])].tobytes())
+                continue
+            if r['status'] == ENC_SKIPPED:
+                raise _lib.MpnError(f"mpn_jpeg_entropy_encode skipped image {i}: its descriptor is out of range")
+            (h, w), off = plan.shapes[i], plan.offsets[i]
+            pixels = sources[off:off + h * w * plan.channels].cpu().numpy().reshape(h, w, plan.channels)
+            files.append(pillow_encode(pixels, plan.quality, plan.subsampling))
+            self.fallbacks += 1
+        return files
+
+    def encode(self, sources, offsets, shapes, channels, quality=75, subsampling='4:2:0', stream=None, capacities=None):
+        import torch
+        if sources.dtype != torch.uint8 or not sources.is_contiguous() or sources.device != self.device:
+            raise ValueError("encode: sources must be a contiguous uint8 tensor on the encoder's device")
+        plan = EncodePlan(shapes, offsets, channels, quality, subsampling, capacities)
+        total = sources.numel()
+        for (h, w), off in zip(plan.shapes, plan.offsets):
+            if off < 0 or off + h * w * channels > total:
+                raise ValueError(f"encode: an image of {(h, w, channels)} at byte {off} does not fit a buffer of {total} bytes")
+        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(stream):
+            self.reserve(len(plan.descs), *plan.need)
+            self.upload(plan)
+            self.launch(sources)
+            return self.collect(plan, sources)
+
+
+def encode_jpegs(images, quality=75, subsampling='4:2:0', device=None):
+    """A list of uint8 [h, w, 3] arrays -> a list of `bytes`: the files Pillow writes for them with `save(buf, "JPEG",
+    quality=quality, subsampling=subsampling)`, encoded on the device (one upload of the pixels, `JpegBatchEncoder.encode`)."""
+    import torch
+    items = list(images)
+    if not items:
+        raise ValueError("empty batch")
+    for im in items:
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("an image must be a uint8 [height, width, 3] array")
+    _sampling(subsampling)
+    quality_tables(quality)
+    device = _lib.current_device() if device is None else torch.device(device)
+    offsets, at = [], 0
+    for im in items:
+        offsets.append(at)
+        at += _round16(im.size)
+    stage = torch.zeros(at, dtype=torch.uint8).pin_memory()
+    host = stage.numpy()
+    for im, off in zip(items, offsets):
+        host[off:off + im.size] = im.reshape(-1)
+    sources = stage.to(device, non_blocking=True)
+    return JpegBatchEncoder(device).encode(sources, offsets, [im.shape[:2] for im in items], 3, quality, subsampling)
