@@ -77,6 +77,27 @@ def _encode_plan(sizes, src_offsets, jp):
     return jpeg.EncodePlan([(h, w) for _, h, w in frames], [at for at, _, _ in frames], 4, *jp)
 
 
+def _batch_frames(b, h, w):
+    """(sizes, byte offsets) of the b frames of a fixed uint8 [b, h, w, 3] batch, as draw.layout and _encode_plan take them."""
+    return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
+
+
+class _Entry:
+    """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
+    input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
+    it last ran with, the drawing and encode state of an annotate entry, and the packed sources, descriptors (with their
+    staging), intermediates and JPEG decoder of the ragged paths. What a path does not use stays None."""
+    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan',
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg')
+
+    def __init__(self, **buffers):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.host = {}
+        for name, buffer in buffers.items():
+            setattr(self, name, buffer)
+
+
 def _no_persons(num_boxes=0):
     return {'boxes': np.zeros([0, 4], np.float32), 'scores': np.zeros([0], np.float32), 'num_boxes': np.int32(num_boxes),
             'keypoint_scores': np.zeros([0, NUM_KEYPOINTS], np.float32), 'keypoint_positions': np.zeros([0, NUM_KEYPOINTS, 2], np.float32),
@@ -143,7 +164,7 @@ class Detector:
             from ..retinanet import PersonDetectorNet
             head = _load(detector_path)
             self.retinanet = PersonDetectorNet(backbone=self.net)
-            self.retinanet.cache_inference_affine = True    # as for the backbone; _replay compares the variable versions
+            self.retinanet.cache_inference_affine = True    # as for the backbone; _run compares the variable versions
             own = set(self.retinanet.vars) | set(self.retinanet.stats)
             self.retinanet.load_state_dict({k: v for k, v in head.items() if k in own}, strict=True)
         self.assigner = None
@@ -227,27 +248,37 @@ class Detector:
         """The device side of a call from a hipGraph captured once per image shape (an eager call first: it sizes the buffers and
         sets kernel attributes); the host copies the image into the graph's input and reads its outputs."""
         h, w, _ = image.shape
-        ent = self._graphs.get((h, w))
-        src = torch.from_numpy(np.ascontiguousarray(image[None]))
+        held = self._graphs.get((h, w))
+        ent = held[1] if held else _Entry(x=torch.empty((1, h, w, 3), dtype=torch.uint8, device=self.net.device))
+        ent.x.copy_(torch.from_numpy(np.ascontiguousarray(image[None])))
+        outs = self._run(ent, lambda: self._device_side(ent.x, True))
+        if held is None:
+            self._graphs[(h, w)] = [ent.graph, ent]     # element 0 is the graph: bench_legs.joint_inference_benchmark reads it there
+        return outs
+
+    def _run(self, ent, device_side):
+        """The one capture / replay state machine of every predict path. device_side() queues the device work of a call over
+        the entry's buffers and returns its outputs. use_graph False: just that. Else the first call of an entry runs it
+        eagerly (the warm-up sizes the buffers, sets kernel attributes and fills the inference caches), synchronises and
+        captures it over this call's data; every call then replays the graph."""
         ver = self._variable_versions()
-        if ent is None:
-            x = src.to(self.net.device)
-            self._device_side(x, True)                              # eager warm-up (also fills the inference caches)
+        if not self.use_graph:
+            return device_side()
+        if ent.graph is None:
+            device_side()
             torch.cuda.synchronize(self.net.device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                outs = self._device_side(x, True)
-            ent = self._graphs[(h, w)] = [graph, x, outs, ver]
-        graph, x, outs, captured_ver = ent
-        x.copy_(src)
-        if captured_ver != ver:
+                ent.outs = device_side()
+            ent.graph, ent.ver = graph, ver
+        elif ent.ver != ver:
             # variables changed since this graph last ran (load_state_dict, a train step on the shared backbone ...): the
             # batch-norm affines and the cast operands the captured launches read are host-cached and NOT in the graph. One
             # eager pass refreshes them through the normal code path into the same persistent buffers the graph reads.
-            self._device_side(x, True)
-            ent[3] = ver
-        graph.replay()
-        return outs
+            device_side()
+            ent.ver = ver
+        ent.graph.replay()
+        return ent.outs
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
@@ -273,31 +304,23 @@ class Detector:
         b, h, w = check_batch(images)
         thr = float(score_threshold)
         ent = self._batch_entry(b, h, w, thr, bool(annotate), jp)
-        if jp and ent['encode_plan'].quality != jp[0]:              # the frames are fixed: only another quality needs new descriptors
-            self._place_encode(ent, _encode_plan([(h, w)] * b, [i * h * w * 3 for i in range(b)], jp))
-        stage = ent['stage'].numpy()
+        if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
+            self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), jp))
+        stage = ent.stage.numpy()
         if isinstance(images, np.ndarray):
             stage[...] = images
         else:
             for i, im in enumerate(images):
                 stage[i] = im
-        ent['x'].copy_(ent['stage'], non_blocking=True)             # ONE host-to-device copy
-        ver = self._variable_versions()
-        if ent['graph'] is None:
-            outs = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
-        else:
-            if ent['ver'] != ver:      # as in _replay: the host-cached affines / operand casts the captured launches read
-                self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
-                ent['ver'] = ver
-            ent['graph'].replay()
-            outs = ent['outs']
+        ent.x.copy_(ent.stage, non_blocking=True)                   # ONE host-to-device copy
+        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode))
         return self._finish(ent, outs, b, return_heatmaps)
 
     @staticmethod
     def _place_encode(ent, plan):
         """This call's encode descriptors (geometry, offsets, quantisation tables) go to the device: one small copy."""
-        ent['encode_plan'] = plan
-        ent['encode'].upload(plan)
+        ent.encode_plan = plan
+        ent.encode.upload(plan)
 
     def _finish(self, ent, outs, b, return_heatmaps):
         """The host side behind the device side of predict_batch / predict_images: the record (and the maps) into pinned
@@ -308,17 +331,17 @@ class Detector:
         for name, src in copies:                                    # ONE device-to-host copy each, into pinned memory
             if src is None:
                 continue
-            if name not in ent['host']:
-                ent['host'][name] = torch.empty(src.shape, dtype=src.dtype).pin_memory()
-            ent['host'][name].copy_(src, non_blocking=True)
+            if name not in ent.host:
+                ent.host[name] = torch.empty(src.shape, dtype=src.dtype).pin_memory()
+            ent.host[name].copy_(src, non_blocking=True)
         if 'annotated' in outs:                                     # this batch's bytes of the packed frames, not the capacity
-            if 'annotated' not in ent['host']:
-                ent['host']['annotated'] = torch.empty(outs['annotated'].shape, dtype=torch.uint8).pin_memory()
-            nb = ent['draw'].out_bytes
-            ent['host']['annotated'][:nb].copy_(outs['annotated'][:nb], non_blocking=True)
+            if 'annotated' not in ent.host:
+                ent.host['annotated'] = torch.empty(outs['annotated'].shape, dtype=torch.uint8).pin_memory()
+            nb = ent.draw.out_bytes
+            ent.host['annotated'][:nb].copy_(outs['annotated'][:nb], non_blocking=True)
         torch.cuda.current_stream(self.net.device).synchronize()
-        host = ent['host']
-        files = ent['encode'].collect(ent['encode_plan'], outs['encoded']) if 'encoded' in outs else None
+        host = ent.host
+        files = ent.encode.collect(ent.encode_plan, outs['encoded']) if 'encoded' in outs else None
         if 'record' in outs:
             persons = unpack_record(host['record'].numpy(), b, self.params['max_boxes'], self.assigner is not None)
         else:                                                       # no detector_path: no boxes are detected
@@ -328,7 +351,7 @@ class Detector:
             for i, p in enumerate(persons):
                 p['keypoint_heatmaps'], p['segmentation_masks'] = heat[i], seg[i]
         if 'annotated' in outs:
-            for p, frame in zip(persons, ent['draw'].unpack(host['annotated'].numpy())):
+            for p, frame in zip(persons, ent.draw.unpack(host['annotated'].numpy())):
                 p['annotated'] = frame
         if files is not None:
             for p, data in zip(persons, files):
@@ -336,8 +359,8 @@ class Detector:
         return persons
 
     def _batch_entry(self, b, h, w, thr, annotate=False, jp=None):
-        """The persistent state of one (b, h, w, threshold[, annotate]): pinned staging, the device input, the captured graph and
-        its outputs. use_graph False: the same buffers, the device side runs eagerly on every call."""
+        """The buffers of one (b, h, w, threshold[, annotate]): pinned staging, the device input, fixed drawing and encode
+        descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
         if annotate:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
@@ -346,24 +369,16 @@ class Detector:
         if ent is not None:
             return ent
         dev = self.net.device
-        ent = {'stage': torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory(),
-               'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        ent = _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory(),
+                     x=torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev))
         if annotate:                                                # the frames are the batch itself: fixed descriptors
-            ent['draw'] = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
-            ent['draw'].place([(h, w)] * b, [i * h * w * 3 for i in range(b)])
+            ent.draw = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
+            ent.draw.place(*_batch_frames(b, h, w))
         if jp:                                                      # the frames lie where the drawing writes them: fixed sizes
-            plan = _encode_plan([(h, w)] * b, [i * h * w * 3 for i in range(b)], jp)
-            ent['encode'] = jpeg.JpegBatchEncoder(dev)
-            ent['encode'].reserve(b, *plan.need)
+            plan = _encode_plan(*_batch_frames(b, h, w), jp)
+            ent.encode = jpeg.JpegBatchEncoder(dev)
+            ent.encode.reserve(b, *plan.need)
             self._place_encode(ent, plan)
-        if self.use_graph:
-            ent['x'].zero_()
-            self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))    # eager warm-up: sizes the buffers, sets kernel attributes
-            torch.cuda.synchronize(dev)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                ent['outs'] = self._device_side_batch(ent['x'], thr, annotate=ent.get('draw'), encode=ent.get('encode'))
-            ent['graph'], ent['ver'] = graph, self._variable_versions()
         store[key] = ent
         return ent
 
@@ -448,41 +463,14 @@ class Detector:
         items = resample.check_images(images)
         height, width = resample.check_size(size)
         plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
-        b, thr = len(items), float(score_threshold)
-        eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
-        ent = self._images_entry(b, height, width, thr, plan, bool(annotate), eplan)
-        stage = ent['stage'].numpy()
-        for im, at in zip(items, plan.src_offsets):
-            stage[at:at + im.size] = im.reshape(-1)
-        ent['meta_stage'].numpy()[:plan.meta_words] = plan.meta
-        nb, nw = plan.stage_bytes, plan.meta_words                  # this batch's bytes, not the buffers' capacity
-        ent['sources'][:nb].copy_(ent['stage'][:nb], non_blocking=True)      # ONE host-to-device copy of the frames,
-        ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)    # one of the descriptors, extents and tables
-        if annotate:
-            ent['draw'].place(plan.sizes, plan.src_offsets)
-        if jp:
-            self._place_encode(ent, eplan)
-        ver = self._variable_versions()
-        if not self.use_graph:
-            outs = self._device_side_images(ent, thr)
-        else:
-            if ent['graph'] is None:   # captured over THIS call's descriptors: the warm-up runs the kernels for real
-                self._device_side_images(ent, thr)
-                torch.cuda.synchronize(self.net.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    ent['outs'] = self._device_side_images(ent, thr)
-                ent['graph'], ent['ver'] = graph, ver
-            elif ent['ver'] != ver:    # as in predict_batch
-                self._device_side_images(ent, thr)
-                ent['ver'] = ver
-            ent['graph'].replay()
-            outs = ent['outs']
-        persons = self._finish(ent, outs, b, return_heatmaps)
-        if return_heatmaps:
-            for p, new_size in zip(persons, plan.new_sizes):
-                p['resized_size'] = new_size
-        return persons
+
+        def upload(ent):
+            stage = ent.stage.numpy()
+            for im, at in zip(items, plan.src_offsets):
+                stage[at:at + im.size] = im.reshape(-1)
+            nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
+            ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
+        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
@@ -515,36 +503,29 @@ class Detector:
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
                 raise ValueError(f"a JPEG decodes to {tuple(e.shape)}, its header says {(h, w, 3)}")
-        b, thr = len(items), float(score_threshold)
+
+        def decode(ent):
+            if ent.jpeg is None:
+                ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
+            ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
+        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps)
+
+    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps):
+        """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
+        frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
+        one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
+        b, thr = plan.b, float(score_threshold)
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
-        ent = self._images_entry(b, height, width, thr, plan, bool(annotate), eplan)
-        if 'jpeg' not in ent:
-            ent['jpeg'] = jpeg.JpegBatchDecoder(self.net.device)
-        ent['meta_stage'].numpy()[:plan.meta_words] = plan.meta
-        nw = plan.meta_words
-        ent['meta'][:nw].copy_(ent['meta_stage'][:nw], non_blocking=True)
-        ent['jpeg'].decode(entries, ent['sources'], plan.src_offsets, torch.cuda.current_stream(self.net.device))
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan)
+        nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
+        ent.meta_stage.numpy()[:nw] = plan.meta
+        ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
+        put_sources(ent)
         if annotate:
-            ent['draw'].place(plan.sizes, plan.src_offsets)
+            ent.draw.place(plan.sizes, plan.src_offsets)
         if jp:
             self._place_encode(ent, eplan)
-        ver = self._variable_versions()
-        if not self.use_graph:
-            outs = self._device_side_images(ent, thr)
-        else:
-            if ent['graph'] is None:   # as in predict_images: captured over this call's descriptors
-                self._device_side_images(ent, thr)
-                torch.cuda.synchronize(self.net.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    ent['outs'] = self._device_side_images(ent, thr)
-                ent['graph'], ent['ver'] = graph, ver
-            elif ent['ver'] != ver:
-                self._device_side_images(ent, thr)
-                ent['ver'] = ver
-            ent['graph'].replay()
-            outs = ent['outs']
-        persons = self._finish(ent, outs, b, return_heatmaps)
+        persons = self._finish(ent, self._run(ent, lambda: self._device_side_images(ent, thr)), b, return_heatmaps)
         if return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):
                 p['resized_size'] = new_size
@@ -576,29 +557,29 @@ class Detector:
         stage_bytes, meta_words, work_bytes = cap[:3]
         if _lib.lib().mpn_image_resize_desc_bytes() != resample.DESC_WORDS * 4:
             raise _lib.MpnError("mpn_image_resize: the descriptor's layout is not the one this binding was written against")
-        ent = {'stage': torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
-               'sources': torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
-               'meta_stage': torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
-               'meta': torch.zeros(meta_words, dtype=torch.int32, device=dev),
-               'work': torch.empty(work_bytes, dtype=torch.uint8, device=dev),
-               'x': torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev), 'host': {}, 'graph': None, 'outs': None, 'ver': None}
+        ent = _Entry(stage=torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
+                     sources=torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
+                     meta_stage=torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
+                     meta=torch.zeros(meta_words, dtype=torch.int32, device=dev),
+                     work=torch.empty(work_bytes, dtype=torch.uint8, device=dev),
+                     x=torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev))
         if annotate:
-            ent['draw'] = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
+            ent.draw = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
         if eplan:
-            ent['encode'] = jpeg.JpegBatchEncoder(dev)
-            ent['encode'].reserve(b, *cap[3:])
+            ent.encode = jpeg.JpegBatchEncoder(dev)
+            ent.encode.reserve(b, *cap[3:])
         store[key] = ent
         return ent
 
     def _device_side_images(self, ent, thr):
         """mpn_image_resize (ragged sources -> the uint8 canvas batch) -> _device_side_batch with mpn_pose_gather_sized last."""
-        x, meta = ent['x'], ent['meta']
+        x, meta = ent.x, ent.meta
         b, h, w, _ = x.shape
         extent = meta[b * resample.DESC_WORDS:b * (resample.DESC_WORDS + 4)].view(torch.float32).view(b, 4)
         tables = meta[b * (resample.DESC_WORDS + 4):]
-        _lib.call("mpn_image_resize", _lib.ptr(ent['sources']), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
-                  _lib.ptr(ent['work']), ent['work'].numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent, annotate=ent.get('draw'), frames=ent['sources'], encode=ent.get('encode'))
+        _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
+                  _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
+        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

@@ -5,13 +5,10 @@ packed output, the descriptors, the device buffers of one batch shape and the la
 import numpy as np
 
 from .. import _lib
+from .resample import _round16
 
 DESC_WORDS = 8                         # mpn_draw_desc in 32-bit words (32 bytes; checked against the library)
 MAX_BOXES = 128                        # MPN_DRAW_MAX_BOXES
-
-
-def _round16(n):
-    return (int(n) + 15) // 16 * 16
 
 
 def out_capacity(source_bytes, b):

@@ -11,6 +11,8 @@ import io
 import numpy as np
 
 from .. import _lib
+from ..model_state import resolve_device
+from .resample import _round16, capacity_for
 
 DESC_BYTES = 512                        # MPN_JPEG_DESC_BYTES (checked against the library)
 REASONS = ('supported', 'malformed', 'progressive', 'arithmetic', 'frame_type', 'precision', 'components', 'colorspace',
@@ -105,13 +107,8 @@ def prepare(item):
     return pillow_decode(data)
 
 
-def _round16(n):
-    return (int(n) + 15) // 16 * 16
-
-
 def _capacity(n):
-    n = max(int(n), 16)
-    return 1 << (n - 1).bit_length()
+    return capacity_for(max(n, 16))
 
 
 class JpegBatchDecoder:
@@ -127,10 +124,7 @@ class JpegBatchDecoder:
     consumer: the next `decode` waits for the previous one's copy before it reuses the staging."""
 
     def __init__(self, device):
-        import torch
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = resolve_device(device)
         if _lib.lib().mpn_jpeg_desc_bytes() != DESC_BYTES:
             raise _lib.MpnError("mpn_jpeg_decode: the descriptor's layout is not the one this binding was written against")
         self._stage = self._dev = self._work = None
@@ -363,10 +357,7 @@ class JpegBatchEncoder:
     graph: the Detector."""
 
     def __init__(self, device):
-        import torch
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = resolve_device(device)
         if _lib.lib().mpn_jpeg_enc_desc_bytes() != ENC_DESC_BYTES:
             raise _lib.MpnError("mpn_jpeg_forward: the descriptor's layout is not the one this binding was written against")
         self.b = self.n = 0                                     # descriptors allocated; images of the batch in place

@@ -104,3 +104,33 @@ def test_predict_images_graph_behaviour(cuda, models):
     for x, y in zip(det.predict_batch(fixed, score_threshold=0.0), batch_before):
         _assert_same(x, y, "predict_batch after predict_images:")
     _assert_same(det(fixed[0], score_threshold=0.0), call_before, "__call__ after predict_images:")
+
+
+def test_ragged_paths_follow_reloaded_variables(cuda, models):
+    """predict_images and predict_jpegs replay a captured graph whose batch-norm affines and operand casts are cached on the host:
+    after load_state_dict the same graph must give, exactly, what a fresh eager Detector on the new variables gives. Needs no
+    detections (canvas 128 x 128, class bias -6): the heatmaps and num_boxes carry the comparison."""
+    from multiposenet_amd.inference import Detector
+    from test_jpeg_host import goldens
+    g = goldens()
+    jpegs = [g[name][0] for name in ("1x1_420", "8x8_444")]       # the smallest 4:2:0 and the smallest 4:4:4 decode golden
+    frames = [np.random.RandomState(s).randint(0, 256, (h, w, 3)).astype(np.uint8) for s, (h, w) in ((1, (128, 128)), (2, (97, 131)))]
+    bb2, hp2, _ = _variables(seed=47, class_seed=47)
+    fresh = Detector(bb2, dtype=torch.float32, detector_path=hp2, prn_path=models["paths"]["p"])
+    fresh.use_graph = False
+    kwargs = dict(size=(128, 128), return_heatmaps=True, score_threshold=0.0)
+    # (a Detector per method: both share the graph entry, and each first call must be a capture)
+    for method, sources in (("predict_images", frames), ("predict_jpegs", jpegs)):
+        det = _detector(models, dtype=torch.float32)
+        first = getattr(det, method)(sources, **kwargs)
+        keys = set(det._graphs)
+        det.net.load_state_dict(bb2)
+        own = set(det.retinanet.vars) | set(det.retinanet.stats)
+        det.retinanet.load_state_dict({k: v for k, v in hp2.items() if k in own})
+        got = getattr(det, method)(sources, **kwargs)
+        assert set(det._graphs) == keys and len(keys) == 1                         # the same graph, refreshed caches
+        want = getattr(fresh, method)(sources, **kwargs)
+        assert len(got) == len(want) == 2
+        for a, b in zip(got, want):
+            _assert_same(a, b, f"{method} after load_state_dict:")
+        assert not np.array_equal(got[0]["keypoint_heatmaps"], first[0]["keypoint_heatmaps"])

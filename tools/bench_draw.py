@@ -124,16 +124,16 @@ def main():
         host_draw_ms = (time.perf_counter() - t0) * 1e3 / b
 
     ent = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and k[-1] == "annotate")
-    buf, record = ent["draw"], ent["outs"]["record"]
+    buf, record = ent.draw, ent.outs["record"]
     pixels = sum(f.shape[0] * f.shape[1] for f in frames)
     moved = 7 * pixels
-    draw_ms = [events_ms(lambda: buf.launch(ent["sources"], record, True), args.replays) for _ in range(args.rounds)]
-    graph_ms = [events_ms(ent["graph"].replay, 20) for _ in range(args.rounds)]
-    plain_graph = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and k[-1] != "annotate")["graph"]
+    draw_ms = [events_ms(lambda: buf.launch(ent.sources, record, True), args.replays) for _ in range(args.rounds)]
+    graph_ms = [events_ms(ent.graph.replay, 20) for _ in range(args.rounds)]
+    plain_graph = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and k[-1] != "annotate").graph
     plain_graph_ms = [events_ms(plain_graph.replay, 20) for _ in range(args.rounds)]
     a, c = torch.empty(moved // 2, dtype=torch.uint8, device=buf.out.device), torch.empty(moved // 2, dtype=torch.uint8, device=buf.out.device)
     copy_ms = [events_ms(lambda: c.copy_(a), args.replays) for _ in range(args.rounds)]
-    nb, pinned = buf.out_bytes, ent["host"]["annotated"]
+    nb, pinned = buf.out_bytes, ent.host["annotated"]
     d2h_ms = [events_ms(lambda: pinned[:nb].copy_(buf.out[:nb], non_blocking=True), 10) for _ in range(args.rounds)]
     t0 = time.perf_counter()
     for _ in range(3):

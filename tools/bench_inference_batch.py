@@ -96,7 +96,7 @@ def main():
             wall[name].append((time.perf_counter() - t0) / images)
     graphs = {"call_loop": (det._graphs[(s, s)][0], 1)}
     for b in BATCHES:
-        graphs[f"b{b}"] = (det._graphs[(b, s, s, thr)]["graph"], b)
+        graphs[f"b{b}"] = (det._graphs[(b, s, s, thr)].graph, b)
     device = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, (g, b) in graphs.items():

@@ -103,7 +103,7 @@ def main():
     pool.shutdown()
 
     ent = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and "jpeg" in k)
-    enc, plan, rgba = ent["encode"], ent["encode_plan"], ent["outs"]["encoded"]
+    enc, plan, rgba = ent.encode, ent.encode_plan, ent.outs["encoded"]
     fallbacks = enc.fallbacks
     scan_bytes = [n - len(h) for n, h in zip(file_bytes, plan.headers)]
     if fallbacks == 0:                                              # what `collect` copied: the records and the streams, no more
@@ -120,8 +120,8 @@ def main():
 
     forward_ms = [events_ms(forward, args.replays) for _ in range(args.rounds)]
     entropy_ms = [events_ms(entropy, args.replays) for _ in range(args.rounds)]
-    graph_ms = [events_ms(ent["graph"].replay, 20) for _ in range(args.rounds)]
-    drawn_graph = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and k[-1] == "annotate")["graph"]
+    graph_ms = [events_ms(ent.graph.replay, 20) for _ in range(args.rounds)]
+    drawn_graph = next(v for k, v in det._graphs.items() if isinstance(k, tuple) and k[0] == "images" and k[-1] == "annotate").graph
     drawn_graph_ms = [events_ms(drawn_graph.replay, 20) for _ in range(args.rounds)]
     pixels = sum(f.shape[0] * f.shape[1] for f in frames)
 

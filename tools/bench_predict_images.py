@@ -109,16 +109,16 @@ def main():
             wall[name].append((time.perf_counter() - t0) / (args.batches * b))
     key = next(k for k in det._graphs if isinstance(k, tuple) and k[0] == "images")
     ent = det._graphs[key]
-    meta = ent["meta"]
+    meta = ent.meta
     tables = meta[b * (resample.DESC_WORDS + 4):]
 
     def resize_only():
-        _lib.call("mpn_image_resize", _lib.ptr(ent["sources"]), _lib.ptr(tables), _lib.ptr(meta), b, s, s, _lib.ptr(ent["x"]),
-                  _lib.ptr(ent["work"]), ent["work"].numel(), _lib.stream_ptr())
+        _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, s, s, _lib.ptr(ent.x),
+                  _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
 
-    graph_ms = [events_ms(ent["graph"].replay, 20) / b for _ in range(args.rounds)]
+    graph_ms = [events_ms(ent.graph.replay, 20) / b for _ in range(args.rounds)]
     resize_ms = [events_ms(resize_only, 20) / b for _ in range(args.rounds)]
-    batch_graph = det._graphs[(b, s, s, thr)]["graph"]
+    batch_graph = det._graphs[(b, s, s, thr)].graph
     batch_ms = [events_ms(batch_graph.replay, 20) / b for _ in range(args.rounds)]
     plan = resample.Plan([f.shape[:2] for f in frames], s, s)
     result = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "batch": b, "source": [sh, sw], "size": [s, s],
