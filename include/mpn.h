@@ -887,6 +887,62 @@ int mpn_draw_detections(const uint8_t* sources, size_t sources_bytes, const void
                         void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Heatmap and mask overlays: `plot_maps` of the reference's inference/predict.ipynb (the cells under "Show heatmaps") for
+ * a batch of B frames of one size, equal byte for byte to what Pillow and matplotlib make there. With h = H / 2, w = W / 2
+ * (integer division), panel j of frame b is rows j*h .. j*h + h - 1 of out_rgba[b]: the frame resized to (w, h) with
+ * Pillow's Lanczos filter, alpha 255; over it panel j's overlay by `Image.alpha_composite`; then label j blended in red.
+ *   overlay j < 17   heatmap channel j -> [minmax_keys != NULL: (x - m) / (M - m) per frame and channel, f32, correctly
+ *                    rounded; M == m gives NaN] -> the colormap entry (matplotlib's rule for f32: NaN transparent (0,0,0,0),
+ *                    x < 0 entry 0, x*256 >= 256 entry 255, else entry trunc(x*256)) -> Pillow's RGBA resize to (w, h):
+ *                    premultiplied by alpha (MULDIV255; the table arrives premultiplied), horizontal then vertical Lanczos
+ *                    pass through a uint8 intermediate, un-premultiplied (alpha 0 or 255: the pixel as it is, else
+ *                    clip8(255 * c / alpha) in integers)
+ *   overlay 17       trunc(255 * clip(mask, 0, 1)) as ONE band through the same two passes, that band as R, G, B and alpha
+ *                    (mask == NULL: a transparent overlay). Inputs are finite.
+ *   label j          stamp j of the tables (L8 pixels [sh, sw]) at (ox, j*h + oy): Pillow's BLEND8 of (255, 0, 0, 255) over
+ *                    all four bands, weight = the stamp's pixel, clipped to the panel
+ * Every pass is clip8((sum_k pixel[first + k] * coeff[k] + 2^21) >> 22) in int32 on the HOST's coefficient tables
+ * (multiposenet_amd/inference/resample.py, filter 'lanczos'), as mpn_image_resize.
+ *
+ *   frames       [B,H,W,3] uint8            heatmaps  [B,hh,hw,17] f32            mask  [B,hh,hw] f32 or NULL
+ *   minmax_keys  mpn_heatmap_minmax's keys of `heatmaps` (B*17*2 words), or NULL: the heatmaps as given
+ *   tables       int32 words, DEVICE, 16-byte aligned: per axis bounds [out,2] = (first tap, tap count) and coeffs
+ *                [out,ksize]; the colour table, 256 words (R in the low byte), premultiplied; 18 stamp descriptors of 8
+ *                words (byte offset into the packed pixels, sw, sh, ox, oy, 3 reserved); the stamps' packed L8 pixels
+ *   desc         ONE mpn_plot_maps_desc in HOST memory: where each part lies in tables (word offsets). Checked against
+ *                table_words before any launch (MPN_ERR_BAD_ARG). What the tables HOLD is read on the device: a tap window is
+ *                clamped to its source and a stamp that leaves stamp_bytes is not blended - no content of tables makes a
+ *                kernel touch memory outside its buffers.
+ *   out_rgba     [B, 18*h, w, 4] uint8, 16-byte aligned. EVERY byte is written.
+ *   workspace    mpn_plot_maps_workspace_bytes(B, H, W, hh, hw) bytes (0 for arguments out of range), 16-byte aligned: the
+ *                horizontally resampled rows [B,H,w4,4] of the frames and [B,hh,18,w4,4] of the overlays, w4 = w rounded up
+ *                to 4
+ * Three launches; grid and block sizes depend on (B, H, W, hh, hw) alone, so the call can be captured.
+ * Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535, 2 <= H <= 65535, 2 <= W <= 65536,
+ * 1 <= hh <= 3640, 1 <= hw <= 65536 (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); workspace_bytes (MPN_ERR_WORKSPACE).
+ */
+#define MPN_PLOT_MAPS_PANELS 18
+#define MPN_PLOT_MAPS_DESC_BYTES 64
+typedef struct mpn_plot_maps_desc {
+    int32_t bounds_fx, coeffs_fx, ksize_fx;     /* frame, horizontal: W -> w */
+    int32_t bounds_fy, coeffs_fy, ksize_fy;     /* frame, vertical:   H -> h */
+    int32_t bounds_mx, coeffs_mx, ksize_mx;     /* maps, horizontal:  hw -> w */
+    int32_t bounds_my, coeffs_my, ksize_my;     /* maps, vertical:    hh -> h */
+    int32_t lut;                                /* the premultiplied colour table, 256 words */
+    int32_t stamps;                             /* 18 stamp descriptors of 8 words, a multiple of 4 */
+    int32_t stamp_pixels;                       /* the stamps' packed L8 pixels */
+    int32_t stamp_bytes;                        /* ... and how many bytes they are */
+} mpn_plot_maps_desc;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_plot_maps_desc) == MPN_PLOT_MAPS_DESC_BYTES, "descriptor size is fixed");
+#endif
+size_t mpn_plot_maps_desc_bytes(void);
+size_t mpn_plot_maps_workspace_bytes(int B, int H, int W, int hh, int hw);
+int mpn_plot_maps(const uint8_t* frames, const float* heatmaps, const float* mask, const void* minmax_keys,
+                  const int32_t* tables, size_t table_words, const void* desc, int B, int H, int W, int hh, int hw,
+                  uint8_t* out_rgba, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * JPEG decode, split in two: the serial part on the HOST, the parallel part on the device. The result equals what
  * libjpeg(-turbo) - and so Pillow's `Image.open(...).convert("RGB")` - returns for the same bytes, byte for byte.
  *

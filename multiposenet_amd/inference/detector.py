@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib
 from ..net import KeypointNet
-from . import draw, jpeg, resample
+from . import draw, jpeg, maps, resample
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -71,6 +71,16 @@ def check_annotate(annotate, jpeg_quality, jpeg_subsampling):
     return int(jpeg_quality), jpeg_subsampling
 
 
+def check_plot_maps(plot_maps, heatmap_outputs):
+    """The `plot_maps` argument of the predict_* methods -> bool. True needs a graph with heatmap outputs (a bool, or a
+    callable asked only then): without them there is nothing to plot, and that is an error up front, not an empty picture."""
+    if not isinstance(plot_maps, (bool, np.bool_)):
+        raise ValueError(f"plot_maps must be False or True (got {plot_maps!r})")
+    if plot_maps and not (heatmap_outputs() if callable(heatmap_outputs) else heatmap_outputs):
+        raise ValueError("plot_maps=True needs the keypoint subnet's heatmap outputs; this Detector has none")
+    return bool(plot_maps)
+
+
 def _encode_plan(sizes, src_offsets, jp):
     """The encode of the annotated frames where mpn_draw_detections writes them (RGBA, draw.layout's offsets)."""
     _, frames, _ = draw.layout(sizes, src_offsets)
@@ -85,9 +95,10 @@ def _batch_frames(b, h, w):
 class _Entry:
     """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
     input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
-    it last ran with, the drawing and encode state of an annotate entry, and the packed sources, descriptors (with their
-    staging), intermediates and JPEG decoder of the ragged paths. What a path does not use stays None."""
-    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan',
+    it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, and the packed
+    sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    stays None."""
+    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps',
                  'sources', 'meta_stage', 'meta', 'work', 'jpeg')
 
     def __init__(self, **buffers):
@@ -282,7 +293,7 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0'):
+                      jpeg_subsampling='4:2:0', plot_maps=False):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -297,13 +308,19 @@ class Detector:
                 graph where the frame lies; only the compressed bytes are copied to the host.
             jpeg_quality, jpeg_subsampling: 1..100 and '4:4:4', '4:2:2' or '4:2:0'. The quality travels in descriptors: another
                 quality replays the same graph; the sampling is part of the graph's key.
+            plot_maps: True adds 'maps', a uint8 [18 * (height // 2), width // 2, 4] RGBA array: inference/predict.ipynb's
+                `plot_maps` of the image, its heatmaps normalised per channel as the notebook normalises them, and its
+                segmentation mask, byte for byte what Pillow and matplotlib make of them (made on the device inside the
+                captured graph, a graph of its own; only the picture is copied to the host, with return_heatmaps False too).
+                Combines freely with annotate.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         b, h, w = check_batch(images)
         thr = float(score_threshold)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps)
         if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
             self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), jp))
         stage = ent.stage.numpy()
@@ -313,7 +330,7 @@ class Detector:
             for i, im in enumerate(images):
                 stage[i] = im
         ent.x.copy_(ent.stage, non_blocking=True)                   # ONE host-to-device copy
-        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode))
+        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps))
         return self._finish(ent, outs, b, return_heatmaps)
 
     @staticmethod
@@ -328,6 +345,8 @@ class Detector:
         copies = [('record', outs.get('record'))]
         if return_heatmaps:
             copies += [('heat', outs['heat']), ('seg', outs['seg'])]
+        if 'maps' in outs:
+            copies.append(('maps', outs['maps']))
         for name, src in copies:                                    # ONE device-to-host copy each, into pinned memory
             if src is None:
                 continue
@@ -356,14 +375,19 @@ class Detector:
         if files is not None:
             for p, data in zip(persons, files):
                 p['annotated_jpeg'] = data
+        if 'maps' in outs:
+            for p, frame in zip(persons, host['maps'].numpy().copy()):
+                p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None):
-        """The buffers of one (b, h, w, threshold[, annotate]): pinned staging, the device input, fixed drawing and encode
-        descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False):
+        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps]): pinned staging, the device input, fixed drawing and
+        encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
         if annotate:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
+        if plot_maps:
+            key += ('maps',)
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -379,22 +403,27 @@ class Detector:
             ent.encode = jpeg.JpegBatchEncoder(dev)
             ent.encode.reserve(b, *plan.need)
             self._place_encode(ent, plan)
+        if plot_maps:
+            ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
         store[key] = ent
         return ent
 
-    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None):
+    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
         draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat uint8; default:
         the batch x itself) -> 'annotated', the packed RGBA frames. encode (a jpeg.JpegBatchEncoder whose descriptors are in
-        place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'."""
+        place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'.
+        plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'."""
         net = self.net
         b, h, w, _ = x.shape
         bufs = net._buffers(b, h, w)
         feats = net.backbone_forward(x, False, bufs)
         heat, seg = net.subnet_forward(feats, False, bufs, inference_outputs=True)
         dev = {'heat': heat, 'seg': seg}
+        if plotter is not None:
+            dev['maps'] = plotter.launch(x, heat, seg, normalise=True)
         if annotate is not None and frames is None:
             frames = x.view(-1)
         if self.retinanet is None:
@@ -435,7 +464,7 @@ class Detector:
 
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
+                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -454,12 +483,14 @@ class Detector:
                 byte (drawn on the device inside the captured graph, from the frames already uploaded for the resize).
                 'jpeg' adds 'annotated_jpeg' instead, as `predict_batch` does: the file Pillow writes for that frame.
             jpeg_quality, jpeg_subsampling: as for `predict_batch`.
+            plot_maps: as for `predict_batch`; the picture shows the network's input, the resized CANVAS (padding included).
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
         raises ValueError.
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         items = resample.check_images(images)
         height, width = resample.check_size(size)
         plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
@@ -470,11 +501,11 @@ class Detector:
                 stage[at:at + im.size] = im.reshape(-1)
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
-        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps)
+        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0'):
+                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -483,12 +514,13 @@ class Detector:
 
         Arguments:
             jpegs: a list of b >= 1 `bytes`, one JPEG file each; the image sizes may all differ.
-            size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling: as for
-                `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
+            size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
+                for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         if isinstance(jpegs, (bytes, bytearray, memoryview)):
             raise ValueError("jpegs must be a list of bytes (got one bytes object)")
         items = list(jpegs)
@@ -508,15 +540,15 @@ class Detector:
             if ent.jpeg is None:
                 ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
-        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps)
+        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps)
 
-    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps):
+    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
         one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
         b, thr = plan.b, float(score_threshold)
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan)
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
@@ -531,17 +563,20 @@ class Detector:
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
         exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
         output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
-        capacity also covers the encoder's coefficients, streams and workspace."""
+        capacity also covers the encoder's coefficients, streams and workspace. plot_maps: an entry of its own with a
+        MapPlotter for the canvas batch."""
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
         base = ('images', b, h, w, thr)
         tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
+        if plot_maps:
+            tail += ('maps',)
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -568,6 +603,8 @@ class Detector:
         if eplan:
             ent.encode = jpeg.JpegBatchEncoder(dev)
             ent.encode.reserve(b, *cap[3:])
+        if plot_maps:
+            ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
         store[key] = ent
         return ent
 
@@ -579,7 +616,7 @@ class Detector:
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode)
+        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)
@@ -587,6 +624,10 @@ class Detector:
             from ..prn_inference import KeypointAssigner
             a = self._batch_assigners[n] = KeypointAssigner(self.assigner.net.for_batch(n), self.assigner.threshold)
         return a
+
+    def _has_heatmaps(self):
+        """Whether the graph has the keypoint subnet's heatmap head (what plot_maps=True shows)."""
+        return getattr(self.net, 'heat_w', None) is not None
 
     def _variable_versions(self):
         return (self.net.var_version, self.retinanet.var_version if self.retinanet is not None else -1,

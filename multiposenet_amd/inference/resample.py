@@ -26,20 +26,42 @@ def _bicubic(x, a=-0.5):
     return 0.0
 
 
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x):
+    """Pillow's `Image.LANCZOS`: sinc(x) * sinc(x / 3), truncated to -3 <= x < 3."""
+    if -3.0 <= x < 3.0:
+        return _sinc(x) * _sinc(x / 3)
+    return 0.0
+
+
+FILTERS = {'bicubic': (_bicubic, 2.0), 'lanczos': (_lanczos, 3.0)}     # name -> (kernel, support)
+
+
 @functools.lru_cache(maxsize=512)
-def resample_tables(in_size, out_size):
+def resample_tables(in_size, out_size, filter='bicubic'):
     """The taps of one axis: `bounds` int32 [out_size, 2] = (first tap, tap count) and `coeffs` int32 [out_size, ksize].
 
     Bicubic with a = -0.5, support 2 * max(in/out, 1), ksize = ceil(support) * 2 + 1; output x has its centre at
     (x + 0.5) * in/out and taps int(centre - support + 0.5) .. int(centre + support + 0.5) clipped to [0, in_size); the weights
     are float64, normalised by their sum (added in tap order), then fixed point with 22 fractional bits rounded half away from
-    zero. Cached per (in_size, out_size): a video stream builds its tables once. The arrays are read-only."""
+    zero. filter='lanczos' (Pillow's `Image.LANCZOS`, of inference/plot_maps): the same rules with sinc(x) * sinc(x / 3) on
+    |x| < 3 and support 3 * max(in/out, 1). Cached per (in_size, out_size, filter): a video stream builds its tables once. The
+    arrays are read-only."""
     in_size, out_size = int(in_size), int(out_size)
     if in_size < 1 or out_size < 1:
         raise ValueError(f"resample_tables: sizes must be >= 1 (got {in_size} -> {out_size})")
+    if filter not in FILTERS:
+        raise ValueError(f"resample_tables: filter must be one of {sorted(FILTERS)} (got {filter!r})")
+    kernel, support = FILTERS[filter]
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
-    support = 2.0 * filterscale
+    support = support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((out_size, 2), np.int32)
     coeffs = np.zeros((out_size, ksize), np.int32)
@@ -50,7 +72,7 @@ def resample_tables(in_size, out_size):
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size)
         n = xmax - xmin
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(n)]
+        w = [kernel((x + xmin - center + 0.5) * ss) for x in range(n)]
         total = 0.0
         for v in w:
             total += v
