@@ -1031,6 +1031,93 @@ int mpn_jpeg_decode(const int16_t* coefs, size_t coef_bytes, const void* descs, 
                     size_t sources_bytes, void* work, size_t work_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * JPEG entropy decode on the device: the Huffman stage of a SUPPORTED stream (above) without the host decode. The host only
+ * parses headers (mpn_jpeg_scan_prepare); the file's own bytes are staged, and mpn_jpeg_entropy_decode_device produces the
+ * coefficients in the layout of mpn_jpeg_entropy_decode and the [B] mpn_jpeg_desc mpn_jpeg_decode reads.
+ *
+ * The scheme: an image's bytes are cut into subsequences of MPN_JPEG_SUBSEQ_BITS bits, the grid anchored at the image's
+ * first byte (file_offset), NOT at the scan. A decoder state is (bit position over the RAW bytes, block index within the
+ * MCU, zigzag index). f_i(entry) decodes whole symbols from `entry` until the position leaves subsequence i and returns the
+ * exit state, the blocks completed and the restart markers passed. It works on raw bytes: the 00 behind an FF is skipped,
+ * FF D0..D7 (behind any FF fill bytes) aligns to the byte behind the marker and resets the state to block 0, index 0, any
+ * other marker or the end of the data ends the scan; nothing at or past nbytes is read. The first entry is known
+ * (scan_offset * 8, 0, 0), every other starts as a guess (its subsequence's first bit, 0, 0); the true entries are the fixed
+ * point of entry[i + 1] = f_i(entry[i]). A workgroup owns MPN_JPEG_GROUP_SUBSEQ consecutive subsequences (32 KB) and sweeps
+ * them in LDS until nothing changes (at most that many sweeps); `max_passes` launches carry each group's exit into the next
+ * group, a pass re-solving only what its changed entry changes. Then: an exclusive prefix sum of the block counts, a write
+ * pass from the true entries (raw coefficients, de-zigzagged, DC as the difference, into the zeroed region), and a DC pass
+ * (per-component running sum in decode order, reset every restart_interval MCUs). 5 + max_passes launches (the first gives every
+ * image its own part of the workspace: a prefix sum over the descriptors); no workgroup waits on another; every loop is
+ * bounded by nbytes, B or the group size; grids depend on B alone; no host synchronisation, no
+ * allocation: capturable.
+ *
+ *   files        the staged bytes of the batch, DEVICE, 16-byte aligned; image b's file at byte file_offset (multiple of 16)
+ *   scan_descs   [B] mpn_jpeg_scan_desc, DEVICE, 16-byte aligned (mpn_jpeg_scan_prepare + the caller's four offsets)
+ *   coefs        as mpn_jpeg_decode reads them; image b's planes at byte coef_offset (zeroed by the call, then written)
+ *   jpeg_descs_out [B] mpn_jpeg_desc, DEVICE, 16-byte aligned (a skipped image's is zeroed: mpn_jpeg_decode skips it too)
+ *   records      [B] mpn_jpeg_entropy_record, DEVICE, 16-byte aligned:
+ *     MPN_JPEG_ENT_OK             the coefficients equal mpn_jpeg_entropy_decode's
+ *     MPN_JPEG_ENT_NOT_CONVERGED  max_passes did not reach the fixed point (a stream longer than max_passes groups that
+ *                                 does not self-synchronise); the coefficients are not valid
+ *     MPN_JPEG_ENT_BAD_DATA       judged from true entries only: an invalid code, a run past 63, a DC category above 11, a
+ *                                 scan that ends without a marker or before the image does, a block or restart count that
+ *                                 disagrees at a restart marker or at the end, a restart marker in a stream without an
+ *                                 interval, a Huffman table that is not a prefix code. (Stricter than the host call in one
+ *                                 place: the scan must END IN A MARKER; a file cut inside its EOI is BAD_DATA here.)
+ *     MPN_JPEG_ENT_SKIPPED        the descriptor is out of range, misaligned, or reaches outside files_bytes / coef_bytes /
+ *                                 work_bytes: nothing of the image is read or written
+ *     passes = passes that changed anything (<= max_passes), blocks = blocks the fixed point holds.
+ *   work         mpn_jpeg_entropy_decode_device_workspace_bytes(B, files_bytes) bytes (0 for arguments out of range),
+ *                16-byte aligned; nothing in it needs initialising. The call divides it among the images in descriptor
+ *                order by their nbytes: the files may lie in `files` in any order. The size covers every batch whose files
+ *                do not overlap; descriptors that name the same bytes several times may exhaust it, and the images
+ *                that no longer fit are SKIPPED - no two images ever share a part of it
+ * Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535, 1 <= max_passes <= MPN_JPEG_MAX_PASSES
+ * (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); files_bytes in [16, 2^31), coef_bytes >= 128, work_bytes >= the
+ * workspace size (MPN_ERR_WORKSPACE).
+ *
+ * mpn_jpeg_scan_prepare (HOST, no HIP call, thread-safe): the marker scan of mpn_jpeg_info into a fixed-size descriptor. It
+ * never touches the scan's bytes. MPN_OK for every stream it can classify: `supported` / `reason` as mpn_jpeg_info reports
+ * them, the other fields filled for a supported stream only; MPN_ERR_BAD_DATA for damaged headers.
+ */
+enum { MPN_JPEG_ENT_OK = 0, MPN_JPEG_ENT_NOT_CONVERGED = 1, MPN_JPEG_ENT_BAD_DATA = 2, MPN_JPEG_ENT_SKIPPED = 3 };
+#define MPN_JPEG_SUBSEQ_BITS 1024
+#define MPN_JPEG_GROUP_SUBSEQ 256
+#define MPN_JPEG_MAX_PASSES 64
+#define MPN_JPEG_MAX_FILE_BYTES (1 << 28)       /* keeps every bit position of a file in 32 bits */
+#define MPN_JPEG_SCAN_DESC_BYTES 2704
+typedef struct mpn_jpeg_scan_desc {
+    int64_t file_offset;                        /* CALLER: byte offset of the file in files, multiple of 16 */
+    int64_t coef_offset;                        /* CALLER: byte offset of its coefficients in coefs, multiple of 16 */
+    int64_t src_offset, work_offset;            /* CALLER: copied into the mpn_jpeg_desc written for mpn_jpeg_decode */
+    int64_t nbytes;                             /* size of the file */
+    int64_t scan_offset;                        /* first entropy-coded byte */
+    int32_t width, height, components, h_samp, v_samp;
+    int32_t restart_interval;                   /* in MCUs; 0 = none */
+    int32_t total_blocks;
+    int32_t blocks_w[3], blocks_h[3];
+    int32_t dc_table[3], ac_table[3];           /* per component: index into huff_bits / huff_vals */
+    int32_t supported, reason;                  /* as mpn_jpeg_header */
+    int32_t reserved[3];
+    uint16_t quant[3][64];                      /* per component, natural order */
+    uint8_t huff_bits[2][4][16];                /* [class: DC, AC][id]: codes of length 1..16 */
+    uint8_t huff_vals[2][4][256];               /* their symbols */
+} mpn_jpeg_scan_desc;
+typedef struct mpn_jpeg_entropy_record {
+    int32_t status, passes, blocks, reserved;
+} mpn_jpeg_entropy_record;
+#ifdef __cplusplus
+static_assert(sizeof(mpn_jpeg_scan_desc) == MPN_JPEG_SCAN_DESC_BYTES, "descriptor size is fixed");
+static_assert(sizeof(mpn_jpeg_entropy_record) == 16, "record size is fixed");
+#endif
+size_t mpn_jpeg_scan_desc_bytes(void);
+int mpn_jpeg_scan_prepare(const uint8_t* data /* host */, size_t nbytes, mpn_jpeg_scan_desc* out /* host */);
+size_t mpn_jpeg_entropy_decode_device_workspace_bytes(int B, long long total_file_bytes);
+int mpn_jpeg_entropy_decode_device(const uint8_t* files, size_t files_bytes, const void* scan_descs, int B, int16_t* coefs,
+                                   size_t coef_bytes, void* jpeg_descs_out, void* records, void* work, size_t work_bytes,
+                                   int max_passes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * JPEG encode, all of it on the device: baseline, three components (YCbCr), luma sampling 1x1, 2x1 or 2x2 with chroma 1x1,
  * the standard (Annex K) Huffman tables, no restart intervals. The entropy-coded scan equals, byte for byte, the one
  * libjpeg(-turbo) - and so Pillow's `save(buf, "JPEG", quality=q, subsampling=s)` - writes for the same pixels and tables;

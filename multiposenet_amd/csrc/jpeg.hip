@@ -630,6 +630,47 @@ extern "C" int mpn_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16
     return MPN_OK;
 }
 
+// The marker scan as a descriptor for the device's entropy stage (jpeg_entropy.hip): headers only, the scan's bytes untouched.
+extern "C" size_t mpn_jpeg_scan_desc_bytes(void) { return sizeof(mpn_jpeg_scan_desc); }
+
+extern "C" int mpn_jpeg_scan_prepare(const uint8_t* data, size_t nbytes, mpn_jpeg_scan_desc* out) {
+    MPN_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_scan_prepare: null pointer");
+    Parsed p;
+    int reason = parse(data, nbytes, p);
+    if (reason == MPN_JPEG_SUPPORTED && nbytes > (size_t)MPN_JPEG_MAX_FILE_BYTES) reason = MPN_JPEG_TOO_LARGE;
+    memset(out, 0, sizeof(*out));
+    out->nbytes = (int64_t)nbytes;
+    out->width = p.width;
+    out->height = p.height;
+    out->components = p.ncomp;
+    out->h_samp = p.hs[0];
+    out->v_samp = p.vs[0];
+    out->restart_interval = p.restart;
+    out->supported = reason == MPN_JPEG_SUPPORTED;
+    out->reason = reason;
+    MPN_REQUIRE(reason != MPN_JPEG_MALFORMED, MPN_ERR_BAD_DATA, "jpeg_scan_prepare: not a JPEG stream, or its headers are damaged");
+    if (reason != MPN_JPEG_SUPPORTED) return MPN_OK;
+    Geometry g;
+    geometry_of(p, g);
+    out->scan_offset = (int64_t)p.scan_pos;
+    out->total_blocks = (int32_t)g.base[3];
+    for (int c = 0; c < g.ncomp; ++c) {
+        out->blocks_w[c] = g.bw[c];
+        out->blocks_h[c] = g.bh[c];
+        out->dc_table[c] = p.td[c];
+        out->ac_table[c] = p.ta[c];
+        memcpy(out->quant[c], p.q[p.tq[c]], sizeof(out->quant[c]));
+    }
+    for (int tc = 0; tc < 2; ++tc) {
+        for (int th = 0; th < 4; ++th) {
+            if (!p.hset[tc][th]) continue;
+            memcpy(out->huff_bits[tc][th], p.hbits[tc][th] + 1, 16);
+            memcpy(out->huff_vals[tc][th], p.hvals[tc][th], 256);
+        }
+    }
+    return MPN_OK;
+}
+
 extern "C" size_t mpn_jpeg_decode_workspace_bytes(int B, long long total_blocks) {
     if (B < 1 || total_blocks < B) return 0;
     return (size_t)total_blocks * 64;

@@ -81,13 +81,18 @@ class _Slot:
 
 class KeypointPipeline:
     def __init__(self, filenames, is_training, params, device=None, buffers=None, num_threads=NUM_PARALLEL_CALLS,
-                 depth=2, decode='host'):
+                 depth=2, decode='host', entropy='host'):
         """filenames: paths of TFRecord files, or a sequence of decoded examples. params: 'batch_size', 'image_size'
         (width, height) for training, 'min_dimension' for evaluation; optional 'seed' (default 0) and
         'shuffle_buffer_size' (default SHUFFLE_BUFFER_SIZE). Under WORLD_SIZE > 1 rank r reads shards i with
         i % world == r (records i % world == r when there are fewer shards than ranks). decode: 'host' (PIL on the
-        thread pool) or 'device' (Huffman decode on the pool, inverse DCT and colour on the device)."""
+        thread pool) or 'device' (Huffman decode on the pool, inverse DCT and colour on the device). entropy (with
+        decode='device'): 'host', or 'device' - the pool only parses headers, the file's bytes are copied and the Huffman decode
+        runs on the device too (mpn_jpeg_entropy_decode_device; an image it cannot settle falls back to the host decode)."""
         self.decode = check_decode_mode(decode)
+        self.entropy = jpeg.check_entropy_mode(entropy)
+        if self.entropy == 'device' and self.decode != 'device':
+            raise ValueError("entropy='device' needs decode='device'")
         self.is_training = bool(is_training)
         if self.is_training:
             self.batch_size = int(params["batch_size"])
@@ -165,17 +170,17 @@ class KeypointPipeline:
             yield rec
 
     @staticmethod
-    def _decode(rec, device=False):
-        """device: a JPEG stays coefficients (jpeg.Coefficients, which has the image's .shape) when the device path
-        supports its stream."""
+    def _decode(rec, device=False, entropy='host'):
+        """device: a JPEG stays coefficients (jpeg.Coefficients, which has the image's .shape; a jpeg.Scan with
+        entropy='device') when the device path supports its stream."""
         if isinstance(rec, (bytes, bytearray, memoryview)):
             ex = decode_keypoint_example(rec, decode_image=not device)
         else:
             ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = jpeg.prepare(img) if device else decode_jpeg(img)
-        if not isinstance(img, jpeg.Coefficients):
+            img = jpeg.prepare(img, entropy) if device else decode_jpeg(img)
+        if not isinstance(img, (jpeg.Coefficients, jpeg.Scan)):
             img = np.ascontiguousarray(img, dtype=np.uint8)
             if img.ndim != 3 or img.shape[2] != 3:
                 raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
@@ -316,7 +321,7 @@ class KeypointPipeline:
                 for rec in records:
                     raw.append(rec)
                     if len(raw) == self.batch_size:
-                        return [pool.submit(self._decode, r, self.decode == 'device') for r in raw]
+                        return [pool.submit(self._decode, r, self.decode == 'device', self.entropy) for r in raw]
                 return None
             pending = next_batch()
             while pending is not None:

@@ -56,12 +56,12 @@ def decode_detector_example(data, decode_image=True):
 
 class DetectorPipeline(KeypointPipeline):
     def __init__(self, filenames, is_training, params, device=None, buffers=None, num_threads=NUM_PARALLEL_CALLS, seed=0,
-                 depth=2, decode='host'):
+                 depth=2, decode='host', entropy='host'):
         """filenames: paths of TFRecord files, or a sequence of decoded examples. params: 'batch_size', 'image_size'
         (width, height) for training, 'min_dimension' for evaluation; optional 'seed' (overrides `seed`) and
-        'shuffle_buffer_size'. decode: 'host' or 'device', as for `KeypointPipeline`."""
+        'shuffle_buffer_size'. decode: 'host' or 'device', entropy: 'host' or 'device', as for `KeypointPipeline`."""
         super().__init__(filenames, is_training, params, device=device, buffers=buffers, num_threads=num_threads,
-                         depth=depth, decode=decode)
+                         depth=depth, decode=decode, entropy=entropy)
         self.seed = int(params.get("seed", seed))
         self._num_examples = None
 
@@ -74,15 +74,15 @@ class DetectorPipeline(KeypointPipeline):
         return self._num_examples
 
     @staticmethod
-    def _decode(rec, device=False):
+    def _decode(rec, device=False, entropy='host'):
         if isinstance(rec, (bytes, bytearray, memoryview)):
             ex = decode_detector_example(rec, decode_image=not device)
         else:
             ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = jpeg.prepare(img) if device else decode_jpeg(img)
-        if not isinstance(img, jpeg.Coefficients):
+            img = jpeg.prepare(img, entropy) if device else decode_jpeg(img)
+        if not isinstance(img, (jpeg.Coefficients, jpeg.Scan)):
             img = np.ascontiguousarray(img, dtype=np.uint8)
             if img.ndim != 3 or img.shape[2] != 3:
                 raise ValueError(f"image must be uint8 [H,W,3], got {img.shape}")
@@ -192,7 +192,7 @@ class DetectorPipeline(KeypointPipeline):
                 for rec in records:
                     raw.append(rec)
                     if len(raw) == self.batch_size:
-                        return [pool.submit(self._decode, r, self.decode == 'device') for r in raw]
+                        return [pool.submit(self._decode, r, self.decode == 'device', self.entropy) for r in raw]
                 return None
             pending = next_batch()
             while pending is not None:

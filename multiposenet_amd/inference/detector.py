@@ -505,15 +505,19 @@ class Detector:
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False):
+                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host'):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
         `predict_images([pillow_decode(j) for j in jpegs], ...)`. A stream outside the supported set (progressive, CMYK, ...)
-        is decoded by Pillow and uploaded as pixels, inside the same batch.
+        is decoded by Pillow and uploaded as pixels, inside the same batch. With entropy='device' the host only parses
+        headers: the files' own bytes are uploaded (about a tenth of the coefficients) and the Huffman decode runs on the device
+        too (mpn_jpeg_entropy_decode_device); an image it cannot settle takes the host decode. The same results either way.
 
         Arguments:
             jpegs: a list of b >= 1 `bytes`, one JPEG file each; the image sizes may all differ.
+            entropy: 'host' (default) or 'device'. `self.jpeg_staged_bytes` / `self.jpeg_fallbacks`: what the call uploaded for
+                the decode, and how many images took the fallback.
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
@@ -531,7 +535,7 @@ class Detector:
         infos = [jpeg.jpeg_info(j) for j in items]
         height, width = resample.check_size(size)
         plan = resample.Plan([(i['height'], i['width']) for i in infos], height, width, keep_aspect_ratio, align=16)
-        entries = [jpeg.prepare(j) for j in items]
+        entries = [jpeg.prepare(j, entropy) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
                 raise ValueError(f"a JPEG decodes to {tuple(e.shape)}, its header says {(h, w, 3)}")
@@ -540,6 +544,7 @@ class Detector:
             if ent.jpeg is None:
                 ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
+            self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
         return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps)
 
     def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False):

@@ -35,6 +35,29 @@ DESC = np.dtype([('src_offset', np.int64), ('coef_offset', np.int64), ('work_off
 assert DESC.itemsize == DESC_BYTES
 
 
+# mpn_jpeg_scan_desc: what the device's entropy stage reads (its four offsets are the caller's)
+SCAN_DESC_BYTES = 2704                  # MPN_JPEG_SCAN_DESC_BYTES (checked against the library)
+ENTROPY_RECORD_BYTES = 16
+ENT_OK, ENT_NOT_CONVERGED, ENT_BAD_DATA, ENT_SKIPPED = 0, 1, 2, 3
+ENTROPY_MODES = ('host', 'device')
+MAX_PASSES = 4                          # launches that carry a 32 KB group's exit into the next group (mpn.h)
+SCAN_DESC = np.dtype([('file_offset', np.int64), ('coef_offset', np.int64), ('src_offset', np.int64), ('work_offset', np.int64),
+                      ('nbytes', np.int64), ('scan_offset', np.int64),
+                      ('width', np.int32), ('height', np.int32), ('components', np.int32), ('h_samp', np.int32), ('v_samp', np.int32),
+                      ('restart_interval', np.int32), ('total_blocks', np.int32), ('blocks_w', np.int32, (3,)),
+                      ('blocks_h', np.int32, (3,)), ('dc_table', np.int32, (3,)), ('ac_table', np.int32, (3,)),
+                      ('supported', np.int32), ('reason', np.int32), ('reserved', np.int32, (3,)),
+                      ('quant', np.uint16, (3, 64)), ('huff_bits', np.uint8, (2, 4, 16)), ('huff_vals', np.uint8, (2, 4, 256))])
+ENTROPY_RECORD = np.dtype([('status', np.int32), ('passes', np.int32), ('blocks', np.int32), ('reserved', np.int32)])
+assert SCAN_DESC.itemsize == SCAN_DESC_BYTES and ENTROPY_RECORD.itemsize == ENTROPY_RECORD_BYTES
+
+
+def check_entropy_mode(entropy):
+    if entropy not in ENTROPY_MODES:
+        raise ValueError(f"entropy must be one of {ENTROPY_MODES} (got {entropy!r})")
+    return entropy
+
+
 def _as_bytes(data):
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise ValueError("a JPEG must be bytes")
@@ -88,18 +111,51 @@ def entropy_decode(data):
     return Coefficients((h.height, h.width, 3), coefs, desc)
 
 
+class Scan:
+    """A SUPPORTED JPEG whose Huffman stage is left to the device: `.data` (the file's bytes), `.shape` (h, w, 3) and `.desc`,
+    a one-element SCAN_DESC record (headers only; the scan's bytes were not touched)."""
+    __slots__ = ('data', 'shape', 'desc')
+
+    def __init__(self, data, shape, desc):
+        self.data, self.shape, self.desc = data, shape, desc
+
+    @property
+    def total_blocks(self):
+        return int(self.desc[0]['total_blocks'])
+
+
+def scan_prepare(data):
+    """The header stage on one SUPPORTED JPEG -> Scan. Raises ValueError for a stream whose headers are damaged or that is
+    outside the supported set."""
+    data = _as_bytes(data)
+    desc = np.zeros(1, SCAN_DESC)
+    _lib.check(_lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p)))
+    d = desc[0]
+    if not d['supported']:
+        raise ValueError(f"scan_prepare: stream not supported ({REASONS[int(d['reason'])]})")
+    return Scan(data, (int(d['height']), int(d['width']), 3), desc)
+
+
 def pillow_decode(data):
     """What the device path must equal, and the per-image fallback: Pillow's decode to uint8 [h, w, 3]."""
     from PIL import Image
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
 
 
-def prepare(item):
-    """One entry of a batch, ready for `JpegBatchDecoder`: JPEG bytes -> Coefficients when the stream is supported, else the
-    pixels Pillow decodes; a uint8 [h, w, 3] array or a Coefficients passes through. Thread-safe (the pipelines' decode pool)."""
-    if isinstance(item, (Coefficients, np.ndarray)):
+def prepare(item, entropy='host'):
+    """One entry of a batch, ready for `JpegBatchDecoder`: JPEG bytes -> Coefficients when the stream is supported (a Scan
+    with entropy='device': headers only, the Huffman stage runs on the device), else the pixels Pillow decodes; a uint8
+    [h, w, 3] array, a Coefficients or a Scan passes through. Thread-safe (the pipelines' decode pool)."""
+    check_entropy_mode(entropy)
+    if isinstance(item, (Coefficients, Scan, np.ndarray)):
         return item
     data = _as_bytes(item)
+    if entropy == 'device':
+        desc = np.zeros(1, SCAN_DESC)
+        rc = _lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p))
+        if rc == 0 and desc[0]['supported']:
+            return Scan(data, (int(desc[0]['height']), int(desc[0]['width']), 3), desc)
+        return pillow_decode(data)
     h = _Header()
     rc = _lib.lib().mpn_jpeg_info(data, len(data), ctypes.byref(h))
     if rc == 0 and h.supported:
@@ -117,17 +173,27 @@ class JpegBatchDecoder:
         decoder = JpegBatchDecoder(device)
         decoder.decode(entries, sources, offsets, stream)
 
-    entries: Coefficients (decoded on the device by mpn_jpeg_decode) or uint8 [h, w, 3] arrays (copied as pixels: streams
-    the device path does not support, records that are not JPEGs). sources: a uint8 device tensor; image i lands at byte
+    entries: Coefficients (decoded on the device by mpn_jpeg_decode), Scan (Huffman-decoded on the device first, by
+    mpn_jpeg_entropy_decode_device: the file's bytes and a header descriptor are staged instead of coefficients; the [B]
+    records come back with one small copy and one event wait, and every image that is not OK takes the host `entropy_decode` -
+    which raises ValueError for a damaged stream - and a second mpn_jpeg_decode; `.fallbacks` counts them) or uint8 [h, w, 3]
+    arrays (copied as pixels: streams the device path does not support, records that are not JPEGs). `.staged_bytes`: what
+    the last `decode` uploaded. sources: a uint8 device tensor; image i lands at byte
     offsets[i], a multiple of 16. Coefficients, descriptors and fallback pixels go through ONE pinned staging buffer and ONE
     host-to-device copy on `stream`; staging and device buffers grow to the largest batch seen. A decoder is bound to one
     consumer: the next `decode` waits for the previous one's copy before it reuses the staging."""
 
-    def __init__(self, device):
+    def __init__(self, device, max_passes=MAX_PASSES):
         self.device = resolve_device(device)
-        if _lib.lib().mpn_jpeg_desc_bytes() != DESC_BYTES:
+        if _lib.lib().mpn_jpeg_desc_bytes() != DESC_BYTES or _lib.lib().mpn_jpeg_scan_desc_bytes() != SCAN_DESC_BYTES:
             raise _lib.MpnError("mpn_jpeg_decode: the descriptor's layout is not the one this binding was written against")
+        self.max_passes = int(max_passes)
+        self.fallbacks = 0                  # Scan entries of the last `decode` that took the host entropy stage
+        self.staged_bytes = 0               # bytes the last `decode` uploaded
+        self.records = None                 # ENTROPY_RECORD per Scan entry of the last `decode`
         self._stage = self._dev = self._work = None
+        self._scan = {}                     # buffers of the device entropy stage, by name
+        self.scan_layout = None
         self._done = None
 
     def _ensure(self, stage_bytes, work_bytes):
@@ -172,6 +238,101 @@ class JpegBatchDecoder:
         return jp, px, {'coef_base': coef_base, 'coef_bytes': coef_bytes, 'coef_at': coef_at, 'work_at': work_at,
                         'work_bytes': work, 'pix_at': pix_at, 'stage_bytes': at}
 
+    def _buffer(self, name, nbytes, pinned=False):
+        """A uint8 buffer of at least nbytes that grows to the largest batch seen."""
+        import torch
+        have = self._scan.get(name)
+        if have is None or have.numel() < nbytes:
+            if have is not None:
+                torch.cuda.synchronize(self.device)             # (rare) growth: no queued copy or launch still uses the old buffer
+            n = _capacity(nbytes)
+            have = torch.empty(n, dtype=torch.uint8).pin_memory() if pinned else torch.empty(n, dtype=torch.uint8, device=self.device)
+            self._scan[name] = have
+        return have
+
+    @staticmethod
+    def plan_scans(scans, offsets, file_order=None):
+        """Host arithmetic of the Scan entries of a batch: the staging holds their descriptors, then their files, each at a
+        multiple of 16; coefficients and inverse-DCT planes follow each other on the device. file_order: the order in which
+        the files lie in the staging (a permutation of the entries' indices; default: the entries' own order) - the device
+        call does not care."""
+        order = list(range(len(scans))) if file_order is None else [int(k) for k in file_order]
+        if sorted(order) != list(range(len(scans))):
+            raise ValueError("file_order must be a permutation of the entries' indices")
+        at = len(scans) * SCAN_DESC_BYTES
+        file_base = at
+        file_at = [0] * len(scans)
+        for k in order:
+            file_at[k] = at - file_base
+            at += _round16(len(scans[k].data))
+        coef_at, work_at, coef, work = [], [], 0, 0
+        for e, off in zip(scans, offsets):
+            if off % 16:
+                raise ValueError(f"the offset of a device-decoded image must be a multiple of 16 (got {off})")
+            coef_at.append(coef)
+            work_at.append(work)
+            coef += e.total_blocks * 128
+            work += e.total_blocks * 64
+        return {'file_base': file_base, 'files_bytes': at - file_base, 'file_at': file_at, 'coef_at': coef_at, 'work_at': work_at,
+                'coef_bytes': coef, 'work_bytes': work, 'stage_bytes': at}
+
+    def entropy_launch(self, stream=None):
+        """mpn_jpeg_entropy_decode_device over the Scan entries `decode_scans` staged last, on `stream` (default: the current
+        one). No host synchronisation: what `decode_scans` queues, and what a benchmark times."""
+        lay, buf = self.scan_layout, self._scan
+        base = buf['dev'].data_ptr()
+        st = _lib.stream_ptr() if stream is None else ctypes.c_void_p(stream.cuda_stream)
+        _lib.call("mpn_jpeg_entropy_decode_device", ctypes.c_void_p(base + lay['file_base']), lay['files_bytes'], ctypes.c_void_p(base),
+                  len(lay['file_at']), _lib.ptr(buf['coefs']), buf['coefs'].numel(), _lib.ptr(buf['descs']), _lib.ptr(buf['records']),
+                  _lib.ptr(buf['work']), buf['work'].numel(), self.max_passes, st)
+
+    def decode_scans(self, scans, sources, offsets, stream, file_order=None):
+        """Entropy stage and inverse DCT of the Scan entries on the device, then the wait for their records (`.records`);
+        returns the indices (into `scans`) of the images whose record is not OK. `decode` calls this and handles them.
+        mpn_jpeg_decode runs over every image of the batch, so until the fallback has run (or when it raises) the pixels
+        of an image that is not OK are undefined inside its own [offset, offset + h * w * 3) of `sources`."""
+        import torch
+        lay = self.scan_layout = self.plan_scans(scans, offsets, file_order)
+        b, n = len(scans), lay['stage_bytes']
+        lib = _lib.lib()
+        ent_work = lib.mpn_jpeg_entropy_decode_device_workspace_bytes(b, lay['files_bytes'])
+        if ent_work == 0:
+            raise ValueError(f"decode: a batch of {b} files in {lay['files_bytes']} bytes is outside what mpn_jpeg_entropy_decode_device takes")
+        stage, dev = self._buffer('stage', n, pinned=True), self._buffer('dev', n)
+        coefs, planes = self._buffer('coefs', lay['coef_bytes']), self._buffer('planes', max(lay['work_bytes'], 64))
+        descs_out, records = self._buffer('descs', b * DESC_BYTES), self._buffer('records', b * ENTROPY_RECORD_BYTES)
+        record_host, work = self._buffer('record_host', b * ENTROPY_RECORD_BYTES, pinned=True), self._buffer('work', ent_work)
+        host = stage.numpy()
+        descs = host[:b * SCAN_DESC_BYTES].view(SCAN_DESC)
+        for k, (e, off) in enumerate(zip(scans, offsets)):
+            descs[k] = e.desc[0]
+            d = descs[k]
+            d['file_offset'], d['coef_offset'], d['src_offset'], d['work_offset'] = lay['file_at'][k], lay['coef_at'][k], off, lay['work_at'][k]
+            at = lay['file_base'] + lay['file_at'][k]
+            host[at:at + len(e.data)] = np.frombuffer(e.data, np.uint8)
+        with torch.cuda.stream(stream):
+            dev[:n].copy_(stage[:n], non_blocking=True)
+            st = ctypes.c_void_p(stream.cuda_stream)
+            self.entropy_launch(stream)
+            _lib.call("mpn_jpeg_decode", _lib.ptr(coefs), coefs.numel(), _lib.ptr(descs_out), b, _lib.ptr(sources), sources.numel(),
+                      _lib.ptr(planes), planes.numel(), st)
+            record_host[:b * ENTROPY_RECORD_BYTES].copy_(records[:b * ENTROPY_RECORD_BYTES], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        done.synchronize()
+        self.records = record_host.numpy()[:b * ENTROPY_RECORD_BYTES].view(ENTROPY_RECORD).copy()
+        self.staged_bytes += n
+        skipped = [k for k in range(b) if self.records[k]['status'] == ENT_SKIPPED]
+        if skipped:
+            raise _lib.MpnError(f"mpn_jpeg_entropy_decode_device skipped image {skipped[0]}: its descriptor is out of range")
+        return [k for k in range(b) if self.records[k]['status'] != ENT_OK]
+
+    def scan_coefficients(self, k):
+        """The device's coefficients of Scan entry k of the last batch, int16 [total_blocks, 64] on the host (tests, tools)."""
+        lay = self.scan_layout
+        end = lay['coef_at'][k + 1] if k + 1 < len(lay['coef_at']) else lay['coef_bytes']
+        return self._scan['coefs'][lay['coef_at'][k]:end].cpu().numpy().view(np.int16).reshape(-1, 64)
+
     def decode(self, entries, sources, offsets, stream=None):
         import torch
         if len(entries) != len(offsets) or not len(entries):
@@ -183,6 +344,20 @@ class JpegBatchDecoder:
             shape = e.shape
             if off < 0 or off + shape[0] * shape[1] * 3 > total:
                 raise ValueError(f"decode: an image of {shape} at byte {off} does not fit a buffer of {total} bytes")
+        self.fallbacks = self.staged_bytes = 0
+        self.records = None
+        sc = [i for i, e in enumerate(entries) if isinstance(e, Scan)]
+        if sc:
+            stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+            if self._done is not None:
+                self._done.synchronize()                        # the previous batch's copy has left the staging
+            bad = self.decode_scans([entries[i] for i in sc], sources, [offsets[i] for i in sc], stream)
+            self.fallbacks = len(bad)
+            redo = {sc[k]: entropy_decode(entries[sc[k]].data) for k in bad}     # (raises ValueError for a damaged stream)
+            keep = [i for i, e in enumerate(entries) if not isinstance(e, Scan) or i in redo]
+            if not keep:
+                return
+            entries, offsets = [redo.get(i, entries[i]) for i in keep], [offsets[i] for i in keep]
         jp, px, lay = self.plan(entries, offsets)
         if self._done is not None:
             self._done.synchronize()                            # the previous batch's copy has left the staging
@@ -201,6 +376,7 @@ class JpegBatchDecoder:
             stage[lay['pix_at'][k]:lay['pix_at'][k] + e.size] = e.reshape(-1)
         stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         n = lay['stage_bytes']
+        self.staged_bytes += n
         with torch.cuda.stream(stream):
             self._dev[:n].copy_(self._stage[:n], non_blocking=True)
             if jp:

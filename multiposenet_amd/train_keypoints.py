@@ -173,6 +173,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--decode", default="host", choices=["host", "device"],
                     help="where the pixel half of the JPEG decode runs (device: Huffman on the host, inverse DCT and colour in HIP)")
+    ap.add_argument("--entropy", default="host", choices=["host", "device"],
+                    help="with --decode device: where the Huffman decode runs (device: only the file's bytes cross the link)")
     args = ap.parse_args()
     params = dict(PARAMS, dtype=args.dtype)
     if args.model_dir:
@@ -199,8 +201,8 @@ def main():
         train(params, lambda: synthetic_batches(params["batch_size"], h, w), max_steps=args.steps)
     else:
         from .detector.input_pipeline import KeypointPipeline
-        val = (lambda: KeypointPipeline(val_files, False, params, decode=args.decode).batches()) if val_files else None
-        step = train(params, lambda: KeypointPipeline(train_files, True, params, decode=args.decode).batches(), val_batches=val,
+        val = (lambda: KeypointPipeline(val_files, False, params, decode=args.decode, entropy=args.entropy).batches()) if val_files else None
+        step = train(params, lambda: KeypointPipeline(train_files, True, params, decode=args.decode, entropy=args.entropy).batches(), val_batches=val,
                      max_steps=args.steps)
         if val is not None:
             evaluate(params, val, step=step)

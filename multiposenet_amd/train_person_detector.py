@@ -180,6 +180,8 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--decode", default="host", choices=["host", "device"],
                     help="where the pixel half of the JPEG decode runs (device: Huffman on the host, inverse DCT and colour in HIP)")
+    ap.add_argument("--entropy", default="host", choices=["host", "device"],
+                    help="with --decode device: where the Huffman decode runs (device: only the file's bytes cross the link)")
     ap.add_argument("--eval-every", type=float, default=None, help="seconds between evaluations (default: 7200)")
     args = ap.parse_args(argv)
     params = dict(PARAMS, dtype=args.dtype)
@@ -196,8 +198,8 @@ def main(argv=None):
     run_config = {}
     if args.eval_every is not None:
         run_config = {"eval_start_delay_secs": args.eval_every, "eval_throttle_secs": args.eval_every}
-    val = (lambda: DetectorPipeline(val_files, False, params, decode=args.decode).batches()) if val_files else None
-    step = train(params, lambda: DetectorPipeline(train_files, True, params, decode=args.decode).batches(), val_batches=val,
+    val = (lambda: DetectorPipeline(val_files, False, params, decode=args.decode, entropy=args.entropy).batches()) if val_files else None
+    step = train(params, lambda: DetectorPipeline(train_files, True, params, decode=args.decode, entropy=args.entropy).batches(), val_batches=val,
                  run_config=run_config, max_steps=args.steps)
     if val is not None:
         evaluate(params, val, step=step)
