@@ -952,6 +952,8 @@ int mpn_plot_maps(const uint8_t* frames, const float* heatmaps, const float* mas
  * Everything else is CLASSIFIED (supported = 0 and a reason) and left to a library: progressive, arithmetic, lossless /
  * hierarchical frames, 12-bit precision, 2 or 4 components (CMYK / YCCK), an Adobe marker with a transform other than 1
  * or 'R','G','B' component ids, other sampling (4:4:0, 4:1:1, ...), several scans, 16-bit quantisation tables.
+ * (Progressive files and Adobe CMYK have a host stage of their own, mpn_jpeg_scans_decode below; these three calls still
+ * classify them as unsupported.)
  *
  * HOST (no HIP call, no global state: thread-safe and re-entrant; nothing is read past nbytes or written past coef_bytes):
  *   mpn_jpeg_info            scans the markers up to the first scan. MPN_OK for every stream it can classify (supported or
@@ -979,7 +981,7 @@ int mpn_plot_maps(const uint8_t* frames, const float* heatmaps, const float* mas
  *   work         mpn_jpeg_decode_workspace_bytes(B, sum of total_blocks) bytes (64 per block; 0 for arguments out of range),
  *                16-byte aligned; image b's planes at byte work_offset
  * src_offset, coef_offset and work_offset are multiples of 16. The kernels recompute an image's geometry from (width,
- * height, components, h_samp, v_samp) and skip an image whose descriptor is out of range, misaligned, or reaches outside
+ * height, components, h_samp, v_samp; components == 4: see "multi-scan and four-component files" below) and skip an image whose descriptor is out of range, misaligned, or reaches outside
  * coef_bytes / work_bytes / sources_bytes: no descriptor makes them read or write outside the four buffers.
  * Grid and block sizes depend on B alone. Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535
  * (MPN_ERR_BAD_SHAPE); alignment (MPN_ERR_BAD_ALIGN); coef_bytes >= 128, work_bytes >= 64, sources_bytes >= 3
@@ -1016,7 +1018,9 @@ typedef struct mpn_jpeg_desc {
     int32_t width, height, components, h_samp, v_samp;
     int32_t total_blocks;
     int32_t blocks_w[3], blocks_h[3];
-    int32_t reserved[14];
+    int32_t blocks_w3, blocks_h3;               /* components == 4: the fourth component's grid (else 0) */
+    int32_t quant3;                             /* components == 4: which of quant[0..2] the fourth component uses */
+    int32_t reserved[11];
     uint16_t quant[3][64];                      /* per component, natural order (the 8-bit tables widened) */
 } mpn_jpeg_desc;
 #ifdef __cplusplus
@@ -1029,6 +1033,54 @@ int mpn_jpeg_entropy_decode(const uint8_t* data /* host */, size_t nbytes, int16
 size_t mpn_jpeg_decode_workspace_bytes(int B, long long total_blocks);
 int mpn_jpeg_decode(const int16_t* coefs, size_t coef_bytes, const void* descs, int B, uint8_t* sources_out,
                     size_t sources_bytes, void* work, size_t work_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * JPEG decode of multi-scan and four-component files: a second HOST stage beside mpn_jpeg_entropy_decode, and a fourth
+ * plane in mpn_jpeg_decode. mpn_jpeg_info / mpn_jpeg_entropy_decode / mpn_jpeg_scan_prepare are unchanged: they still
+ * classify these files as MPN_JPEG_PROGRESSIVE / MPN_JPEG_COMPONENTS.
+ *
+ * What it adds: 8-bit Huffman PROGRESSIVE files (SOF2) of one component, of three in YCbCr (the samplings above) or of four;
+ * and BASELINE files of four. Four components means: every component sampled 1x1 and an Adobe APP14 marker with transform 0
+ * (CMYK stored inverted: what Pillow writes for a "CMYK" image), the fourth component's quantisation table equal to one of
+ * the first three's. YCCK (transform 2), four components without the Adobe marker, sampled CMYK, 4:4:0, arithmetic coding,
+ * 12-bit precision, 16-bit quantisation tables and sequential files of several scans stay with a library (route LIBRARY).
+ *
+ * HOST (no HIP call, no global state, no allocation: thread-safe and re-entrant; nothing is read past nbytes or written
+ * past coef_bytes, whatever the bytes are):
+ *   mpn_jpeg_scans_info    the marker scan up to the first scan: geometry of up to four components, `route` - DEVICE (a
+ *                          stream mpn_jpeg_info supports: its Huffman stage may run on the device), HOST_ENTROPY (a stream
+ *                          only mpn_jpeg_scans_decode reads) or LIBRARY - and `reason` (MPN_JPEG_*; SUPPORTED unless the
+ *                          route is LIBRARY). MPN_ERR_BAD_DATA when the headers are damaged.
+ *   mpn_jpeg_scans_decode  decodes EVERY scan of a DEVICE or HOST_ENTROPY stream into the layout of
+ *                          mpn_jpeg_entropy_decode: DC first / DC refinement scans (interleaved or one component), AC first
+ *                          scans with end-of-band runs, AC refinement scans with their correction bits, any spectral band,
+ *                          DHT / DQT / DRI redefined between scans (a component's quantisation table is the one in force
+ *                          at its first scan), restart intervals; a scan of ONE component walks that component's own
+ *                          ceil(w / 8) x ceil(h / 8) blocks, not the padded grid. Fills `desc` except its three offsets.
+ *                          MPN_ERR_WORKSPACE when coef_bytes < total_blocks * 128; MPN_ERR_BAD_DATA for a LIBRARY stream, a
+ *                          truncated file, an invalid code, a band past 63, a bit position above 13, a scan that does not
+ *                          continue what the scans before it left (a refinement of a band never started, a band coded
+ *                          twice), a file that ends before every coefficient has all its bits, more than 100 scans.
+ *
+ * DEVICE: a descriptor with components == 4 (h_samp = v_samp = 1; blocks_w3, blocks_h3, quant3 set) makes mpn_jpeg_decode
+ * run the same inverse DCT over four planes and, in place of YCbCr -> RGB, what Pillow does with such a file: the four
+ * samples s0..s3 pass through the library unchanged, Pillow inverts them on load (C = 255 - s0, ..., K = 255 - s3) and
+ * `convert("RGB")` computes R = nk - MULDIV255(C, nk) with nk = 255 - K, MULDIV255(a, b) = (t + (t >> 8)) >> 8 for
+ * t = a * b + 128 (likewise G from M, B from Y). Three bytes per pixel at src_offset, as for the other streams.
+ */
+enum { MPN_JPEG_ROUTE_DEVICE = 0, MPN_JPEG_ROUTE_HOST_ENTROPY = 1, MPN_JPEG_ROUTE_LIBRARY = 2 };
+typedef struct mpn_jpeg_scans_header {          /* what mpn_jpeg_scans_info reports (host) */
+    int32_t width, height, components;
+    int32_t h_samp, v_samp;                     /* sampling of the first component (1, 1 for grayscale) */
+    int32_t progressive;                        /* 1: SOF2 */
+    int32_t route, reason;                      /* MPN_JPEG_ROUTE_*, MPN_JPEG_* */
+    int32_t blocks_w[4], blocks_h[4];           /* padded block grid of each component (route DEVICE / HOST_ENTROPY only) */
+    int32_t total_blocks, reserved;
+    int64_t coef_bytes;                         /* total_blocks * 128 */
+} mpn_jpeg_scans_header;
+int mpn_jpeg_scans_info(const uint8_t* data /* host */, size_t nbytes, mpn_jpeg_scans_header* out /* host */);
+int mpn_jpeg_scans_decode(const uint8_t* data /* host */, size_t nbytes, int16_t* coefs /* host */, size_t coef_bytes,
+                          mpn_jpeg_desc* desc /* host */);
 
 /* ------------------------------------------------------------------------------------
  * JPEG entropy decode on the device: the Huffman stage of a SUPPORTED stream (above) without the host decode. The host only

@@ -157,6 +157,8 @@ SIGNATURES = {
     "mpn_jpeg_entropy_decode": (_I, [_P, _Z, _P, _Z, _P]),
     "mpn_jpeg_decode_workspace_bytes": (_Z, [_I, _L]),
     "mpn_jpeg_decode": (_I, [_P, _Z, _P, _I, _P, _Z, _P, _Z, _P]),
+    "mpn_jpeg_scans_info": (_I, [_P, _Z, _P]),
+    "mpn_jpeg_scans_decode": (_I, [_P, _Z, _P, _Z, _P]),
     "mpn_jpeg_scan_desc_bytes": (_Z, []),
     "mpn_jpeg_scan_prepare": (_I, [_P, _Z, _P]),
     "mpn_jpeg_entropy_decode_device_workspace_bytes": (_Z, [_I, _L]),

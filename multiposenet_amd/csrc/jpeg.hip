@@ -4,9 +4,12 @@
 //   HOST   mpn_jpeg_info            marker scan: geometry, sampling, restart interval, supported / reason
 //          mpn_jpeg_entropy_decode  Huffman decode of the one interleaved scan -> raw int16 coefficients, 64 per 8x8 block in
 //                                   natural order, one plane of blocks per component + a fixed-size descriptor
-//          (no HIP call, no globals: thread-safe and re-entrant; every read is checked against `nbytes`)
+//          (no HIP call, no globals: thread-safe and re-entrant; every read is checked against `nbytes`; Huffman tables
+//          and the bit reader live in jpeg_host.h, shared with the multi-scan stage of jpeg_scans.hip)
 //   DEVICE mpn_jpeg_decode          jpeg_idct_kernel    dequantise + 8x8 inverse DCT -> uint8 component planes in `work`
 //                                   jpeg_colour_kernel  "fancy" chroma upsampling + YCbCr->RGB -> packed HWC uint8 at src_offset
+//                                   (four components - Adobe CMYK, coefficients from jpeg_scans.hip - : four planes, and
+//                                   Pillow's inversion and CMYK->RGB in place of YCbCr->RGB)
 //
 // The arithmetic is libjpeg's, all integer:
 //   - inverse DCT: the "slow integer" method (13-bit constants, 2 extra bits after pass 1, COLUMNS first, then rows),
@@ -15,6 +18,7 @@
 //     the component's TRUE down-sampled size; a component of width <= 2 is replicated (the library's own rule);
 //   - colour: the 16-bit fixed-point YCbCr->RGB tables with their rounding terms.
 #include "common.h"
+#include "jpeg_host.h"
 #include <string.h>
 
 namespace {
@@ -24,10 +28,7 @@ static_assert(sizeof(Desc) == MPN_JPEG_DESC_BYTES, "descriptor layout is part of
 
 constexpr long long kMaxPixels = 1ll << 28;    // keeps every index of an image in 32 bits
 
-// zigzag position -> natural (row-major) position
-const uint8_t kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using namespace mpn_jpeg_host;
 
 // ------------------------------------------------------------------------------------------------ host: markers
 struct Parsed {
@@ -207,134 +208,10 @@ void fill_info(const Parsed& p, int reason, mpn_jpeg_header* out) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ host: Huffman
-constexpr int kLook = 9;
-
-struct HuffTable {
-    uint16_t look[1 << kLook];      // (code length << 8) | symbol of the code that starts these 9 bits; 0 = longer than 9
-    int32_t maxcode[18];            // largest code of each length (-1: none)
-    int32_t valoff[17];             // index of a length's first symbol minus its first code
-    uint8_t vals[256];
-};
-
-bool build_table(const uint8_t* bits, const uint8_t* vals, HuffTable& t) {
-    memset(t.look, 0, sizeof(t.look));
-    memcpy(t.vals, vals, 256);
-    int32_t code = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        t.valoff[l] = k - code;
-        for (int i = 0; i < bits[l]; ++i, ++k, ++code) {
-            if (l <= kLook) {
-                const int first = code << (kLook - l), count = 1 << (kLook - l);
-                if (first + count > (1 << kLook)) return false;
-                for (int j = 0; j < count; ++j) t.look[first + j] = (uint16_t)((l << 8) | vals[k]);
-            }
-        }
-        if (code > (1 << l)) return false;          // more codes than the length has
-        t.maxcode[l] = bits[l] ? code - 1 : -1;
-        code <<= 1;
-    }
-    t.maxcode[17] = 0x7fffffff;
-    return true;
-}
-
-// The entropy-coded segment as a bit stream: a 64-bit buffer holding `n` unread bits in its low end. Byte stuffing (FF 00) is
-// removed on the way in; a marker or the end of the data stops the input and zero bits follow, counted in `fake`.
-struct Bits {
-    const uint8_t* p;
-    const uint8_t* end;
-    uint64_t buf;
-    int n, fake;
-    bool stopped;
-
-    inline void refill() {
-        while (n <= 56) {
-            if (!stopped && n <= 32 && end - p >= 4) {           // four plain bytes at once
-                uint32_t v;
-                memcpy(&v, p, 4);
-                if (((~v - 0x01010101u) & v & 0x80808080u) == 0) {   // no byte is FF
-                    buf = (buf << 32) | __builtin_bswap32(v);
-                    n += 32;
-                    p += 4;
-                    continue;
-                }
-            }
-            if (!stopped && p < end) {
-                const unsigned c = *p;
-                if (c == 0xFF) {
-                    if (p + 1 >= end || p[1] != 0) {
-                        stopped = true;
-                        continue;
-                    }
-                    p += 2;
-                } else {
-                    ++p;
-                }
-                buf = (buf << 8) | c;
-                n += 8;
-            } else {
-                stopped = true;
-                buf <<= 8;
-                n += 8;
-                fake += 8;
-            }
-        }
-    }
-    inline unsigned get(int s) {                    // 1 <= s <= 16, n >= s
-        n -= s;
-        return (unsigned)(buf >> n) & ((1u << s) - 1u);
-    }
-    inline int decode(const HuffTable& t) {         // n >= 16
-        const unsigned e = t.look[(unsigned)(buf >> (n - kLook)) & ((1u << kLook) - 1u)];
-        if (e) {
-            n -= (int)(e >> 8);
-            return (int)(e & 255u);
-        }
-        int l = kLook + 1;
-        int32_t code = (int32_t)((buf >> (n - l)) & ((1u << l) - 1u));
-        while (l <= 16 && code > t.maxcode[l]) {
-            ++l;
-            code = (int32_t)((buf >> (n - l)) & ((1u << l) - 1u));
-        }
-        if (l > 16) return -1;
-        n -= l;
-        return t.vals[(code + t.valoff[l]) & 255];
-    }
-    inline bool overran() const { return n < fake; }     // zero bits that are not in the stream were consumed
-};
-
-inline int extend(unsigned v, int s) { return v < (1u << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
-
-inline bool decode_block(Bits& b, const HuffTable& dc, const HuffTable& ac, int& pred, int16_t* out) {
-    if (b.n < 32) b.refill();
-    int s = b.decode(dc);
-    if (s < 0 || s > 11) return false;
-    if (s) pred = (int)((unsigned)pred + (unsigned)extend(b.get(s), s));
-    out[0] = (int16_t)pred;
-    for (int k = 1; k < 64;) {
-        if (b.n < 32) b.refill();
-        const int rs = b.decode(ac);
-        if (rs < 0) return false;
-        const int r = rs >> 4;
-        s = rs & 15;
-        if (s) {
-            k += r;
-            if (k > 63) return false;
-            out[kNatural[k]] = (int16_t)extend(b.get(s), s);
-            ++k;
-        } else {
-            if (r != 15) break;             // end of block
-            k += 16;
-        }
-    }
-    return true;
-}
-
 // ------------------------------------------------------------------------------------------------ device
 struct DevGeometry {
     int ncomp, hs, vs, total;
-    int bw[3], bh[3], base[3];
+    int bw[4], bh[4], base[4];  // (base[c] = total for a component the image does not have)
     int cw, ch;                 // true size of a chroma component
 };
 
@@ -342,9 +219,10 @@ struct DevGeometry {
 // kernels touch: false = the image is skipped.
 __device__ __forceinline__ bool dev_geometry(const Desc& d, DevGeometry& g, size_t coef_bytes, size_t work_bytes, size_t sources_bytes) {
     if (d.width < 1 || d.height < 1 || d.width > 65535 || d.height > 65535 || (long long)d.width * d.height > kMaxPixels) return false;
-    if (d.components != 1 && d.components != 3) return false;
+    if (d.components != 1 && d.components != 3 && d.components != 4) return false;
     const bool samp_ok = (d.h_samp == 1 && d.v_samp == 1) || (d.components == 3 && d.h_samp == 2 && (d.v_samp == 1 || d.v_samp == 2));
     if (!samp_ok) return false;
+    if (d.components == 4 && (d.quant3 < 0 || d.quant3 > 2)) return false;      // the table the fourth component shares
     g.ncomp = d.components;
     g.hs = d.h_samp;
     g.vs = d.v_samp;
@@ -353,10 +231,13 @@ __device__ __forceinline__ bool dev_geometry(const Desc& d, DevGeometry& g, size
     g.bh[0] = my * g.vs;
     g.base[0] = 0;
     g.base[1] = g.bw[0] * g.bh[0];
-    g.bw[1] = g.bw[2] = g.ncomp == 3 ? mx : 0;
-    g.bh[1] = g.bh[2] = g.ncomp == 3 ? my : 0;
+    g.bw[1] = g.bw[2] = g.ncomp >= 3 ? mx : 0;
+    g.bh[1] = g.bh[2] = g.ncomp >= 3 ? my : 0;
+    g.bw[3] = g.ncomp == 4 ? mx : 0;
+    g.bh[3] = g.ncomp == 4 ? my : 0;
     g.base[2] = g.base[1] + g.bw[1] * g.bh[1];
-    g.total = g.base[2] + g.bw[2] * g.bh[2];
+    g.base[3] = g.base[2] + g.bw[2] * g.bh[2];
+    g.total = g.base[3] + g.bw[3] * g.bh[3];
     g.cw = (d.width + g.hs - 1) / g.hs;
     g.ch = (d.height + g.vs - 1) / g.vs;
     if (d.src_offset < 0 || d.coef_offset < 0 || d.work_offset < 0 || ((d.src_offset | d.coef_offset | d.work_offset) & 15)) return false;
@@ -436,13 +317,14 @@ __global__ void __launch_bounds__(kThreads) jpeg_idct_kernel(const int16_t* __re
     for (int first = blockIdx.x * kSlots; first < g.total; first += gridDim.x * kSlots) {       // (uniform trip count)
         const int blk = first + slot;
         const bool on = blk < g.total;
-        const int c = !on ? 0 : blk >= g.base[2] ? 2 : blk >= g.base[1] ? 1 : 0;     // (a grayscale image has base[1] = base[2] = total)
+        const int c = !on ? 0 : blk >= g.base[3] ? 3 : blk >= g.base[2] ? 2 : blk >= g.base[1] ? 1 : 0;     // (a missing component's base = total)
+        const int qc = c == 3 ? d.quant3 : c;
         int v[8], o[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = 0;
         if (on) {
             const uint4 cq = *reinterpret_cast<const uint4*>(src + (size_t)blk * 64 + lane * 8);
-            const uint4 qq = *reinterpret_cast<const uint4*>(&d.quant[c][lane * 8]);
+            const uint4 qq = *reinterpret_cast<const uint4*>(&d.quant[qc][lane * 8]);
             const unsigned cu[4] = {cq.x, cq.y, cq.z, cq.w}, qu[4] = {qq.x, qq.y, qq.z, qq.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -495,6 +377,12 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ plane, int 
 
 __device__ __forceinline__ unsigned clip255(int v) { return (unsigned)min(max(v, 0), 255); }
 
+// Pillow's MULDIV255: a * b / 255, rounded, for a, b in 0..255
+__device__ __forceinline__ int muldiv255(int a, int b) {
+    const int t = a * b + 128;
+    return ((t >> 8) + t) >> 8;
+}
+
 // One thread per 4 consecutive pixels of the packed image = 12 bytes = three aligned dword stores (src_offset is a multiple
 // of 16); the last, partial group of an image is stored byte by byte so that nothing behind the image is touched.
 __global__ void __launch_bounds__(kThreads) jpeg_colour_kernel(const Desc* __restrict__ descs, const uint8_t* __restrict__ work,
@@ -508,6 +396,7 @@ __global__ void __launch_bounds__(kThreads) jpeg_colour_kernel(const Desc* __res
     const uint8_t* yp = work + d.work_offset;
     const uint8_t* cbp = yp + (size_t)g.base[1] * 64;
     const uint8_t* crp = yp + (size_t)g.base[2] * 64;
+    const uint8_t* kp = yp + (size_t)g.base[3] * 64;            // (read only when the image has four components)
     const int ys = g.bw[0] * 8, cs = g.bw[1] * 8;
     uint8_t* dst = sources + d.src_offset;
     for (unsigned it = blockIdx.x * kThreads + threadIdx.x; it < groups; it += gridDim.x * kThreads) {
@@ -521,6 +410,14 @@ __global__ void __launch_bounds__(kThreads) jpeg_colour_kernel(const Desc* __res
                 const int lum = yp[(size_t)y * ys + x];
                 if (g.ncomp == 1) {
                     r = gg = b = (unsigned)lum;
+                } else if (g.ncomp == 4) {
+                    // Adobe CMYK, stored inverted: the library passes the four samples through, Pillow inverts them on load
+                    // (C = 255 - sample) and converts with nk = 255 - K = the fourth sample
+                    const size_t at = (size_t)y * ys + x;       // (four planes of one size)
+                    const int nk = kp[at];
+                    r = clip255(nk - muldiv255(255 - lum, nk));
+                    gg = clip255(nk - muldiv255(255 - (int)cbp[at], nk));
+                    b = clip255(nk - muldiv255(255 - (int)crp[at], nk));
                 } else {
                     const int cb = chroma_at(cbp, cs, g, x, y) - 128, cr = chroma_at(crp, cs, g, x, y) - 128;
                     r = clip255(lum + ((91881 * cr + 32768) >> 16));

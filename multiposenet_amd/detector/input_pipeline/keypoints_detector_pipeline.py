@@ -24,8 +24,9 @@ a batch stays valid until the next-but-one is requested. Evaluation batches (bat
 
 `decode='device'` (default 'host') moves the pixel half of the JPEG decode to the device: the pool runs only the marker scan and
 the Huffman decode (inference/jpeg.py), the coefficients are copied on the side stream and `mpn_jpeg_decode` writes the
-uint8 sources there, byte for byte what PIL decodes - so a seed gives the same batches in both modes. Streams the device path
-does not support (progressive, CMYK, ...) are decoded by PIL per image, inside the same batch.
+uint8 sources there, byte for byte what PIL decodes - so a seed gives the same batches in both modes. Progressive and Adobe
+CMYK files have all their scans decoded on the pool (`mpn_jpeg_scans_decode`); streams the device path does not support
+(arithmetic coding, YCCK, ...) are decoded by PIL per image, inside the same batch.
 
 `filenames` may also be an in-memory sequence of decoded examples, dicts with 'image' (uint8 [H,W,3]), 'boxes'
 (f32 [P,4] absolute), 'keypoints' (int [P,17,3]) and 'masks' (np.packbits bytes of [ceil(H/4), ceil(W/4), 2]) - no PIL is
@@ -179,7 +180,7 @@ class KeypointPipeline:
             ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = jpeg.prepare(img, entropy) if device else decode_jpeg(img)
+            img = jpeg.prepare(img, entropy, extended=True) if device else decode_jpeg(img)
         if not isinstance(img, (jpeg.Coefficients, jpeg.Scan)):
             img = np.ascontiguousarray(img, dtype=np.uint8)
             if img.ndim != 3 or img.shape[2] != 3:

@@ -81,7 +81,7 @@ class DetectorPipeline(KeypointPipeline):
             ex = dict(rec)
         img = ex["image"]
         if isinstance(img, (bytes, bytearray, memoryview)):
-            img = jpeg.prepare(img, entropy) if device else decode_jpeg(img)
+            img = jpeg.prepare(img, entropy, extended=True) if device else decode_jpeg(img)
         if not isinstance(img, (jpeg.Coefficients, jpeg.Scan)):
             img = np.ascontiguousarray(img, dtype=np.uint8)
             if img.ndim != 3 or img.shape[2] != 3:

@@ -509,8 +509,9 @@ class Detector:
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
-        `predict_images([pillow_decode(j) for j in jpegs], ...)`. A stream outside the supported set (progressive, CMYK, ...)
-        is decoded by Pillow and uploaded as pixels, inside the same batch. With entropy='device' the host only parses
+        `predict_images([pillow_decode(j) for j in jpegs], ...)`. Progressive and Adobe CMYK files have every scan
+        decoded on the host (mpn_jpeg_scans_decode) and the rest on the device like the others; a stream outside the supported
+        set (arithmetic coding, YCCK, ...) is decoded by Pillow and uploaded as pixels, inside the same batch. With entropy='device' the host only parses
         headers: the files' own bytes are uploaded (about a tenth of the coefficients) and the Huffman decode runs on the device
         too (mpn_jpeg_entropy_decode_device); an image it cannot settle takes the host decode. The same results either way.
 
@@ -535,7 +536,7 @@ class Detector:
         infos = [jpeg.jpeg_info(j) for j in items]
         height, width = resample.check_size(size)
         plan = resample.Plan([(i['height'], i['width']) for i in infos], height, width, keep_aspect_ratio, align=16)
-        entries = [jpeg.prepare(j, entropy) for j in items]
+        entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
                 raise ValueError(f"a JPEG decodes to {tuple(e.shape)}, its header says {(h, w, 3)}")

@@ -1,8 +1,10 @@
 """JPEG decode split between host and device (include/mpn.h, "JPEG decode"): `jpeg_info` and `entropy_decode` are the host
 stage (marker scan and Huffman decode in C++, the GIL released: a thread pool runs them in parallel), `JpegBatchDecoder` ships
 the coefficients of a batch and launches `mpn_jpeg_decode`, which writes uint8 RGB into a packed source buffer - the bytes Pillow
-returns for the same file. Streams outside the supported set (progressive, CMYK, ...) are decoded by Pillow per image and
-copied as pixels, inside the same batch.
+returns for the same file. Progressive files and Adobe CMYK files take a second host stage, `scans_decode` (every scan of the
+file -> the same coefficients; four planes for CMYK, which the device converts as Pillow does); `jpeg_support` says which route
+a file takes. Streams outside both sets (YCCK, arithmetic coding, 12 bits, ...) are decoded by Pillow per image and copied as
+pixels, inside the same batch.
 
 JPEG encode is the second half of the file: `quality_tables`, `jpeg_headers`, `JpegBatchEncoder`, `encode_jpegs`."""
 import ctypes
@@ -27,11 +29,23 @@ class _Header(ctypes.Structure):        # mpn_jpeg_header
                 ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32), ('coef_bytes', ctypes.c_int64)]
 
 
-# mpn_jpeg_desc as a numpy record (its three offsets are the caller's)
+class _ScansHeader(ctypes.Structure):   # mpn_jpeg_scans_header
+    _fields_ = [('width', ctypes.c_int32), ('height', ctypes.c_int32), ('components', ctypes.c_int32),
+                ('h_samp', ctypes.c_int32), ('v_samp', ctypes.c_int32), ('progressive', ctypes.c_int32),
+                ('route', ctypes.c_int32), ('reason', ctypes.c_int32),
+                ('blocks_w', ctypes.c_int32 * 4), ('blocks_h', ctypes.c_int32 * 4),
+                ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32), ('coef_bytes', ctypes.c_int64)]
+
+
+ROUTES = ('device', 'host-entropy', 'pillow')       # MPN_JPEG_ROUTE_*
+
+# mpn_jpeg_desc as a numpy record (its three offsets are the caller's). With four components the fourth's grid is
+# (blocks_h3, blocks_w3) and its quantisation table is quant[quant3]
 DESC = np.dtype([('src_offset', np.int64), ('coef_offset', np.int64), ('work_offset', np.int64),
                  ('width', np.int32), ('height', np.int32), ('components', np.int32), ('h_samp', np.int32), ('v_samp', np.int32),
                  ('total_blocks', np.int32), ('blocks_w', np.int32, (3,)), ('blocks_h', np.int32, (3,)),
-                 ('reserved', np.int32, (14,)), ('quant', np.uint16, (3, 64))])
+                 ('blocks_w3', np.int32), ('blocks_h3', np.int32), ('quant3', np.int32),
+                 ('reserved', np.int32, (11,)), ('quant', np.uint16, (3, 64))])
 assert DESC.itemsize == DESC_BYTES
 
 
@@ -78,8 +92,8 @@ def jpeg_info(data):
 
 
 class Coefficients:
-    """A JPEG after the host stage: `.shape` (h, w, 3) of the image it decodes to, `.coefs` int16 [total_blocks, 64] (raw
-    coefficients, natural order, one plane of blocks per component) and `.desc`, a one-element DESC record."""
+    """A JPEG after a host stage: `.shape` (h, w, 3) of the image it decodes to, `.coefs` int16 [total_blocks, 64] (raw
+    coefficients, natural order, one plane of blocks per component: 1, 3 or - CMYK - 4) and `.desc`, a one-element DESC record."""
     __slots__ = ('shape', 'coefs', 'desc')
 
     def __init__(self, shape, coefs, desc):
@@ -89,8 +103,8 @@ class Coefficients:
         """[(coefficients [blocks_h, blocks_w, 8, 8], quantisation table [8, 8])] per component."""
         d, out, at = self.desc[0], [], 0
         for c in range(int(d['components'])):
-            bh, bw = int(d['blocks_h'][c]), int(d['blocks_w'][c])
-            out.append((self.coefs[at:at + bh * bw].reshape(bh, bw, 8, 8), d['quant'][c].reshape(8, 8)))
+            bh, bw = (int(d['blocks_h'][c]), int(d['blocks_w'][c])) if c < 3 else (int(d['blocks_h3']), int(d['blocks_w3']))
+            out.append((self.coefs[at:at + bh * bw].reshape(bh, bw, 8, 8), d['quant'][c if c < 3 else int(d['quant3'])].reshape(8, 8)))
             at += bh * bw
         return out
 
@@ -108,6 +122,42 @@ def entropy_decode(data):
     desc = np.zeros(1, DESC)
     _lib.check(lib.mpn_jpeg_entropy_decode(data, len(data), coefs.ctypes.data_as(ctypes.c_void_p), coefs.nbytes,
                                            desc.ctypes.data_as(ctypes.c_void_p)))
+    return Coefficients((h.height, h.width, 3), coefs, desc)
+
+
+def scans_info(data):
+    """The header of a JPEG as the multi-scan host stage sees it: 'width', 'height', 'components', 'sampling', 'progressive'
+    (bool), 'route' (one of ROUTES), 'reason' (one of REASONS: why the route is 'pillow', else 'supported'), 'blocks'
+    [(blocks_h, blocks_w)] of up to four components, 'total_blocks', 'coef_bytes'. Damaged headers raise ValueError."""
+    data = _as_bytes(data)
+    h = _ScansHeader()
+    _lib.check(_lib.lib().mpn_jpeg_scans_info(data, len(data), ctypes.byref(h)))
+    return {'width': h.width, 'height': h.height, 'components': h.components, 'sampling': (h.h_samp, h.v_samp),
+            'progressive': bool(h.progressive), 'route': ROUTES[h.route], 'reason': REASONS[h.reason],
+            'blocks': [(h.blocks_h[c], h.blocks_w[c]) for c in range(min(h.components, 4))] if h.route != 2 else [],
+            'total_blocks': h.total_blocks, 'coef_bytes': h.coef_bytes}
+
+
+def jpeg_support(data):
+    """The route a JPEG takes through `prepare(..., extended=True)`: 'device' (baseline gray / YCbCr: one scan, whose Huffman
+    stage may run on the host or on the device), 'host-entropy' (progressive, Adobe CMYK: every scan decoded on the host by
+    `scans_decode`, the rest on the device) or 'pillow' (decoded by Pillow, copied as pixels). Damaged headers raise ValueError."""
+    return scans_info(data)['route']
+
+
+def scans_decode(data):
+    """The multi-scan host stage on one JPEG whose route is 'host-entropy' or 'device' -> Coefficients (four planes for CMYK).
+    Raises ValueError for a file that is damaged, truncated, incomplete or on the 'pillow' route."""
+    data = _as_bytes(data)
+    lib = _lib.lib()
+    h = _ScansHeader()
+    _lib.check(lib.mpn_jpeg_scans_info(data, len(data), ctypes.byref(h)))
+    if h.route == 2:
+        raise ValueError(f"scans_decode: stream not supported ({REASONS[h.reason]})")
+    coefs = np.empty((h.total_blocks, 64), np.int16)
+    desc = np.zeros(1, DESC)
+    _lib.check(lib.mpn_jpeg_scans_decode(data, len(data), coefs.ctypes.data_as(ctypes.c_void_p), coefs.nbytes,
+                                         desc.ctypes.data_as(ctypes.c_void_p)))
     return Coefficients((h.height, h.width, 3), coefs, desc)
 
 
@@ -142,10 +192,24 @@ def pillow_decode(data):
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
 
 
-def prepare(item, entropy='host'):
+def _extended(data):
+    """Coefficients of a file on the 'host-entropy' route, else Pillow's pixels (which raises for a damaged file)."""
+    h = _ScansHeader()
+    if _lib.lib().mpn_jpeg_scans_info(data, len(data), ctypes.byref(h)) == 0 and h.route == 1:
+        try:
+            return scans_decode(data)
+        except ValueError:
+            pass                # damaged, or a script the stage refuses: the library decides what the file is worth
+    return pillow_decode(data)
+
+
+def prepare(item, entropy='host', extended=False):
     """One entry of a batch, ready for `JpegBatchDecoder`: JPEG bytes -> Coefficients when the stream is supported (a Scan
     with entropy='device': headers only, the Huffman stage runs on the device), else the pixels Pillow decodes; a uint8
-    [h, w, 3] array, a Coefficients or a Scan passes through. Thread-safe (the pipelines' decode pool)."""
+    [h, w, 3] array, a Coefficients or a Scan passes through. extended=True (what the pipelines and `Detector.predict_jpegs`
+    pass) also returns Coefficients for progressive and Adobe CMYK files (`jpeg_support(data) == 'host-entropy'`): their
+    scans are decoded here, on the host, with either `entropy` - a file of several scans has no single scan to hand to the
+    device. The default keeps Pillow's pixels for them. Thread-safe (the pipelines' decode pool)."""
     check_entropy_mode(entropy)
     if isinstance(item, (Coefficients, Scan, np.ndarray)):
         return item
@@ -155,12 +219,12 @@ def prepare(item, entropy='host'):
         rc = _lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p))
         if rc == 0 and desc[0]['supported']:
             return Scan(data, (int(desc[0]['height']), int(desc[0]['width']), 3), desc)
-        return pillow_decode(data)
+        return _extended(data) if extended else pillow_decode(data)
     h = _Header()
     rc = _lib.lib().mpn_jpeg_info(data, len(data), ctypes.byref(h))
     if rc == 0 and h.supported:
         return entropy_decode(data)
-    return pillow_decode(data)
+    return _extended(data) if extended else pillow_decode(data)
 
 
 def _capacity(n):
@@ -177,7 +241,8 @@ class JpegBatchDecoder:
     mpn_jpeg_entropy_decode_device: the file's bytes and a header descriptor are staged instead of coefficients; the [B]
     records come back with one small copy and one event wait, and every image that is not OK takes the host `entropy_decode` -
     which raises ValueError for a damaged stream - and a second mpn_jpeg_decode; `.fallbacks` counts them) or uint8 [h, w, 3]
-    arrays (copied as pixels: streams the device path does not support, records that are not JPEGs). `.staged_bytes`: what
+    arrays (copied as pixels: streams the device path does not support, records that are not JPEGs). A Coefficients entry may
+    hold one, three or four planes (CMYK), in any mix. `.staged_bytes`: what
     the last `decode` uploaded. sources: a uint8 device tensor; image i lands at byte
     offsets[i], a multiple of 16. Coefficients, descriptors and fallback pixels go through ONE pinned staging buffer and ONE
     host-to-device copy on `stream`; staging and device buffers grow to the largest batch seen. A decoder is bound to one
