@@ -777,6 +777,49 @@ int mpn_pose_gather_sized(const float* boxes, const float* scores, const int* nu
                           const float* extent, void* record, size_t record_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * COCO keypoint evaluation of the record's persons against ground truth: object keypoint similarity (OKS) and the greedy
+ * matching of pycocotools' COCOeval for iouType='keypoints' (computeOks, evaluateImg), one block per image.
+ *
+ *   mpn_oks_match   record: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place (the header's total
+ *                     and counts; of a row its score, keypoint_scores and keypoints).
+ *                   gt f64 [B, max_gt, 64] DEVICE: a row of mpn_oks_gt_row_bytes() = 512 bytes is keypoints[17][3] = (x, y, v),
+ *                     bbox (x, y, w, h), area, ignore, iscrowd (non-zero = set), 6 doubles of padding; the pixels of the
+ *                     record's keypoints. gt_counts int32 [B] DEVICE (a count above max_gt reads max_gt rows).
+ *                   thresholds f64 [num_thresholds] DEVICE, 1 <= num_thresholds <= 10 (np.linspace(.5, .95, 10)).
+ *                   score_mode 0: a detection's score is the box score; 1: box score * (sum of keypoint_scores in order / 17),
+ *                     in f32. max_dets in 1..20: per image the first max_dets detections in descending score, equal scores
+ *                     in record order, are evaluated.
+ *                   Semantics, in float64 in this order without contraction: detection area (max x - min x) * (max y - min y)
+ *                     of its 17 keypoints; vars = (2 sigma)^2 of COCO's 17 sigmas; k1 = ground-truth keypoints with v > 0;
+ *                     k1 > 0: dx, dy = detection - ground truth over the v > 0 keypoints, else the distance to the doubled box
+ *                     (x0 = bx - bw, x1 = bx + 2 bw: max(0, x0 - xd) + max(0, xd - x1)) over all 17;
+ *                     e = (dx^2 + dy^2) / vars / (area + 2^-52) / 2; OKS = mean of exp(-e). Per area range (all [0, 1e10],
+ *                     medium [32^2, 96^2], large [96^2, 1e10]) a ground truth is ignored iff its ignore is set or its area
+ *                     lies outside; ground truth is walked not-ignored first (stable). Per range, threshold t and detection
+ *                     in score order: iou = min(t, 1 - 1e-10), m = none; for each ground truth: skip it if matched and not
+ *                     crowd; stop if m is set, not ignored, and this one is ignored; skip it if OKS < iou; else iou = OKS,
+ *                     m = it. A matched detection takes the ignore flag of its ground truth; an unmatched one is ignored iff
+ *                     its area lies outside the range.
+ *                   out: mpn_oks_match_out_bytes(B, max_boxes) bytes DEVICE, one row of 152 bytes per record row, aligned
+ *                     with the record's rows 0 .. total-1, every other row zero: int32 rank (>= max_dets: not evaluated,
+ *                     matches -1), f32 score, f64 area, int32 match[3][10] (range, threshold): the ground truth's index in
+ *                     the image's own order or -1 (also beyond num_thresholds), uint32 ignore[3]: bit t = ignored at
+ *                     threshold t, 4 bytes of zero.
+ *                   oks_out (may be NULL): f64 [B * max_boxes, max_gt], the OKS of each evaluated row against the image's
+ *                     ground truth, zero elsewhere.
+ *                   Checked before any HIP call: max_gt in 1..64 (MPN_ERR_BAD_SHAPE; a lane keeps its matched set in one
+ *                     64-bit mask), null pointers and score_mode (MPN_ERR_BAD_ARG), B, max_boxes <= 256, B * max_boxes <=
+ *                     4096, num_thresholds, max_dets (MPN_ERR_BAD_SHAPE), record 16-byte and the f64 buffers 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN). The grid depends on B alone: a captured launch serves any later ground truth.
+ *   mpn_oks_match_out_bytes   0 for arguments out of range.
+ */
+size_t mpn_oks_gt_row_bytes(void);
+size_t mpn_oks_match_out_bytes(int B, int max_boxes);
+int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, const int* gt_counts, int max_gt,
+                  const double* thresholds, int num_thresholds, int score_mode, int max_dets, void* out, double* oks_out,
+                  mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resize of a batch of RAGGED uint8 RGB sources onto the network canvas, equal byte for byte to Pillow's
  * `Image.resize` of an 8-bit RGB image with its default filter (antialiased bicubic), the host step of the reference's
  * inference/predict.ipynb (cell 6), with the top-left placement of `pad_to_bounding_box`

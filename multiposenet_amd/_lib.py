@@ -142,6 +142,9 @@ SIGNATURES = {
     "mpn_pose_gather_row_offset": (_Z, [_I, _I, _I]),
     "mpn_pose_gather": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _I, _P, _Z, _P]),
     "mpn_pose_gather_sized": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _Z, _P]),
+    "mpn_oks_gt_row_bytes": (_Z, []),
+    "mpn_oks_match_out_bytes": (_Z, [_I, _I]),
+    "mpn_oks_match": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "mpn_image_resize_desc_bytes": (_Z, []),
     "mpn_image_resize_workspace_bytes": (_Z, [_I, _I, _I, _L]),
     "mpn_image_resize": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),

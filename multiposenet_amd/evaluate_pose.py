@@ -1,0 +1,115 @@
+"""COCO keypoint AP of the joint inference graph over a validation set.
+
+    python -m multiposenet_amd.evaluate_pose --val-dataset DIR | --annotations JSON --images DIR
+        [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32]
+        [--batch 16] [--size W H] [--keep-aspect-ratio] [--score-threshold 0.05] [--score box|box*keypoints] [--out FILE]
+
+--val-dataset: TFRecord shards of the keypoint contract (input_pipeline/tfrecord.py; tools/make_toy_tfrecords.py writes toy
+ones). Their JPEG bytes go through `Detector.predict_jpegs`, their persons become the ground truth
+(`pose_metrics.groundtruth_from_record`: box areas, no dropped persons - a yardstick between runs, not the official number).
+--annotations / --images: COCO's person_keypoints_*.json and the directory of its JPEG files; COCO's own areas and crowds.
+The matching runs inside the Detector's captured graph (`groundtruth=`); the ten numbers are printed and appended to --out
+as one JSON line. Without a model file the weights are seeded random ones: the numbers then only show that the path runs."""
+import argparse
+import json
+import os
+
+import numpy as np
+
+
+def _record_batches(directory, batch):
+    from .detector.input_pipeline.tfrecord import decode_keypoint_example, read_records
+    from .pose_metrics import groundtruth_from_record
+    shards = sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(".tfrecords"))
+    if not shards:
+        raise SystemExit(f"no *.tfrecords under {directory}")
+    jpegs, gts = [], []
+    for path in shards:
+        for data in read_records(path):
+            example = decode_keypoint_example(data, decode_image=False)
+            jpegs.append(bytes(example["image"]))
+            gts.append(groundtruth_from_record(example))
+            if len(jpegs) == batch:
+                yield jpegs, gts
+                jpegs, gts = [], []
+    if jpegs:
+        yield jpegs, gts
+
+
+def _coco_batches(annotations, images, batch):
+    from .pose_metrics import groundtruth_from_coco
+    jpegs, gts = [], []
+    for _, (file_name, gt) in sorted(groundtruth_from_coco(annotations).items()):
+        with open(os.path.join(images, file_name), "rb") as f:
+            jpegs.append(f.read())
+        gts.append(gt)
+        if len(jpegs) == batch:
+            yield jpegs, gts
+            jpegs, gts = [], []
+    if jpegs:
+        yield jpegs, gts
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--val-dataset")
+    ap.add_argument("--annotations")
+    ap.add_argument("--images")
+    ap.add_argument("--model", help="keypoint model .npz (the shared backbone)")
+    ap.add_argument("--detector", help="person detector head .npz")
+    ap.add_argument("--prn", help="pose residual network .npz")
+    ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, nargs=2, default=(640, 640), metavar=("W", "H"))
+    ap.add_argument("--keep-aspect-ratio", action="store_true")
+    ap.add_argument("--score-threshold", type=float, default=0.05)
+    ap.add_argument("--score", choices=("box", "box*keypoints"), default="box")
+    ap.add_argument("--out", default="pose_eval.jsonl")
+    args = ap.parse_args(argv)
+    if bool(args.val_dataset) == bool(args.annotations):
+        ap.error("give --val-dataset DIR, or --annotations JSON with --images DIR")
+    if args.annotations and not args.images:
+        ap.error("--annotations needs --images DIR")
+
+    import torch
+    from .inference import Detector
+    from .pose_metrics import STAT_NAMES, PoseEvaluator
+    from .prn import initial_values
+    if args.detector is None or args.prn is None:
+        print("[evaluate_pose] no --detector / --prn file: seeded random weights, the numbers mean nothing")
+    head = args.detector if args.detector is not None else _random_head()
+    det = Detector(args.model, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, detector_path=head,
+                   prn_path=args.prn if args.prn is not None else initial_values(seed=0))
+    det.oks_score = args.score
+    evaluator = PoseEvaluator(score=args.score)
+    batches = _record_batches(args.val_dataset, args.batch) if args.val_dataset else _coco_batches(args.annotations, args.images, args.batch)
+    images = persons = 0
+    for jpegs, gts in batches:
+        outs = det.predict_jpegs(jpegs, size=(args.size[1], args.size[0]), keep_aspect_ratio=args.keep_aspect_ratio,
+                                 score_threshold=args.score_threshold, groundtruth=gts)
+        evaluator.update(outs, gts)
+        images += len(jpegs)
+        persons += sum(len(o["scores"]) for o in outs)
+    stats = evaluator.evaluate()
+    for name in STAT_NAMES:
+        print(f"{name:5s} {stats[name]:.4f}")
+    line = dict(stats, images=images, detections=persons, groundtruth=int(evaluator.num_groundtruth[0]), dtype=args.dtype,
+                size=list(args.size), keep_aspect_ratio=args.keep_aspect_ratio, score_threshold=args.score_threshold, score=args.score)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+    return stats
+
+
+def _random_head():
+    """Seeded random variables of the person detector's head with lively class logits (a random-init class tower gives every
+    anchor the same score), for trying the path without trained models."""
+    from .retinanet import initial_head_values
+    head = initial_head_values(0)
+    head["class_net/logits/kernel"] = (np.random.RandomState(8).randn(3, 3, 64, 6) * 0.4).astype(np.float32)
+    head["class_net/logits/bias"] = np.full(6, -2.0, np.float32)
+    return head
+
+
+if __name__ == "__main__":
+    main()

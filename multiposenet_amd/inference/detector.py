@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import pose_metrics
 from ..net import KeypointNet
 from . import draw, jpeg, maps, resample
 
@@ -95,10 +96,10 @@ def _batch_frames(b, h, w):
 class _Entry:
     """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
     input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
-    it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, and the packed
-    sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
+    ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
-    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps',
+    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
                  'sources', 'meta_stage', 'meta', 'work', 'jpeg')
 
     def __init__(self, **buffers):
@@ -170,6 +171,8 @@ class Detector:
         self._graphs = {}
         self._eager_batches, self._batch_assigners = {}, {}         # predict_batch: buffers of the eager path, PRN per slot count
         self._image_capacity = {}                                   # predict_images: buffer capacities per (b, h, w, threshold)
+        # groundtruth=: how mpn_oks_match scores and cuts an image's detections (by-value launch arguments: part of the key)
+        self.oks_score, self.oks_max_dets = 'box', pose_metrics.MAX_DETS
         self.retinanet = None
         if detector_path is not None:
             from ..retinanet import PersonDetectorNet
@@ -293,7 +296,7 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0', plot_maps=False):
+                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -313,6 +316,12 @@ class Detector:
                 segmentation mask, byte for byte what Pillow and matplotlib make of them (made on the device inside the
                 captured graph, a graph of its own; only the picture is copied to the host, with return_heatmaps False too).
                 Combines freely with annotate.
+            groundtruth: a list of b ground-truth dicts (pose_metrics.groundtruth_arrays: 'keypoints' [g,17,3] (x, y, v) and
+                'boxes' [g,4] (x, y, w, h) in the pixels of the network input, optional 'area' and 'iscrowd'; at most 64
+                persons each). Adds 'oks' to every dict: COCO's keypoint matching of that image's persons against its ground
+                truth (`pose_metrics.PoseEvaluator.update` takes the dicts as they are), made by one mpn_oks_match launch
+                behind the gather inside the captured graph - a graph of its own per (b, height, width, threshold,
+                self.oks_score, self.oks_max_dets) that follows each call's ground truth; every other key is unchanged.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
@@ -320,7 +329,10 @@ class Detector:
         plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         b, h, w = check_batch(images)
         thr = float(score_threshold)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps)
+        oks = self._check_groundtruth(groundtruth, b)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks)
+        if oks:
+            ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
         if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
             self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), jp))
         stage = ent.stage.numpy()
@@ -330,8 +342,24 @@ class Detector:
             for i, im in enumerate(images):
                 stage[i] = im
         ent.x.copy_(ent.stage, non_blocking=True)                   # ONE host-to-device copy
-        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps))
+        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps,
+                                                              oks=ent.oks))
         return self._finish(ent, outs, b, return_heatmaps)
+
+    def _check_groundtruth(self, groundtruth, b):
+        """The `groundtruth` argument of the predict_* methods -> () or the tail of the entry's key."""
+        if groundtruth is None:
+            return ()
+        if self.retinanet is None:
+            raise ValueError("groundtruth= needs the person detector (detector_path): without it no persons are detected")
+        if not isinstance(groundtruth, (list, tuple)) or len(groundtruth) != b:
+            raise ValueError(f"groundtruth must be a list of {b} dicts, one per image")
+        if self.oks_score not in pose_metrics.SCORE_MODES:
+            raise ValueError(f"oks_score must be one of {sorted(pose_metrics.SCORE_MODES)} (got {self.oks_score!r})")
+        return ('oks', self.oks_score, int(self.oks_max_dets))
+
+    def _oks_buffers(self, b, oks):
+        return pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, self.net.device, oks[1], oks[2])
 
     @staticmethod
     def _place_encode(ent, plan):
@@ -362,7 +390,12 @@ class Detector:
         host = ent.host
         files = ent.encode.collect(ent.encode_plan, outs['encoded']) if 'encoded' in outs else None
         if 'record' in outs:
-            persons = unpack_record(host['record'].numpy(), b, self.params['max_boxes'], self.assigner is not None)
+            record = host['record'].numpy()
+            persons = unpack_record(record, b, self.params['max_boxes'], self.assigner is not None)
+            if ent.oks is not None:                                 # the match rows lie behind the record: they came with it
+                at = _lib.lib().mpn_pose_gather_record_bytes(b, self.params['max_boxes'])
+                for p, table in zip(persons, ent.oks.unpack(record[at:], record[4:4 + 4 * b].view(np.int32))):
+                    p['oks'] = table
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -380,14 +413,15 @@ class Detector:
                 p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False):
-        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps]): pinned staging, the device input, fixed drawing and
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=()):
+        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks]): pinned staging, the device input, fixed drawing and
         encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
         if annotate:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
         if plot_maps:
             key += ('maps',)
+        key += oks
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -405,17 +439,22 @@ class Detector:
             self._place_encode(ent, plan)
         if plot_maps:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
+        if oks:
+            ent.oks = self._oks_buffers(b, oks)
         store[key] = ent
         return ent
 
-    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None):
+    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None,
+                           oks=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
         draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat uint8; default:
         the batch x itself) -> 'annotated', the packed RGBA frames. encode (a jpeg.JpegBatchEncoder whose descriptors are in
         place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'.
-        plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'."""
+        plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
+        oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
+        the record in the same buffer, so that they reach the host in the record's copy."""
         net = self.net
         b, h, w, _ = x.shape
         bufs = net._buffers(b, h, w)
@@ -441,7 +480,8 @@ class Detector:
         nbytes = lib.mpn_pose_gather_record_bytes(b, max_boxes)
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        record = torch.empty(nbytes, dtype=torch.uint8, device=net.device)
+        whole = torch.empty(nbytes + (oks.out_bytes if oks is not None else 0), dtype=torch.uint8, device=net.device)
+        record = whole[:nbytes]
         if extent is None:
             _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
                       _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
@@ -450,7 +490,9 @@ class Detector:
             _lib.call("mpn_pose_gather_sized", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']),
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
-        dev['record'] = record
+        if oks is not None:
+            oks.launch(record, whole[nbytes:])
+        dev['record'] = whole
         if annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
         return self._encode_frames(dev, encode)
@@ -464,7 +506,7 @@ class Detector:
 
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False):
+                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -484,6 +526,7 @@ class Detector:
                 'jpeg' adds 'annotated_jpeg' instead, as `predict_batch` does: the file Pillow writes for that frame.
             jpeg_quality, jpeg_subsampling: as for `predict_batch`.
             plot_maps: as for `predict_batch`; the picture shows the network's input, the resized CANVAS (padding included).
+            groundtruth: as for `predict_batch`, in the pixels of the SOURCE images (where 'keypoints' are returned).
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -501,11 +544,12 @@ class Detector:
                 stage[at:at + im.size] = im.reshape(-1)
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
-        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps)
+        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host'):
+                      annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
+                      groundtruth=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -521,6 +565,7 @@ class Detector:
                 the decode, and how many images took the fallback.
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
+            groundtruth: as for `predict_images` (source pixels).
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -546,15 +591,17 @@ class Detector:
                 ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
             self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
-        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps)
+        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth)
 
-    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False):
+    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False,
+                         groundtruth=None):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
         one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
         b, thr = plan.b, float(score_threshold)
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps)
+        oks = self._check_groundtruth(groundtruth, b)
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
@@ -563,26 +610,29 @@ class Detector:
             ent.draw.place(plan.sizes, plan.src_offsets)
         if jp:
             self._place_encode(ent, eplan)
+        if oks:
+            ent.oks.place(groundtruth)
         persons = self._finish(ent, self._run(ent, lambda: self._device_side_images(ent, thr)), b, return_heatmaps)
         if return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=()):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
         exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
         output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
         capacity also covers the encoder's coefficients, streams and workspace. plot_maps: an entry of its own with a
-        MapPlotter for the canvas batch."""
+        MapPlotter for the canvas batch. oks (groundtruth=): an entry of its own with the ground-truth buffers."""
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
         base = ('images', b, h, w, thr)
         tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
         if plot_maps:
             tail += ('maps',)
+        tail += oks
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -611,6 +661,8 @@ class Detector:
             ent.encode.reserve(b, *cap[3:])
         if plot_maps:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
+        if oks:
+            ent.oks = self._oks_buffers(b, oks)
         store[key] = ent
         return ent
 
@@ -622,7 +674,8 @@ class Detector:
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps)
+        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps,
+                                       oks=ent.oks)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)
