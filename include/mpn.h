@@ -820,6 +820,56 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
                   mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
+ * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
+ * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no
+ * synchronisation. DESIGN.md section 21 has the semantics in full; tests/coco_mask_ref.py is their definition.
+ *
+ *   images   DEVICE [num_images]: sides h, w in 1..max_side; plane_offset: 32-bit words into `workspace`, where the image's
+ *              mpn_coco_masks_plane_words(h, w) words lie; packed_offset: bytes into `packed`, where its
+ *              mpn_coco_masks_packed_bytes(h, w) bytes go; full_offset: bytes into `full` (h * w * 2 of them; unused
+ *              without `full`); tap_x, tap_y: first entry of its ceil(w/4) horizontal and ceil(h/4) vertical taps.
+ *   parts    DEVICE [num_parts]: one polygon or one run-length code of a person of image `image`. flags:
+ *              MPN_COCO_PART_DROPPED - the person is masked out of the loss (else it belongs to the segmentation mask);
+ *              MPN_COCO_PART_RLE - `offset` / `count` are uint32 run lengths in `runs` (COCO's order: column-major,
+ *              starting with a run of zeros), else `count` vertices = 2 * count float64 (x, y) from `xy[offset]`.
+ *              Polygon -> mask is COCO maskApi's rleFrPoly; the masks of a person's parts are united (OR).
+ *              seg = OR over the kept persons, loss = AND over the dropped persons of (mask == 0).
+ *   taps     DEVICE [num_taps][5] int32: {floor of the source coordinate s, then int16 weight[8]} of OpenCV's
+ *              resize(INTER_LANCZOS4) for uint8: taps at s-3 .. s+4, indices clamped to the image, weights with 11
+ *              fractional bits; horizontal integer sum, vertical integer sum, (x + 2^21) >> 22 saturated to 0..255.
+ *   workspace  DEVICE, 16-byte aligned, workspace_bytes a multiple of 16: the images' bitmaps (zeroed by the call).
+ *   packed   DEVICE: per image numpy.packbits(stack([loss, seg], 2) > 0) of the [ceil(h/4), ceil(w/4), 2] array: MSB first,
+ *              the bit stream running across row ends, the last byte zero-padded.
+ *   full     DEVICE or NULL: per image uint8 [h, w, 2] of 0 / 1 (loss, seg).
+ * The tables are read on the device: a part or an image whose offsets, counts or sides do not fit the totals given here
+ * (num_xy in doubles, num_runs, num_taps, the three byte counts, max_side) is skipped, nothing is indexed out of range.
+ * Checked before any HIP call: max_side in 1..MPN_COCO_MASKS_MAX_SIDE, num_images in 1..65535, counts >= 0, num_taps >= 1
+ * (MPN_ERR_BAD_SHAPE); null pointers (MPN_ERR_BAD_ARG; parts / xy / runs may be null with a count of 0); alignment
+ * (MPN_ERR_BAD_ALIGN); workspace_bytes, packed_bytes, full_bytes (MPN_ERR_WORKSPACE).
+ *   mpn_coco_masks_plane_words, mpn_coco_masks_packed_bytes   0 for a side outside 1..MPN_COCO_MASKS_MAX_SIDE.
+ */
+#define MPN_COCO_MASKS_MAX_SIDE 1024
+#define MPN_COCO_PART_DROPPED 1
+#define MPN_COCO_PART_RLE 2
+typedef struct mpn_coco_image_desc {
+    long long plane_offset, packed_offset, full_offset;
+    int h, w, tap_x, tap_y;
+} mpn_coco_image_desc;                          /* 40 bytes */
+typedef struct mpn_coco_part_desc {
+    long long offset;
+    int count, image, flags, reserved;
+} mpn_coco_part_desc;                           /* 24 bytes */
+size_t mpn_coco_masks_image_desc_bytes(void);
+size_t mpn_coco_masks_part_desc_bytes(void);
+size_t mpn_coco_masks_plane_words(int h, int w);
+size_t mpn_coco_masks_packed_bytes(int h, int w);
+int mpn_coco_masks(const mpn_coco_image_desc* images, int num_images, int max_side, const mpn_coco_part_desc* parts,
+                   int num_parts, const double* xy, long long num_xy, const uint32_t* runs, long long num_runs,
+                   const int32_t* taps, long long num_taps, void* workspace, size_t workspace_bytes, void* packed,
+                   size_t packed_bytes, void* full, size_t full_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Resize of a batch of RAGGED uint8 RGB sources onto the network canvas, equal byte for byte to Pillow's
  * `Image.resize` of an 8-bit RGB image with its default filter (antialiased bicubic), the host step of the reference's
  * inference/predict.ipynb (cell 6), with the top-left placement of `pad_to_bounding_box`

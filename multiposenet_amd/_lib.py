@@ -145,6 +145,11 @@ SIGNATURES = {
     "mpn_oks_gt_row_bytes": (_Z, []),
     "mpn_oks_match_out_bytes": (_Z, [_I, _I]),
     "mpn_oks_match": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "mpn_coco_masks_image_desc_bytes": (_Z, []),
+    "mpn_coco_masks_part_desc_bytes": (_Z, []),
+    "mpn_coco_masks_plane_words": (_Z, [_I, _I]),
+    "mpn_coco_masks_packed_bytes": (_Z, [_I, _I]),
+    "mpn_coco_masks": (_I, [_P, _I, _I, _P, _I, _P, _L, _P, _L, _P, _L, _P, _Z, _P, _Z, _P, _Z, _P]),
     "mpn_image_resize_desc_bytes": (_Z, []),
     "mpn_image_resize_workspace_bytes": (_Z, [_I, _I, _I, _L]),
     "mpn_image_resize": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),
