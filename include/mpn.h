@@ -1045,8 +1045,8 @@ int mpn_plot_maps(const uint8_t* frames, const float* heatmaps, const float* mas
  * Everything else is CLASSIFIED (supported = 0 and a reason) and left to a library: progressive, arithmetic, lossless /
  * hierarchical frames, 12-bit precision, 2 or 4 components (CMYK / YCCK), an Adobe marker with a transform other than 1
  * or 'R','G','B' component ids, other sampling (4:4:0, 4:1:1, ...), several scans, 16-bit quantisation tables.
- * (Progressive files and Adobe CMYK have a host stage of their own, mpn_jpeg_scans_decode below; these three calls still
- * classify them as unsupported.)
+ * (Progressive files and Adobe CMYK are read by the same host front end under its all-scans policy, mpn_jpeg_scans_decode
+ * below; these three calls - its one-scan policy - still classify them as unsupported.)
  *
  * HOST (no HIP call, no global state: thread-safe and re-entrant; nothing is read past nbytes or written past coef_bytes):
  *   mpn_jpeg_info            scans the markers up to the first scan. MPN_OK for every stream it can classify (supported or
@@ -1128,9 +1128,11 @@ int mpn_jpeg_decode(const int16_t* coefs, size_t coef_bytes, const void* descs, 
                     size_t sources_bytes, void* work, size_t work_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
- * JPEG decode of multi-scan and four-component files: a second HOST stage beside mpn_jpeg_entropy_decode, and a fourth
- * plane in mpn_jpeg_decode. mpn_jpeg_info / mpn_jpeg_entropy_decode / mpn_jpeg_scan_prepare are unchanged: they still
- * classify these files as MPN_JPEG_PROGRESSIVE / MPN_JPEG_COMPONENTS.
+ * JPEG decode of multi-scan and four-component files: the all-scans policy of the HOST front end (one marker parser and one
+ * scan decoder serve it and mpn_jpeg_entropy_decode alike), and a fourth plane in mpn_jpeg_decode. mpn_jpeg_info /
+ * mpn_jpeg_entropy_decode / mpn_jpeg_scan_prepare keep the one-scan policy: they classify these files as
+ * MPN_JPEG_PROGRESSIVE / MPN_JPEG_COMPONENTS, stop at the first verdict and never read behind the first scan, so on damaged
+ * input the two policies may answer differently ("JPEG host front end").
  *
  * What it adds: 8-bit Huffman PROGRESSIVE files (SOF2) of one component, of three in YCbCr (the samplings above) or of four;
  * and BASELINE files of four. Four components means: every component sampled 1x1 and an Adobe APP14 marker with transform 0

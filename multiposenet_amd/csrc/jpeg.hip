@@ -1,15 +1,11 @@
-// Baseline JPEG decode split in two ("hybrid"): the serial part on the host, the parallel part on the device, the result equal
-// byte for byte to what libjpeg(-turbo) - and so Pillow - returns for the same bytes.
+// The device half of the JPEG decode: the host front end (jpeg_host.hip, plain C++) turns a file into raw int16 coefficients,
+// 64 per 8x8 block in natural order, one plane of blocks per component, and a fixed-size descriptor; the kernels here turn
+// those into pixels equal byte for byte to what libjpeg(-turbo) - and so Pillow - returns for the same bytes.
 //
-//   HOST   mpn_jpeg_info            marker scan: geometry, sampling, restart interval, supported / reason
-//          mpn_jpeg_entropy_decode  Huffman decode of the one interleaved scan -> raw int16 coefficients, 64 per 8x8 block in
-//                                   natural order, one plane of blocks per component + a fixed-size descriptor
-//          (no HIP call, no globals: thread-safe and re-entrant; every read is checked against `nbytes`; Huffman tables
-//          and the bit reader live in jpeg_host.h, shared with the multi-scan stage of jpeg_scans.hip)
-//   DEVICE mpn_jpeg_decode          jpeg_idct_kernel    dequantise + 8x8 inverse DCT -> uint8 component planes in `work`
-//                                   jpeg_colour_kernel  "fancy" chroma upsampling + YCbCr->RGB -> packed HWC uint8 at src_offset
-//                                   (four components - Adobe CMYK, coefficients from jpeg_scans.hip - : four planes, and
-//                                   Pillow's inversion and CMYK->RGB in place of YCbCr->RGB)
+//   mpn_jpeg_decode          jpeg_idct_kernel    dequantise + 8x8 inverse DCT -> uint8 component planes in `work`
+//                            jpeg_colour_kernel  "fancy" chroma upsampling + YCbCr->RGB -> packed HWC uint8 at src_offset
+//                            (four components - Adobe CMYK - : four planes, and Pillow's inversion and CMYK->RGB in place of
+//                            YCbCr->RGB)
 //
 // The arithmetic is libjpeg's, all integer:
 //   - inverse DCT: the "slow integer" method (13-bit constants, 2 extra bits after pass 1, COLUMNS first, then rows),
@@ -18,195 +14,13 @@
 //     the component's TRUE down-sampled size; a component of width <= 2 is replicated (the library's own rule);
 //   - colour: the 16-bit fixed-point YCbCr->RGB tables with their rounding terms.
 #include "common.h"
-#include "jpeg_host.h"
-#include <string.h>
 
 namespace {
 
 typedef mpn_jpeg_desc Desc;
 static_assert(sizeof(Desc) == MPN_JPEG_DESC_BYTES, "descriptor layout is part of the ABI");
 
-constexpr long long kMaxPixels = 1ll << 28;    // keeps every index of an image in 32 bits
-
-using namespace mpn_jpeg_host;
-
-// ------------------------------------------------------------------------------------------------ host: markers
-struct Parsed {
-    int width, height, ncomp;
-    int cid[3], hs[3], vs[3], tq[3], td[3], ta[3];
-    int restart;
-    bool jfif, adobe, sof, q16;
-    int adobe_transform;
-    uint16_t q[4][64];                  // natural order
-    bool qset[4];
-    uint8_t hbits[2][4][17];            // [class][id]: codes per length 1..16
-    uint8_t hvals[2][4][256];
-    bool hset[2][4];
-    size_t scan_pos;                    // first entropy-coded byte
-};
-
-// Scans the markers up to the first scan. Returns the reason code (MPN_JPEG_SUPPORTED = 0: a stream the device path decodes).
-int parse(const uint8_t* data, size_t n, Parsed& p) {
-    memset(&p, 0, sizeof(p));
-    if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return MPN_JPEG_MALFORMED;
-    size_t pos = 2;
-    for (;;) {
-        if (pos + 2 > n || data[pos] != 0xFF) return MPN_JPEG_MALFORMED;
-        while (pos < n && data[pos] == 0xFF) ++pos;          // fill bytes
-        if (pos >= n) return MPN_JPEG_MALFORMED;
-        const int m = data[pos++];
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;  // stand-alone markers
-        if (m == 0x00 || m == 0xD8 || m == 0xD9) return MPN_JPEG_MALFORMED;
-        if (pos + 2 > n) return MPN_JPEG_MALFORMED;
-        const size_t L = ((size_t)data[pos] << 8) | data[pos + 1];
-        if (L < 2 || pos + L > n) return MPN_JPEG_MALFORMED;
-        const uint8_t* s = data + pos + 2;
-        const size_t len = L - 2;
-        if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {      // a frame header
-            if (p.sof || len < 6) return MPN_JPEG_MALFORMED;
-            p.sof = true;
-            const int precision = s[0], nf = s[5];
-            p.height = (s[1] << 8) | s[2];
-            p.width = (s[3] << 8) | s[4];
-            p.ncomp = nf;
-            if (len != 6 + 3 * (size_t)nf || nf < 1) return MPN_JPEG_MALFORMED;
-            for (int i = 0; i < nf && i < 3; ++i) {
-                p.cid[i] = s[6 + 3 * i];
-                p.hs[i] = s[7 + 3 * i] >> 4;
-                p.vs[i] = s[7 + 3 * i] & 15;
-                p.tq[i] = s[8 + 3 * i];
-            }
-            if (m == 0xC2) return MPN_JPEG_PROGRESSIVE;
-            if (m >= 0xC9) return MPN_JPEG_ARITHMETIC;
-            if (m != 0xC0 && m != 0xC1) return MPN_JPEG_FRAME_TYPE;      // lossless, hierarchical
-            if (precision != 8) return MPN_JPEG_PRECISION;
-            if (p.width < 1 || p.height < 1) return MPN_JPEG_MALFORMED;  // (height 0 = a DNL marker follows: not handled)
-            if (nf != 1 && nf != 3) return MPN_JPEG_COMPONENTS;
-            for (int i = 0; i < nf; ++i) {
-                if (p.hs[i] < 1 || p.hs[i] > 4 || p.vs[i] < 1 || p.vs[i] > 4 || p.tq[i] > 3) return MPN_JPEG_MALFORMED;
-            }
-            if (nf == 3) {
-                const bool luma_ok = (p.hs[0] == 1 && p.vs[0] == 1) || (p.hs[0] == 2 && p.vs[0] == 1) || (p.hs[0] == 2 && p.vs[0] == 2);
-                if (!luma_ok || p.hs[1] != 1 || p.vs[1] != 1 || p.hs[2] != 1 || p.vs[2] != 1) return MPN_JPEG_SAMPLING;
-            } else {
-                p.hs[0] = p.vs[0] = 1;      // a single component is never interleaved: its factors do not matter
-            }
-            if ((long long)p.width * p.height > kMaxPixels) return MPN_JPEG_TOO_LARGE;
-        } else if (m == 0xCC) {
-            return MPN_JPEG_ARITHMETIC;
-        } else if (m == 0xDB) {             // quantisation tables
-            size_t i = 0;
-            while (i < len) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                ++i;
-                if (tq > 3 || pq > 1 || i + (pq ? 128u : 64u) > len) return MPN_JPEG_MALFORMED;
-                if (pq) p.q16 = true;
-                for (int k = 0; k < 64; ++k) {
-                    p.q[tq][kNatural[k]] = pq ? (uint16_t)((s[i + 2 * k] << 8) | s[i + 2 * k + 1]) : s[i + k];
-                }
-                p.qset[tq] = true;
-                i += pq ? 128 : 64;
-            }
-        } else if (m == 0xC4) {             // Huffman tables
-            size_t i = 0;
-            while (i < len) {
-                if (i + 17 > len) return MPN_JPEG_MALFORMED;
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 3) return MPN_JPEG_MALFORMED;
-                int count = 0;
-                p.hbits[tc][th][0] = 0;
-                for (int l = 1; l <= 16; ++l) {
-                    p.hbits[tc][th][l] = s[i + l];
-                    count += s[i + l];
-                }
-                i += 17;
-                if (count > 256 || i + count > len) return MPN_JPEG_MALFORMED;
-                memset(p.hvals[tc][th], 0, 256);
-                memcpy(p.hvals[tc][th], s + i, count);
-                p.hset[tc][th] = true;
-                i += count;
-            }
-        } else if (m == 0xDD) {
-            if (len != 2) return MPN_JPEG_MALFORMED;
-            p.restart = (s[0] << 8) | s[1];
-        } else if (m == 0xE0) {
-            if (len >= 5 && memcmp(s, "JFIF", 5) == 0) p.jfif = true;
-        } else if (m == 0xEE) {
-            if (len >= 12 && memcmp(s, "Adobe", 5) == 0) {
-                p.adobe = true;
-                p.adobe_transform = s[11];
-            }
-        } else if (m == 0xDA) {             // the scan
-            if (!p.sof || len < 1) return MPN_JPEG_MALFORMED;
-            const int ns = s[0];
-            if (ns < 1 || ns > 4 || len != 4 + 2 * (size_t)ns) return MPN_JPEG_MALFORMED;
-            if (ns != p.ncomp) return MPN_JPEG_MULTISCAN;
-            for (int i = 0; i < ns; ++i) {
-                if (s[1 + 2 * i] != p.cid[i]) return MPN_JPEG_MALFORMED;
-                p.td[i] = s[2 + 2 * i] >> 4;
-                p.ta[i] = s[2 + 2 * i] & 15;
-                if (p.td[i] > 3 || p.ta[i] > 3 || !p.hset[0][p.td[i]] || !p.hset[1][p.ta[i]] || !p.qset[p.tq[i]]) return MPN_JPEG_MALFORMED;
-            }
-            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) return MPN_JPEG_MALFORMED;
-            if (p.q16) return MPN_JPEG_DQT16;
-            if (p.ncomp == 3) {
-                // libjpeg's colour-space guess: anything but YCbCr is left to the library
-                if (p.adobe && p.adobe_transform != 1) return MPN_JPEG_COLORSPACE;
-                if (!p.jfif && !p.adobe && p.cid[0] == 'R' && p.cid[1] == 'G' && p.cid[2] == 'B') return MPN_JPEG_COLORSPACE;
-            }
-            p.scan_pos = pos + L;
-            return MPN_JPEG_SUPPORTED;
-        }
-        pos += L;
-    }
-}
-
-struct Geometry {
-    int ncomp, hs, vs;
-    int bw[3], bh[3];       // padded block grid of each component
-    long long base[4];      // first block of each component's plane; base[ncomp] = all blocks
-};
-
-void geometry_of(const Parsed& p, Geometry& g) {
-    g.ncomp = p.ncomp;
-    g.hs = p.hs[0];
-    g.vs = p.vs[0];
-    const int mx = (p.width + 8 * g.hs - 1) / (8 * g.hs), my = (p.height + 8 * g.vs - 1) / (8 * g.vs);
-    long long at = 0;
-    for (int c = 0; c < 3; ++c) {
-        g.bw[c] = g.bh[c] = 0;
-        g.base[c] = at;
-        if (c < g.ncomp) {
-            g.bw[c] = mx * (c == 0 ? g.hs : 1);
-            g.bh[c] = my * (c == 0 ? g.vs : 1);
-            at += (long long)g.bw[c] * g.bh[c];
-        }
-    }
-    g.base[3] = at;
-    if (g.ncomp == 1) g.base[1] = g.base[2] = at;
-}
-
-void fill_info(const Parsed& p, int reason, mpn_jpeg_header* out) {
-    memset(out, 0, sizeof(*out));
-    out->width = p.width;
-    out->height = p.height;
-    out->components = p.ncomp;
-    out->h_samp = p.hs[0];
-    out->v_samp = p.vs[0];
-    out->restart_interval = p.restart;
-    out->supported = reason == MPN_JPEG_SUPPORTED;
-    out->reason = reason;
-    if (reason == MPN_JPEG_SUPPORTED) {
-        Geometry g;
-        geometry_of(p, g);
-        for (int c = 0; c < 3; ++c) {
-            out->blocks_w[c] = g.bw[c];
-            out->blocks_h[c] = g.bh[c];
-        }
-        out->total_blocks = g.base[3];
-        out->coef_bytes = g.base[3] * 128;
-    }
-}
+constexpr long long kMaxPixels = 1ll << 28;    // keeps every index of an image in 32 bits (a descriptor is checked on its own)
 
 // ------------------------------------------------------------------------------------------------ device
 struct DevGeometry {
@@ -451,122 +265,6 @@ __global__ void __launch_bounds__(kThreads) jpeg_colour_kernel(const Desc* __res
 
 // ------------------------------------------------------------------------------------------------ entry points
 extern "C" size_t mpn_jpeg_desc_bytes(void) { return sizeof(Desc); }
-
-extern "C" int mpn_jpeg_info(const uint8_t* data, size_t nbytes, mpn_jpeg_header* out) {
-    MPN_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_info: null pointer");
-    Parsed p;
-    const int reason = parse(data, nbytes, p);
-    fill_info(p, reason, out);
-    MPN_REQUIRE(reason != MPN_JPEG_MALFORMED, MPN_ERR_BAD_DATA, "jpeg_info: not a JPEG stream, or its headers are damaged");
-    return MPN_OK;
-}
-
-extern "C" int mpn_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, size_t coef_bytes, mpn_jpeg_desc* desc) {
-    MPN_REQUIRE(data && coefs && desc, MPN_ERR_BAD_ARG, "jpeg_entropy_decode: null pointer");
-    Parsed p;
-    const int reason = parse(data, nbytes, p);
-    MPN_REQUIRE(reason == MPN_JPEG_SUPPORTED, MPN_ERR_BAD_DATA, "jpeg_entropy_decode: stream not supported (reason %d, see MPN_JPEG_*)", reason);
-    Geometry g;
-    geometry_of(p, g);
-    const size_t need = (size_t)g.base[3] * 128;
-    MPN_REQUIRE(coef_bytes >= need, MPN_ERR_WORKSPACE, "jpeg_entropy_decode: coef_bytes %zu < %zu", coef_bytes, need);
-    HuffTable dc[3], ac[3];
-    for (int c = 0; c < g.ncomp; ++c) {
-        MPN_REQUIRE(build_table(p.hbits[0][p.td[c]], p.hvals[0][p.td[c]], dc[c]) && build_table(p.hbits[1][p.ta[c]], p.hvals[1][p.ta[c]], ac[c]),
-                    MPN_ERR_BAD_DATA, "jpeg_entropy_decode: a Huffman table is not a prefix code");
-    }
-    memset(coefs, 0, need);
-    Bits b = {data + p.scan_pos, data + nbytes, 0, 0, 0, false};
-    int pred[3] = {0, 0, 0};
-    const int mcus_x = g.bw[0] / g.hs;
-    const long long mcus = (long long)mcus_x * (g.bh[0] / g.vs);
-    int mx = 0, my = 0, until_restart = p.restart;
-    for (long long m = 0; m < mcus; ++m) {
-        if (p.restart && until_restart == 0) {
-            // a restart: the coder was flushed to a byte boundary and an RSTn marker follows (the reader stops in front of it)
-            MPN_REQUIRE(!b.overran(), MPN_ERR_BAD_DATA, "jpeg_entropy_decode: the scan ends before its restart interval does");
-            const uint8_t* q = b.p;
-            while (q + 1 < b.end && q[0] == 0xFF && q[1] == 0xFF) ++q;
-            MPN_REQUIRE(q + 1 < b.end && q[0] == 0xFF && q[1] >= 0xD0 && q[1] <= 0xD7, MPN_ERR_BAD_DATA,
-                        "jpeg_entropy_decode: restart marker missing");
-            b.p = q + 2;
-            b.buf = 0;
-            b.n = b.fake = 0;
-            b.stopped = false;
-            pred[0] = pred[1] = pred[2] = 0;
-            until_restart = p.restart;
-        }
-        for (int c = 0; c < g.ncomp; ++c) {
-            const int ch = c == 0 ? g.hs : 1, cv = c == 0 ? g.vs : 1;
-            for (int v = 0; v < cv; ++v) {
-                for (int h = 0; h < ch; ++h) {
-                    int16_t* out = coefs + (g.base[c] + (long long)(my * cv + v) * g.bw[c] + (mx * ch + h)) * 64;
-                    MPN_REQUIRE(decode_block(b, dc[c], ac[c], pred[c], out), MPN_ERR_BAD_DATA, "jpeg_entropy_decode: damaged entropy-coded data");
-                }
-            }
-        }
-        --until_restart;
-        if (++mx == mcus_x) {
-            mx = 0;
-            ++my;
-        }
-    }
-    MPN_REQUIRE(!b.overran(), MPN_ERR_BAD_DATA, "jpeg_entropy_decode: the scan ends before the image does");
-    memset(desc, 0, sizeof(*desc));
-    desc->width = p.width;
-    desc->height = p.height;
-    desc->components = g.ncomp;
-    desc->h_samp = g.hs;
-    desc->v_samp = g.vs;
-    desc->total_blocks = (int32_t)g.base[3];
-    for (int c = 0; c < g.ncomp; ++c) {
-        desc->blocks_w[c] = g.bw[c];
-        desc->blocks_h[c] = g.bh[c];
-        memcpy(desc->quant[c], p.q[p.tq[c]], sizeof(desc->quant[c]));
-    }
-    return MPN_OK;
-}
-
-// The marker scan as a descriptor for the device's entropy stage (jpeg_entropy.hip): headers only, the scan's bytes untouched.
-extern "C" size_t mpn_jpeg_scan_desc_bytes(void) { return sizeof(mpn_jpeg_scan_desc); }
-
-extern "C" int mpn_jpeg_scan_prepare(const uint8_t* data, size_t nbytes, mpn_jpeg_scan_desc* out) {
-    MPN_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_scan_prepare: null pointer");
-    Parsed p;
-    int reason = parse(data, nbytes, p);
-    if (reason == MPN_JPEG_SUPPORTED && nbytes > (size_t)MPN_JPEG_MAX_FILE_BYTES) reason = MPN_JPEG_TOO_LARGE;
-    memset(out, 0, sizeof(*out));
-    out->nbytes = (int64_t)nbytes;
-    out->width = p.width;
-    out->height = p.height;
-    out->components = p.ncomp;
-    out->h_samp = p.hs[0];
-    out->v_samp = p.vs[0];
-    out->restart_interval = p.restart;
-    out->supported = reason == MPN_JPEG_SUPPORTED;
-    out->reason = reason;
-    MPN_REQUIRE(reason != MPN_JPEG_MALFORMED, MPN_ERR_BAD_DATA, "jpeg_scan_prepare: not a JPEG stream, or its headers are damaged");
-    if (reason != MPN_JPEG_SUPPORTED) return MPN_OK;
-    Geometry g;
-    geometry_of(p, g);
-    out->scan_offset = (int64_t)p.scan_pos;
-    out->total_blocks = (int32_t)g.base[3];
-    for (int c = 0; c < g.ncomp; ++c) {
-        out->blocks_w[c] = g.bw[c];
-        out->blocks_h[c] = g.bh[c];
-        out->dc_table[c] = p.td[c];
-        out->ac_table[c] = p.ta[c];
-        memcpy(out->quant[c], p.q[p.tq[c]], sizeof(out->quant[c]));
-    }
-    for (int tc = 0; tc < 2; ++tc) {
-        for (int th = 0; th < 4; ++th) {
-            if (!p.hset[tc][th]) continue;
-            memcpy(out->huff_bits[tc][th], p.hbits[tc][th] + 1, 16);
-            memcpy(out->huff_vals[tc][th], p.hvals[tc][th], 256);
-        }
-    }
-    return MPN_OK;
-}
 
 extern "C" size_t mpn_jpeg_decode_workspace_bytes(int B, long long total_blocks) {
     if (B < 1 || total_blocks < B) return 0;

@@ -1,6 +1,5 @@
-// The host half of the JPEG entropy stages, shared by the sequential stage (jpeg.hip) and the multi-scan stage
-// (jpeg_scans.hip): the zigzag table, Huffman tables with a 9-bit lookahead, the bit reader and one sequential block.
-// Plain C++ (no HIP): a host-only program can include it.
+// What the JPEG host front end (jpeg_host.hip) decodes with: the zigzag table, Huffman tables with a 9-bit lookahead, the
+// bit reader and one sequential block. Plain C++ (no HIP): a host-only program can include it.
 #ifndef MPN_JPEG_HOST_H_
 #define MPN_JPEG_HOST_H_
 #include <stdint.h>

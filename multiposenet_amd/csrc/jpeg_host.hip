@@ -1,18 +1,28 @@
-// The multi-scan host stage of the JPEG decode: every scan of a file -> the raw coefficients mpn_jpeg_decode reads. It adds
-// what the one-scan stage (jpeg.hip: mpn_jpeg_entropy_decode) leaves to a library: progressive files (SOF2) of one, three or
-// four components, and baseline files of four (Adobe CMYK as Pillow writes it).
+// The host front end of the JPEG decode: ONE marker parser and ONE scan decoder behind every host entry point, in a file
+// that compiles as plain C++ (tools/jpeg_host_fuzz.sh builds it so, under ASan + UBSan). The device half is jpeg.hip.
 //
-//   mpn_jpeg_scans_info    marker scan up to the first scan: geometry of up to four components, route, reason
-//   mpn_jpeg_scans_decode  walks ALL markers of the file. Tables (DHT, DQT) and the restart interval (DRI) may change between
-//                          scans; a component's quantisation table is latched at its first scan (the library's rule). A scan
-//                          is one of five kinds - sequential, DC first, DC refinement, AC first, AC refinement (T.81 annex G,
-//                          the arithmetic of the library's jdphuff.c) - over interleaved MCUs or, with one component, over the
-//                          component's own ceil(w / 8) x ceil(h / 8) blocks. `bits[c][k]` holds the successive-approximation
-//                          position every coefficient has reached (-1: not seen): a scan must continue it exactly, and the
-//                          file must bring every coefficient to position 0.
+//   mpn_jpeg_info, mpn_jpeg_scan_prepare   walk(one_scan) up to the first scan: the verdict (supported / reason), and for
+//                                          the second the header descriptor of the device's entropy stage (jpeg_entropy.hip)
+//   mpn_jpeg_entropy_decode                walk(one_scan) + the one sequential interleaved scan -> raw int16 coefficients, 64
+//                                          per 8x8 block in natural order, one plane of blocks per component; nothing behind
+//                                          the scan is read
+//   mpn_jpeg_scans_info                    walk(all_scans) up to the first scan: up to four components, route, reason
+//   mpn_jpeg_scans_decode                  walk(all_scans) over ALL markers of the file -> the same coefficients. Tables
+//                                          (DHT, DQT) and the restart interval (DRI) may change between scans; a component's
+//                                          quantisation table is latched at its first scan (the library's rule). A scan is
+//                                          one of five kinds - sequential, DC first, DC refinement, AC first, AC refinement
+//                                          (T.81 annex G, the arithmetic of the library's jdphuff.c) - over interleaved MCUs
+//                                          or, with one component, over the component's own ceil(w / 8) x ceil(h / 8) blocks.
+//                                          `bits[c][k]` holds the successive-approximation position every coefficient has
+//                                          reached (-1: not seen): a scan must continue it exactly, and the file must bring
+//                                          every coefficient to position 0.
 //
-// Plain C++: no HIP call, no global, no allocation; every read is checked against `nbytes`, every block index is inside the
-// padded planes by construction. Thread-safe and re-entrant. (A program without the HIP runtime can compile this file as C++.)
+// The two policies read the same segments with the same readers and differ only in what they JUDGE (frame_reason,
+// one_scan_reason against scan_script / first-scan rules) and in where they stop: DESIGN.md, "JPEG host front end", lists
+// the inputs on which their verdicts part, and tests/golden/jpeg_host_verdicts.npz holds them fixed.
+//
+// No HIP call, no global, no allocation; every read is checked against `nbytes`, every block index is inside the padded
+// planes by construction. Thread-safe and re-entrant.
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
@@ -21,7 +31,7 @@
 
 void mpn_set_error(const char* fmt, ...);       // common.h (which needs the HIP headers; this file does not)
 
-#define SCANS_REQUIRE(cond, code, ...)     \
+#define HOST_REQUIRE(cond, code, ...)      \
     do {                                   \
         if (!(cond)) {                     \
             mpn_set_error(__VA_ARGS__);    \
@@ -33,11 +43,21 @@ namespace {
 
 using namespace mpn_jpeg_host;
 
-constexpr long long kMaxPixels = 1ll << 28;     // as the one-scan stage
+constexpr long long kMaxPixels = 1ll << 28;     // keeps every index of an image in 32 bits (the device checks the same bound)
 constexpr int kMaxScans = 100;                  // a script longer than this is refused (Pillow's own limit)
 
+enum Policy {
+    one_scan,       // baseline, one interleaved scan of one or three components: stops at (decodes only) the first scan
+    all_scans       // also progressive and four components: every scan of the file
+};
+
+struct Scan {
+    int ns, id[4], comp[4], td[4], ta[4];       // id: as the header names a component; comp: its index in the frame
+    int ss, se, ah, al;
+};
+
 struct Frame {
-    int width, height, ncomp;
+    int marker, precision, width, height, ncomp;
     bool progressive, sof, jfif, adobe, q16;
     int adobe_transform;
     int cid[4], hs[4], vs[4], tq[4];
@@ -46,37 +66,49 @@ struct Frame {
     long long base[5];
     int mcus_x, mcus_y;
     int restart;
-    uint16_t q[4][64];
+    uint16_t q[4][64];          // by table id, natural order
     bool qset[4];
+    uint16_t quant[4][64];      // by COMPONENT: its table as latched at its first decoded scan
     uint8_t hbits[2][4][17];
     uint8_t hvals[2][4][256];
     bool hset[2][4];
+    Scan first;                 // the first scan and the position of its first entropy-coded byte (once it is accepted)
+    size_t scan_pos;
 };
 
-// A frame header -> reason (MPN_JPEG_SUPPORTED: a frame this stage decodes, once the colour space is known at the first scan)
-int read_frame(int m, const uint8_t* s, size_t len, Frame& f) {
-    if (f.sof || len < 6) return MPN_JPEG_MALFORMED;
+// A frame header's fields -> false when the segment is damaged. What the frame is worth is frame_reason's business.
+bool read_frame(int m, const uint8_t* s, size_t len, Frame& f) {
+    if (f.sof || len < 6) return false;
     f.sof = true;
-    const int precision = s[0], nf = s[5];
+    f.marker = m;
+    f.precision = s[0];
     f.height = (s[1] << 8) | s[2];
     f.width = (s[3] << 8) | s[4];
-    f.ncomp = nf;
-    if (nf < 1 || len != 6 + 3 * (size_t)nf) return MPN_JPEG_MALFORMED;
+    const int nf = f.ncomp = s[5];
+    if (nf < 1 || len != 6 + 3 * (size_t)nf) return false;
     for (int i = 0; i < nf && i < 4; ++i) {
         f.cid[i] = s[6 + 3 * i];
         f.hs[i] = s[7 + 3 * i] >> 4;
         f.vs[i] = s[7 + 3 * i] & 15;
         f.tq[i] = s[8 + 3 * i];
     }
+    return true;
+}
+
+// The frame under a policy -> reason (MPN_JPEG_SUPPORTED: a frame the policy decodes, once the first scan is known; then
+// the block grids are laid out). The ORDER of the checks is part of what the entry points answer.
+int frame_reason(Frame& f, Policy policy) {
+    const int m = f.marker, nf = f.ncomp;
+    if (policy == one_scan && m == 0xC2) return MPN_JPEG_PROGRESSIVE;
     if (m >= 0xC9) return MPN_JPEG_ARITHMETIC;
-    if (m != 0xC0 && m != 0xC1 && m != 0xC2) return MPN_JPEG_FRAME_TYPE;
+    if (m != 0xC0 && m != 0xC1 && m != 0xC2) return MPN_JPEG_FRAME_TYPE;      // lossless, hierarchical
     f.progressive = m == 0xC2;
-    if (precision != 8) return MPN_JPEG_PRECISION;
-    if (f.width < 1 || f.height < 1) return MPN_JPEG_MALFORMED;
-    if (nf != 1 && nf != 3 && nf != 4) return MPN_JPEG_COMPONENTS;
+    if (f.precision != 8) return MPN_JPEG_PRECISION;
+    if (f.width < 1 || f.height < 1) return MPN_JPEG_MALFORMED;               // (height 0 = a DNL marker follows: not handled)
+    if (nf != 1 && nf != 3 && !(policy == all_scans && nf == 4)) return MPN_JPEG_COMPONENTS;
     for (int i = 0; i < nf; ++i) {
         if (f.hs[i] < 1 || f.hs[i] > 4 || f.vs[i] < 1 || f.vs[i] > 4 || f.tq[i] > 3) return MPN_JPEG_MALFORMED;
-        for (int j = 0; j < i; ++j) {
+        for (int j = 0; j < i && policy == all_scans; ++j) {     // (a scan of this policy finds its components by id)
             if (f.cid[j] == f.cid[i]) return MPN_JPEG_MALFORMED;
         }
     }
@@ -164,35 +196,52 @@ int colour_reason(const Frame& f) {
     return MPN_JPEG_SUPPORTED;
 }
 
-struct Scan {
-    int ns, comp[4], td[4], ta[4];
-    int ss, se, ah, al;
-};
-
-// The SOS header against the frame: false when it is damaged or names a script the standard does not allow
-bool read_scan(const uint8_t* s, size_t len, const Frame& f, Scan& sc) {
+// An SOS header's fields -> false when the segment does not have the shape of one
+bool read_scan(const uint8_t* s, size_t len, Scan& sc) {
     if (len < 1) return false;
     sc.ns = s[0];
-    if (sc.ns < 1 || sc.ns > 4 || sc.ns > f.ncomp || len != 4 + 2 * (size_t)sc.ns) return false;
+    if (sc.ns < 1 || sc.ns > 4 || len != 4 + 2 * (size_t)sc.ns) return false;
     for (int i = 0; i < sc.ns; ++i) {
-        int c = -1;
-        for (int j = 0; j < f.ncomp; ++j) {
-            if (f.cid[j] == s[1 + 2 * i]) c = j;
-        }
-        if (c < 0 || (i > 0 && c <= sc.comp[i - 1])) return false;         // components of a scan come in frame order
-        sc.comp[i] = c;
+        sc.id[i] = s[1 + 2 * i];
         sc.td[i] = s[2 + 2 * i] >> 4;
         sc.ta[i] = s[2 + 2 * i] & 15;
-        if (sc.td[i] > 3 || sc.ta[i] > 3) return false;
     }
     sc.ss = s[1 + 2 * sc.ns];
     sc.se = s[2 + 2 * sc.ns];
     sc.ah = s[3 + 2 * sc.ns] >> 4;
     sc.al = s[3 + 2 * sc.ns] & 15;
+    return true;
+}
+
+// all_scans: the scan against the frame -> false when it names a script the standard does not allow
+bool scan_script(const Frame& f, Scan& sc) {
+    if (sc.ns > f.ncomp) return false;
+    for (int i = 0; i < sc.ns; ++i) {
+        int c = -1;
+        for (int j = 0; j < f.ncomp; ++j) {
+            if (f.cid[j] == sc.id[i]) c = j;
+        }
+        if (c < 0 || (i > 0 && c <= sc.comp[i - 1])) return false;         // components of a scan come in frame order
+        sc.comp[i] = c;
+        if (sc.td[i] > 3 || sc.ta[i] > 3) return false;
+    }
     if (!f.progressive) return sc.ss == 0 && sc.se == 63 && sc.ah == 0 && sc.al == 0;
     if (sc.ss > sc.se || sc.se > 63 || sc.al > 13) return false;
     if (sc.ss == 0 ? sc.se != 0 : sc.ns != 1) return false;                  // DC alone, or a band of ONE component
     return sc.ah == 0 || sc.al == sc.ah - 1;
+}
+
+// one_scan: the first scan against the frame -> reason. It must be THE scan: every component, in the frame's order, with
+// its tables in place. (Again the order is part of the answer; all_scans leaves a missing table to the decode.)
+int one_scan_reason(const Frame& f, Scan& sc) {
+    if (sc.ns != f.ncomp) return MPN_JPEG_MULTISCAN;
+    for (int i = 0; i < sc.ns; ++i) {
+        if (sc.id[i] != f.cid[i] || sc.td[i] > 3 || sc.ta[i] > 3) return MPN_JPEG_MALFORMED;
+        if (!f.hset[0][sc.td[i]] || !f.hset[1][sc.ta[i]] || !f.qset[f.tq[i]]) return MPN_JPEG_MALFORMED;
+        sc.comp[i] = i;
+    }
+    if (sc.ss != 0 || sc.se != 63 || sc.ah != 0 || sc.al != 0) return MPN_JPEG_MALFORMED;
+    return colour_reason(f);
 }
 
 struct Coder {
@@ -302,9 +351,9 @@ inline bool ac_refine(Coder& k, const HuffTable& t, int ss, int se, int al, int1
 }
 
 // One scan's entropy-coded data from `pos` on. Returns "" or what is wrong; `pos` becomes where the reader stopped.
+template <bool sequential>
 const char* decode_scan(const uint8_t* data, size_t n, size_t& pos, const Frame& f, const Scan& sc, int16_t* coefs) {
     HuffTable dc[4], ac[4];
-    const bool sequential = !f.progressive;
     const bool need_dc = sequential || (sc.ss == 0 && sc.ah == 0), need_ac = sequential || sc.ss > 0;
     for (int i = 0; i < sc.ns; ++i) {
         if (need_dc && (!f.hset[0][sc.td[i]] || !build_table(f.hbits[0][sc.td[i]], f.hvals[0][sc.td[i]], dc[i]))) {
@@ -370,9 +419,10 @@ const char* decode_scan(const uint8_t* data, size_t n, size_t& pos, const Frame&
     return "";
 }
 
-// Walks the markers from the start. With coefs == nullptr it stops at the first scan (info); else it decodes every scan.
-// reason: MPN_JPEG_* of the file; on MPN_JPEG_SUPPORTED with coefs the planes are complete.
-int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, size_t coef_bytes, const char*& what) {
+// Walks the markers from the start under a policy. With coefs == nullptr it stops at the first scan (f.first, f.scan_pos);
+// else it decodes the first scan (one_scan) or every scan (all_scans). reason: MPN_JPEG_* of the file; on
+// MPN_JPEG_SUPPORTED with coefs the planes are complete and f.quant holds every component's table.
+int walk(Policy policy, const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, size_t coef_bytes, const char*& what) {
     memset(&f, 0, sizeof(f));
     reason = MPN_JPEG_MALFORMED;
     what = "not a JPEG stream, or its headers are damaged";
@@ -380,11 +430,9 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
     int8_t bits[4][64];                 // successive-approximation position reached; -1: not seen
     memset(bits, -1, sizeof(bits));
     bool latched[4] = {false, false, false, false};
-    uint16_t quant[4][64];
     int scans = 0;
-    bool eoi = false;
     size_t pos = 2;
-    while (!eoi) {
+    for (;;) {
         // the next marker: (after a scan) bytes that are not one are skipped, as the library does
         while (pos + 1 < n && !(data[pos] == 0xFF && data[pos + 1] != 0x00 && data[pos + 1] != 0xFF)) {
             if (scans == 0 && data[pos] != 0xFF) return MPN_ERR_BAD_DATA;      // in the headers a segment follows a segment
@@ -393,10 +441,7 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
         if (pos + 1 >= n) break;
         const int m = data[pos + 1];
         pos += 2;
-        if (m == 0xD9) {
-            eoi = true;
-            break;
-        }
+        if (m == 0xD9) break;
         if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
         if (m == 0xD8) return MPN_ERR_BAD_DATA;
         if (pos + 2 > n) return MPN_ERR_BAD_DATA;
@@ -410,10 +455,12 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
             return MPN_OK;
         }
         if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
-            reason = read_frame(m, s, len, f);
-            if (reason == MPN_JPEG_MALFORMED) return MPN_ERR_BAD_DATA;
-            if (reason != MPN_JPEG_SUPPORTED) return MPN_OK;
-            reason = MPN_JPEG_MALFORMED;
+            const int r = read_frame(m, s, len, f) ? frame_reason(f, policy) : MPN_JPEG_MALFORMED;
+            if (r == MPN_JPEG_MALFORMED) return MPN_ERR_BAD_DATA;
+            if (r != MPN_JPEG_SUPPORTED) {
+                reason = r;
+                return MPN_OK;
+            }
             continue;
         }
         if (m != 0xDA) {
@@ -421,22 +468,25 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
             continue;
         }
         // ---- a scan
-        if (!f.sof) return MPN_ERR_BAD_DATA;
         Scan sc;
-        if (!read_scan(s, len, f, sc)) {
+        if (!f.sof || !read_scan(s, len, sc)) return MPN_ERR_BAD_DATA;
+        int r = MPN_JPEG_SUPPORTED;
+        if (policy == one_scan) {
+            r = one_scan_reason(f, sc);
+        } else if (!scan_script(f, sc)) {
             what = "a scan header is damaged, or its script is not one the standard allows";
-            return MPN_ERR_BAD_DATA;
+            r = MPN_JPEG_MALFORMED;
+        } else if (scans == 0) {        // what is known at the first scan
+            r = !f.progressive && sc.ns != f.ncomp ? MPN_JPEG_MULTISCAN : colour_reason(f);
+        }
+        if (r == MPN_JPEG_MALFORMED) return MPN_ERR_BAD_DATA;
+        if (r != MPN_JPEG_SUPPORTED) {
+            reason = r;
+            return MPN_OK;
         }
         if (scans == 0) {
-            const int cr = colour_reason(f);
-            if (!f.progressive && sc.ns != f.ncomp) {
-                reason = MPN_JPEG_MULTISCAN;
-                return MPN_OK;
-            }
-            if (cr != MPN_JPEG_SUPPORTED) {
-                reason = cr;
-                return MPN_OK;
-            }
+            f.first = sc;
+            f.scan_pos = pos;
             if (!coefs) {
                 reason = MPN_JPEG_SUPPORTED;
                 return MPN_OK;
@@ -458,7 +508,7 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
                     what = "a quantisation table is missing";
                     return MPN_ERR_BAD_DATA;
                 }
-                memcpy(quant[c], f.q[f.tq[c]], sizeof(quant[c]));
+                memcpy(f.quant[c], f.q[f.tq[c]], sizeof(f.quant[c]));
                 latched[c] = true;
             }
             // the script: this scan continues, coefficient by coefficient, what the scans before it left
@@ -483,13 +533,14 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
                 bits[c][k] = (int8_t)sc.al;
             }
         }
-        const char* err = decode_scan(data, n, pos, f, sc, coefs);
+        const char* err = f.progressive ? decode_scan<false>(data, n, pos, f, sc, coefs) : decode_scan<true>(data, n, pos, f, sc, coefs);
         if (err[0]) {
             what = err;
             return MPN_ERR_BAD_DATA;
         }
+        if (policy == one_scan) break;  // its whole image; what follows the scan is never read
     }
-    if (!coefs || scans == 0) return MPN_ERR_BAD_DATA;          // no scan at all: damaged
+    if (scans == 0) return MPN_ERR_BAD_DATA;                    // no scan at all: damaged
     for (int c = 0; c < f.ncomp; ++c) {
         for (int k = 0; k < 64; ++k) {
             if (bits[c][k] != 0) {
@@ -498,24 +549,114 @@ int walk(const uint8_t* data, size_t n, Frame& f, int& reason, int16_t* coefs, s
             }
         }
     }
-    memcpy(f.q, quant, sizeof(quant));  // (from here on f.q[c] is COMPONENT c's latched table)
     reason = MPN_JPEG_SUPPORTED;
     return MPN_OK;
 }
 
-int route_of(const Frame& f, int reason) {
-    if (reason != MPN_JPEG_SUPPORTED) return MPN_JPEG_ROUTE_LIBRARY;
-    return !f.progressive && f.ncomp != 4 ? MPN_JPEG_ROUTE_DEVICE : MPN_JPEG_ROUTE_HOST_ENTROPY;
+// The geometry of a decoded frame and its (up to three) latched tables, for both decode entry points
+void fill_desc(const Frame& f, mpn_jpeg_desc* desc) {
+    memset(desc, 0, sizeof(*desc));
+    desc->width = f.width;
+    desc->height = f.height;
+    desc->components = f.ncomp;
+    desc->h_samp = f.hs[0];
+    desc->v_samp = f.vs[0];
+    desc->total_blocks = (int32_t)f.base[4];
+    for (int c = 0; c < f.ncomp && c < 3; ++c) {
+        desc->blocks_w[c] = f.bw[c];
+        desc->blocks_h[c] = f.bh[c];
+        memcpy(desc->quant[c], f.quant[c], sizeof(desc->quant[c]));
+    }
 }
 
 }  // namespace
 
-extern "C" int mpn_jpeg_scans_info(const uint8_t* data, size_t nbytes, mpn_jpeg_scans_header* out) {
-    SCANS_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_scans_info: null pointer");
+extern "C" int mpn_jpeg_info(const uint8_t* data, size_t nbytes, mpn_jpeg_header* out) {
+    HOST_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_info: null pointer");
     Frame f;
     int reason;
     const char* what;
-    const int rc = walk(data, nbytes, f, reason, nullptr, 0, what);
+    const int rc = walk(one_scan, data, nbytes, f, reason, nullptr, 0, what);
+    memset(out, 0, sizeof(*out));
+    out->width = f.width;
+    out->height = f.height;
+    out->components = f.ncomp;
+    out->h_samp = f.hs[0];
+    out->v_samp = f.vs[0];
+    out->restart_interval = f.restart;
+    out->supported = reason == MPN_JPEG_SUPPORTED;
+    out->reason = reason;
+    HOST_REQUIRE(rc == MPN_OK, rc, "jpeg_info: %s", what);
+    if (out->supported) {
+        for (int c = 0; c < f.ncomp; ++c) {
+            out->blocks_w[c] = f.bw[c];
+            out->blocks_h[c] = f.bh[c];
+        }
+        out->total_blocks = (int32_t)f.base[4];
+        out->coef_bytes = f.base[4] * 128;
+    }
+    return MPN_OK;
+}
+
+extern "C" int mpn_jpeg_entropy_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, size_t coef_bytes, mpn_jpeg_desc* desc) {
+    HOST_REQUIRE(data && coefs && desc, MPN_ERR_BAD_ARG, "jpeg_entropy_decode: null pointer");
+    Frame f;
+    int reason;
+    const char* what;
+    const int rc = walk(one_scan, data, nbytes, f, reason, coefs, coef_bytes, what);
+    HOST_REQUIRE(rc == MPN_OK, rc, "jpeg_entropy_decode: %s", what);
+    HOST_REQUIRE(reason == MPN_JPEG_SUPPORTED, MPN_ERR_BAD_DATA, "jpeg_entropy_decode: stream not supported (reason %d, see MPN_JPEG_*)", reason);
+    fill_desc(f, desc);
+    return MPN_OK;
+}
+
+// The marker scan as a descriptor for the device's entropy stage (jpeg_entropy.hip): headers only, the scan's bytes untouched.
+extern "C" size_t mpn_jpeg_scan_desc_bytes(void) { return sizeof(mpn_jpeg_scan_desc); }
+
+extern "C" int mpn_jpeg_scan_prepare(const uint8_t* data, size_t nbytes, mpn_jpeg_scan_desc* out) {
+    HOST_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_scan_prepare: null pointer");
+    Frame f;
+    int reason;
+    const char* what;
+    const int rc = walk(one_scan, data, nbytes, f, reason, nullptr, 0, what);
+    if (reason == MPN_JPEG_SUPPORTED && nbytes > (size_t)MPN_JPEG_MAX_FILE_BYTES) reason = MPN_JPEG_TOO_LARGE;
+    memset(out, 0, sizeof(*out));
+    out->nbytes = (int64_t)nbytes;
+    out->width = f.width;
+    out->height = f.height;
+    out->components = f.ncomp;
+    out->h_samp = f.hs[0];
+    out->v_samp = f.vs[0];
+    out->restart_interval = f.restart;
+    out->supported = reason == MPN_JPEG_SUPPORTED;
+    out->reason = reason;
+    HOST_REQUIRE(rc == MPN_OK, rc, "jpeg_scan_prepare: %s", what);
+    if (!out->supported) return MPN_OK;
+    out->scan_offset = (int64_t)f.scan_pos;
+    out->total_blocks = (int32_t)f.base[4];
+    for (int c = 0; c < f.ncomp; ++c) {
+        out->blocks_w[c] = f.bw[c];
+        out->blocks_h[c] = f.bh[c];
+        out->dc_table[c] = f.first.td[c];
+        out->ac_table[c] = f.first.ta[c];
+        memcpy(out->quant[c], f.q[f.tq[c]], sizeof(out->quant[c]));
+    }
+    for (int tc = 0; tc < 2; ++tc) {
+        for (int th = 0; th < 4; ++th) {
+            if (!f.hset[tc][th]) continue;
+            memcpy(out->huff_bits[tc][th], f.hbits[tc][th] + 1, 16);
+            memcpy(out->huff_vals[tc][th], f.hvals[tc][th], 256);
+        }
+    }
+    return MPN_OK;
+}
+
+extern "C" int mpn_jpeg_scans_info(const uint8_t* data, size_t nbytes, mpn_jpeg_scans_header* out) {
+    HOST_REQUIRE(data && out, MPN_ERR_BAD_ARG, "jpeg_scans_info: null pointer");
+    Frame f;
+    int reason;
+    const char* what;
+    const int rc = walk(all_scans, data, nbytes, f, reason, nullptr, 0, what);
     memset(out, 0, sizeof(*out));
     out->width = f.width;
     out->height = f.height;
@@ -524,8 +665,9 @@ extern "C" int mpn_jpeg_scans_info(const uint8_t* data, size_t nbytes, mpn_jpeg_
     out->v_samp = f.vs[0];
     out->progressive = f.progressive;
     out->reason = reason;
-    out->route = route_of(f, reason);
-    SCANS_REQUIRE(rc == MPN_OK, rc, "jpeg_scans_info: %s", what);
+    out->route = reason != MPN_JPEG_SUPPORTED ? MPN_JPEG_ROUTE_LIBRARY
+                 : !f.progressive && f.ncomp != 4 ? MPN_JPEG_ROUTE_DEVICE : MPN_JPEG_ROUTE_HOST_ENTROPY;
+    HOST_REQUIRE(rc == MPN_OK, rc, "jpeg_scans_info: %s", what);
     if (reason == MPN_JPEG_SUPPORTED) {
         for (int c = 0; c < f.ncomp; ++c) {
             out->blocks_w[c] = f.bw[c];
@@ -538,25 +680,14 @@ extern "C" int mpn_jpeg_scans_info(const uint8_t* data, size_t nbytes, mpn_jpeg_
 }
 
 extern "C" int mpn_jpeg_scans_decode(const uint8_t* data, size_t nbytes, int16_t* coefs, size_t coef_bytes, mpn_jpeg_desc* desc) {
-    SCANS_REQUIRE(data && coefs && desc, MPN_ERR_BAD_ARG, "jpeg_scans_decode: null pointer");
+    HOST_REQUIRE(data && coefs && desc, MPN_ERR_BAD_ARG, "jpeg_scans_decode: null pointer");
     Frame f;
     int reason;
     const char* what;
-    const int rc = walk(data, nbytes, f, reason, coefs, coef_bytes, what);
-    SCANS_REQUIRE(rc == MPN_OK, rc, "jpeg_scans_decode: %s", what);
-    SCANS_REQUIRE(reason == MPN_JPEG_SUPPORTED, MPN_ERR_BAD_DATA, "jpeg_scans_decode: stream not supported (reason %d, see MPN_JPEG_*)", reason);
-    memset(desc, 0, sizeof(*desc));
-    desc->width = f.width;
-    desc->height = f.height;
-    desc->components = f.ncomp;
-    desc->h_samp = f.hs[0];
-    desc->v_samp = f.vs[0];
-    desc->total_blocks = (int32_t)f.base[4];
-    for (int c = 0; c < f.ncomp && c < 3; ++c) {
-        desc->blocks_w[c] = f.bw[c];
-        desc->blocks_h[c] = f.bh[c];
-        memcpy(desc->quant[c], f.q[c], sizeof(desc->quant[c]));
-    }
+    const int rc = walk(all_scans, data, nbytes, f, reason, coefs, coef_bytes, what);
+    HOST_REQUIRE(rc == MPN_OK, rc, "jpeg_scans_decode: %s", what);
+    HOST_REQUIRE(reason == MPN_JPEG_SUPPORTED, MPN_ERR_BAD_DATA, "jpeg_scans_decode: stream not supported (reason %d, see MPN_JPEG_*)", reason);
+    fill_desc(f, desc);
     if (f.ncomp == 4) {
         // the descriptor holds three tables: the fourth component names the one of them it shares (Pillow and the usual
         // writers give all four one table)
@@ -564,10 +695,10 @@ extern "C" int mpn_jpeg_scans_decode(const uint8_t* data, size_t nbytes, int16_t
         desc->blocks_h3 = f.bh[3];
         desc->quant3 = -1;
         for (int c = 2; c >= 0; --c) {
-            if (memcmp(f.q[3], f.q[c], sizeof(f.q[3])) == 0) desc->quant3 = c;
+            if (memcmp(f.quant[3], f.quant[c], sizeof(f.quant[3])) == 0) desc->quant3 = c;
         }
-        SCANS_REQUIRE(desc->quant3 >= 0, MPN_ERR_BAD_DATA,
-                      "jpeg_scans_decode: stream not supported (the fourth component has a quantisation table of its own)");
+        HOST_REQUIRE(desc->quant3 >= 0, MPN_ERR_BAD_DATA,
+                     "jpeg_scans_decode: stream not supported (the fourth component has a quantisation table of its own)");
     }
     return MPN_OK;
 }

@@ -27,6 +27,8 @@ class _Header(ctypes.Structure):        # mpn_jpeg_header
                 ('supported', ctypes.c_int32), ('reason', ctypes.c_int32),
                 ('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3),
                 ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32), ('coef_bytes', ctypes.c_int64)]
+    INFO = "mpn_jpeg_info"
+    decodes = property(lambda h: bool(h.supported))     # mpn_jpeg_entropy_decode takes the stream
 
 
 class _ScansHeader(ctypes.Structure):   # mpn_jpeg_scans_header
@@ -35,6 +37,8 @@ class _ScansHeader(ctypes.Structure):   # mpn_jpeg_scans_header
                 ('route', ctypes.c_int32), ('reason', ctypes.c_int32),
                 ('blocks_w', ctypes.c_int32 * 4), ('blocks_h', ctypes.c_int32 * 4),
                 ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32), ('coef_bytes', ctypes.c_int64)]
+    INFO = "mpn_jpeg_scans_info"
+    decodes = property(lambda h: h.route != 2)          # mpn_jpeg_scans_decode takes the stream
 
 
 ROUTES = ('device', 'host-entropy', 'pillow')       # MPN_JPEG_ROUTE_*
@@ -78,17 +82,26 @@ def _as_bytes(data):
     return bytes(data)
 
 
+def _header(h, data):
+    """The info call of the header struct `h` into it; damaged headers raise ValueError."""
+    _lib.check(getattr(_lib.lib(), h.INFO)(data, len(data), ctypes.byref(h)))
+    return h
+
+
+def _header_dict(h, **own):
+    """What both header structs hold, and the fields `own` of one of them."""
+    return {'width': h.width, 'height': h.height, 'components': h.components, 'sampling': (h.h_samp, h.v_samp), **own,
+            'reason': REASONS[h.reason],
+            'blocks': [(h.blocks_h[c], h.blocks_w[c]) for c in range(min(h.components, len(h.blocks_w)))] if h.decodes else [],
+            'total_blocks': h.total_blocks, 'coef_bytes': h.coef_bytes}
+
+
 def jpeg_info(data):
     """The header of a JPEG as a dict: 'width', 'height', 'components', 'sampling' (h, v) of the first component,
     'restart_interval', 'supported' (bool), 'reason' (one of REASONS), 'blocks' [(blocks_h, blocks_w)] per component,
     'total_blocks', 'coef_bytes'. A stream whose headers are damaged raises ValueError."""
-    data = _as_bytes(data)
-    h = _Header()
-    _lib.check(_lib.lib().mpn_jpeg_info(data, len(data), ctypes.byref(h)))
-    return {'width': h.width, 'height': h.height, 'components': h.components, 'sampling': (h.h_samp, h.v_samp),
-            'restart_interval': h.restart_interval, 'supported': bool(h.supported), 'reason': REASONS[h.reason],
-            'blocks': [(h.blocks_h[c], h.blocks_w[c]) for c in range(min(h.components, 3))] if h.supported else [],
-            'total_blocks': h.total_blocks, 'coef_bytes': h.coef_bytes}
+    h = _header(_Header(), _as_bytes(data))
+    return _header_dict(h, restart_interval=h.restart_interval, supported=bool(h.supported))
 
 
 class Coefficients:
@@ -109,33 +122,31 @@ class Coefficients:
         return out
 
 
+def _host_stage(name, h, data):
+    """The info call of `h`, then mpn_jpeg_<name> into a buffer of the size the header reports -> Coefficients."""
+    data = _as_bytes(data)
+    _header(h, data)
+    if not h.decodes:
+        raise ValueError(f"{name}: stream not supported ({REASONS[h.reason]})")
+    coefs = np.empty((h.total_blocks, 64), np.int16)
+    desc = np.zeros(1, DESC)
+    _lib.check(getattr(_lib.lib(), "mpn_jpeg_" + name)(data, len(data), coefs.ctypes.data_as(ctypes.c_void_p), coefs.nbytes,
+                                                       desc.ctypes.data_as(ctypes.c_void_p)))
+    return Coefficients((h.height, h.width, 3), coefs, desc)
+
+
 def entropy_decode(data):
     """The host stage on one SUPPORTED JPEG -> Coefficients. Raises ValueError for a stream that is damaged, truncated or
     outside the supported set (`jpeg_info(data)['supported']`)."""
-    data = _as_bytes(data)
-    lib = _lib.lib()
-    h = _Header()
-    _lib.check(lib.mpn_jpeg_info(data, len(data), ctypes.byref(h)))
-    if not h.supported:
-        raise ValueError(f"entropy_decode: stream not supported ({REASONS[h.reason]})")
-    coefs = np.empty((h.total_blocks, 64), np.int16)
-    desc = np.zeros(1, DESC)
-    _lib.check(lib.mpn_jpeg_entropy_decode(data, len(data), coefs.ctypes.data_as(ctypes.c_void_p), coefs.nbytes,
-                                           desc.ctypes.data_as(ctypes.c_void_p)))
-    return Coefficients((h.height, h.width, 3), coefs, desc)
+    return _host_stage("entropy_decode", _Header(), data)
 
 
 def scans_info(data):
     """The header of a JPEG as the multi-scan host stage sees it: 'width', 'height', 'components', 'sampling', 'progressive'
     (bool), 'route' (one of ROUTES), 'reason' (one of REASONS: why the route is 'pillow', else 'supported'), 'blocks'
     [(blocks_h, blocks_w)] of up to four components, 'total_blocks', 'coef_bytes'. Damaged headers raise ValueError."""
-    data = _as_bytes(data)
-    h = _ScansHeader()
-    _lib.check(_lib.lib().mpn_jpeg_scans_info(data, len(data), ctypes.byref(h)))
-    return {'width': h.width, 'height': h.height, 'components': h.components, 'sampling': (h.h_samp, h.v_samp),
-            'progressive': bool(h.progressive), 'route': ROUTES[h.route], 'reason': REASONS[h.reason],
-            'blocks': [(h.blocks_h[c], h.blocks_w[c]) for c in range(min(h.components, 4))] if h.route != 2 else [],
-            'total_blocks': h.total_blocks, 'coef_bytes': h.coef_bytes}
+    h = _header(_ScansHeader(), _as_bytes(data))
+    return _header_dict(h, progressive=bool(h.progressive), route=ROUTES[h.route])
 
 
 def jpeg_support(data):
@@ -148,17 +159,7 @@ def jpeg_support(data):
 def scans_decode(data):
     """The multi-scan host stage on one JPEG whose route is 'host-entropy' or 'device' -> Coefficients (four planes for CMYK).
     Raises ValueError for a file that is damaged, truncated, incomplete or on the 'pillow' route."""
-    data = _as_bytes(data)
-    lib = _lib.lib()
-    h = _ScansHeader()
-    _lib.check(lib.mpn_jpeg_scans_info(data, len(data), ctypes.byref(h)))
-    if h.route == 2:
-        raise ValueError(f"scans_decode: stream not supported ({REASONS[h.reason]})")
-    coefs = np.empty((h.total_blocks, 64), np.int16)
-    desc = np.zeros(1, DESC)
-    _lib.check(lib.mpn_jpeg_scans_decode(data, len(data), coefs.ctypes.data_as(ctypes.c_void_p), coefs.nbytes,
-                                         desc.ctypes.data_as(ctypes.c_void_p)))
-    return Coefficients((h.height, h.width, 3), coefs, desc)
+    return _host_stage("scans_decode", _ScansHeader(), data)
 
 
 class Scan:
@@ -174,16 +175,22 @@ class Scan:
         return int(self.desc[0]['total_blocks'])
 
 
+def _scan(data):
+    """mpn_jpeg_scan_prepare -> (return code, reason, the Scan of a SUPPORTED stream or None)."""
+    desc = np.zeros(1, SCAN_DESC)
+    rc = _lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p))
+    d = desc[0]
+    return rc, REASONS[int(d['reason'])], Scan(data, (int(d['height']), int(d['width']), 3), desc) if rc == 0 and d['supported'] else None
+
+
 def scan_prepare(data):
     """The header stage on one SUPPORTED JPEG -> Scan. Raises ValueError for a stream whose headers are damaged or that is
     outside the supported set."""
-    data = _as_bytes(data)
-    desc = np.zeros(1, SCAN_DESC)
-    _lib.check(_lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p)))
-    d = desc[0]
-    if not d['supported']:
-        raise ValueError(f"scan_prepare: stream not supported ({REASONS[int(d['reason'])]})")
-    return Scan(data, (int(d['height']), int(d['width']), 3), desc)
+    rc, reason, scan = _scan(_as_bytes(data))
+    _lib.check(rc)
+    if scan is None:
+        raise ValueError(f"scan_prepare: stream not supported ({reason})")
+    return scan
 
 
 def pillow_decode(data):
@@ -215,15 +222,12 @@ def prepare(item, entropy='host', extended=False):
         return item
     data = _as_bytes(item)
     if entropy == 'device':
-        desc = np.zeros(1, SCAN_DESC)
-        rc = _lib.lib().mpn_jpeg_scan_prepare(data, len(data), desc.ctypes.data_as(ctypes.c_void_p))
-        if rc == 0 and desc[0]['supported']:
-            return Scan(data, (int(desc[0]['height']), int(desc[0]['width']), 3), desc)
-        return _extended(data) if extended else pillow_decode(data)
-    h = _Header()
-    rc = _lib.lib().mpn_jpeg_info(data, len(data), ctypes.byref(h))
-    if rc == 0 and h.supported:
-        return entropy_decode(data)
+        entry = _scan(data)[2]
+    else:
+        h = _Header()
+        entry = entropy_decode(data) if _lib.lib().mpn_jpeg_info(data, len(data), ctypes.byref(h)) == 0 and h.supported else None
+    if entry is not None:
+        return entry
     return _extended(data) if extended else pillow_decode(data)
 
 
@@ -256,23 +260,9 @@ class JpegBatchDecoder:
         self.fallbacks = 0                  # Scan entries of the last `decode` that took the host entropy stage
         self.staged_bytes = 0               # bytes the last `decode` uploaded
         self.records = None                 # ENTROPY_RECORD per Scan entry of the last `decode`
-        self._stage = self._dev = self._work = None
-        self._scan = {}                     # buffers of the device entropy stage, by name
+        self._buf = {}                      # grow-only buffers, by name
         self.scan_layout = None
         self._done = None
-
-    def _ensure(self, stage_bytes, work_bytes):
-        import torch
-        grow_stage = self._stage is None or self._stage.numel() < stage_bytes
-        grow_work = self._work is None or self._work.numel() < work_bytes
-        if (grow_stage and self._stage is not None) or (grow_work and self._work is not None):
-            torch.cuda.synchronize(self.device)     # (rare) growth: no queued copy or launch still uses the old buffers
-        if grow_stage:
-            n = _capacity(stage_bytes)
-            self._stage = torch.empty(n, dtype=torch.uint8).pin_memory()
-            self._dev = torch.empty(n, dtype=torch.uint8, device=self.device)
-        if grow_work:
-            self._work = torch.empty(_capacity(work_bytes), dtype=torch.uint8, device=self.device)
 
     @staticmethod
     def plan(entries, offsets):
@@ -306,14 +296,41 @@ class JpegBatchDecoder:
     def _buffer(self, name, nbytes, pinned=False):
         """A uint8 buffer of at least nbytes that grows to the largest batch seen."""
         import torch
-        have = self._scan.get(name)
+        have = self._buf.get(name)
         if have is None or have.numel() < nbytes:
             if have is not None:
                 torch.cuda.synchronize(self.device)             # (rare) growth: no queued copy or launch still uses the old buffer
             n = _capacity(nbytes)
             have = torch.empty(n, dtype=torch.uint8).pin_memory() if pinned else torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._scan[name] = have
+            self._buf[name] = have
         return have
+
+    def _staging(self, name, nbytes):
+        """The pinned staging buffer `name`, free to be written: the previous batch's copy has left it."""
+        if self._done is not None:
+            self._done.synchronize()
+        return self._buffer(name, nbytes, pinned=True)
+
+    def _ship(self, stage, dev, n, kind, items, decode_args, sources, stream, entropy=False):
+        """Writes `items` - (descriptor record of dtype `kind`, the caller's offsets {field: value}, payload as uint8, its
+        position) - into the staging, queues the copy of its first n bytes to `dev` and behind it (the device's entropy stage
+        and) mpn_jpeg_decode over the items: decode_args = (coefs, coef_bytes, descs, work buffer)."""
+        import torch
+        host = stage.numpy()
+        descs = host[:len(items) * kind.itemsize].view(kind)
+        for k, (record, own, payload, at) in enumerate(items):
+            descs[k] = record
+            for field, value in own.items():
+                descs[k][field] = value
+            host[at:at + payload.size] = payload
+        with torch.cuda.stream(stream):
+            dev[:n].copy_(stage[:n], non_blocking=True)
+            if entropy:
+                self.entropy_launch(stream)
+            if items:
+                coefs, coef_bytes, dev_descs, work = decode_args
+                _lib.call("mpn_jpeg_decode", coefs, coef_bytes, dev_descs, len(items), _lib.ptr(sources), sources.numel(),
+                          _lib.ptr(work), work.numel(), ctypes.c_void_p(stream.cuda_stream))
 
     @staticmethod
     def plan_scans(scans, offsets, file_order=None):
@@ -344,12 +361,12 @@ class JpegBatchDecoder:
     def entropy_launch(self, stream=None):
         """mpn_jpeg_entropy_decode_device over the Scan entries `decode_scans` staged last, on `stream` (default: the current
         one). No host synchronisation: what `decode_scans` queues, and what a benchmark times."""
-        lay, buf = self.scan_layout, self._scan
-        base = buf['dev'].data_ptr()
+        lay, buf = self.scan_layout, self._buf
+        base = buf['scan_dev'].data_ptr()
         st = _lib.stream_ptr() if stream is None else ctypes.c_void_p(stream.cuda_stream)
         _lib.call("mpn_jpeg_entropy_decode_device", ctypes.c_void_p(base + lay['file_base']), lay['files_bytes'], ctypes.c_void_p(base),
-                  len(lay['file_at']), _lib.ptr(buf['coefs']), buf['coefs'].numel(), _lib.ptr(buf['descs']), _lib.ptr(buf['records']),
-                  _lib.ptr(buf['work']), buf['work'].numel(), self.max_passes, st)
+                  len(lay['file_at']), _lib.ptr(buf['scan_coefs']), buf['scan_coefs'].numel(), _lib.ptr(buf['scan_descs']),
+                  _lib.ptr(buf['records']), _lib.ptr(buf['entropy_work']), buf['entropy_work'].numel(), self.max_passes, st)
 
     def decode_scans(self, scans, sources, offsets, stream, file_order=None):
         """Entropy stage and inverse DCT of the Scan entries on the device, then the wait for their records (`.records`);
@@ -359,28 +376,18 @@ class JpegBatchDecoder:
         import torch
         lay = self.scan_layout = self.plan_scans(scans, offsets, file_order)
         b, n = len(scans), lay['stage_bytes']
-        lib = _lib.lib()
-        ent_work = lib.mpn_jpeg_entropy_decode_device_workspace_bytes(b, lay['files_bytes'])
+        ent_work = _lib.lib().mpn_jpeg_entropy_decode_device_workspace_bytes(b, lay['files_bytes'])
         if ent_work == 0:
             raise ValueError(f"decode: a batch of {b} files in {lay['files_bytes']} bytes is outside what mpn_jpeg_entropy_decode_device takes")
-        stage, dev = self._buffer('stage', n, pinned=True), self._buffer('dev', n)
-        coefs, planes = self._buffer('coefs', lay['coef_bytes']), self._buffer('planes', max(lay['work_bytes'], 64))
-        descs_out, records = self._buffer('descs', b * DESC_BYTES), self._buffer('records', b * ENTROPY_RECORD_BYTES)
-        record_host, work = self._buffer('record_host', b * ENTROPY_RECORD_BYTES, pinned=True), self._buffer('work', ent_work)
-        host = stage.numpy()
-        descs = host[:b * SCAN_DESC_BYTES].view(SCAN_DESC)
-        for k, (e, off) in enumerate(zip(scans, offsets)):
-            descs[k] = e.desc[0]
-            d = descs[k]
-            d['file_offset'], d['coef_offset'], d['src_offset'], d['work_offset'] = lay['file_at'][k], lay['coef_at'][k], off, lay['work_at'][k]
-            at = lay['file_base'] + lay['file_at'][k]
-            host[at:at + len(e.data)] = np.frombuffer(e.data, np.uint8)
+        stage, dev = self._staging('scan_stage', n), self._buffer('scan_dev', n)
+        coefs, planes = self._buffer('scan_coefs', lay['coef_bytes']), self._buffer('scan_planes', max(lay['work_bytes'], 64))
+        descs_out, records = self._buffer('scan_descs', b * DESC_BYTES), self._buffer('records', b * ENTROPY_RECORD_BYTES)
+        record_host = self._buffer('record_host', b * ENTROPY_RECORD_BYTES, pinned=True)
+        self._buffer('entropy_work', ent_work)
+        items = [(e.desc[0], {'file_offset': lay['file_at'][k], 'coef_offset': lay['coef_at'][k], 'src_offset': off, 'work_offset': lay['work_at'][k]},
+                  np.frombuffer(e.data, np.uint8), lay['file_base'] + lay['file_at'][k]) for k, (e, off) in enumerate(zip(scans, offsets))]
+        self._ship(stage, dev, n, SCAN_DESC, items, (_lib.ptr(coefs), coefs.numel(), _lib.ptr(descs_out), planes), sources, stream, entropy=True)
         with torch.cuda.stream(stream):
-            dev[:n].copy_(stage[:n], non_blocking=True)
-            st = ctypes.c_void_p(stream.cuda_stream)
-            self.entropy_launch(stream)
-            _lib.call("mpn_jpeg_decode", _lib.ptr(coefs), coefs.numel(), _lib.ptr(descs_out), b, _lib.ptr(sources), sources.numel(),
-                      _lib.ptr(planes), planes.numel(), st)
             record_host[:b * ENTROPY_RECORD_BYTES].copy_(records[:b * ENTROPY_RECORD_BYTES], non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
@@ -396,7 +403,7 @@ class JpegBatchDecoder:
         """The device's coefficients of Scan entry k of the last batch, int16 [total_blocks, 64] on the host (tests, tools)."""
         lay = self.scan_layout
         end = lay['coef_at'][k + 1] if k + 1 < len(lay['coef_at']) else lay['coef_bytes']
-        return self._scan['coefs'][lay['coef_at'][k]:end].cpu().numpy().view(np.int16).reshape(-1, 64)
+        return self._buf['scan_coefs'][lay['coef_at'][k]:end].cpu().numpy().view(np.int16).reshape(-1, 64)
 
     def decode(self, entries, sources, offsets, stream=None):
         import torch
@@ -411,11 +418,9 @@ class JpegBatchDecoder:
                 raise ValueError(f"decode: an image of {shape} at byte {off} does not fit a buffer of {total} bytes")
         self.fallbacks = self.staged_bytes = 0
         self.records = None
+        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         sc = [i for i, e in enumerate(entries) if isinstance(e, Scan)]
         if sc:
-            stream = stream if stream is not None else torch.cuda.current_stream(self.device)
-            if self._done is not None:
-                self._done.synchronize()                        # the previous batch's copy has left the staging
             bad = self.decode_scans([entries[i] for i in sc], sources, [offsets[i] for i in sc], stream)
             self.fallbacks = len(bad)
             redo = {sc[k]: entropy_decode(entries[sc[k]].data) for k in bad}     # (raises ValueError for a damaged stream)
@@ -424,34 +429,20 @@ class JpegBatchDecoder:
                 return
             entries, offsets = [redo.get(i, entries[i]) for i in keep], [offsets[i] for i in keep]
         jp, px, lay = self.plan(entries, offsets)
-        if self._done is not None:
-            self._done.synchronize()                            # the previous batch's copy has left the staging
-        self._ensure(lay['stage_bytes'], max(lay['work_bytes'], 64))
-        stage = self._stage.numpy()
-        if jp:
-            descs = stage[:len(jp) * DESC_BYTES].view(DESC)
-            for k, i in enumerate(jp):
-                e = entries[i]
-                descs[k] = e.desc[0]
-                descs[k]['src_offset'], descs[k]['coef_offset'], descs[k]['work_offset'] = offsets[i], lay['coef_at'][k], lay['work_at'][k]
-                at = lay['coef_base'] + lay['coef_at'][k]
-                stage[at:at + e.coefs.nbytes] = e.coefs.reshape(-1).view(np.uint8)
-        for k, i in enumerate(px):
-            e = entries[i]
-            stage[lay['pix_at'][k]:lay['pix_at'][k] + e.size] = e.reshape(-1)
-        stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         n = lay['stage_bytes']
+        stage, dev, work = self._staging('stage', n), self._buffer('dev', n), self._buffer('work', max(lay['work_bytes'], 64))
+        for k, i in enumerate(px):
+            stage.numpy()[lay['pix_at'][k]:lay['pix_at'][k] + entries[i].size] = entries[i].reshape(-1)
+        items = [(entries[i].desc[0], {'src_offset': offsets[i], 'coef_offset': lay['coef_at'][k], 'work_offset': lay['work_at'][k]},
+                  entries[i].coefs.reshape(-1).view(np.uint8), lay['coef_base'] + lay['coef_at'][k]) for k, i in enumerate(jp)]
         self.staged_bytes += n
+        base = dev.data_ptr()
+        self._ship(stage, dev, n, DESC, items, (ctypes.c_void_p(base + lay['coef_base']), lay['coef_bytes'], ctypes.c_void_p(base), work),
+                   sources, stream)
         with torch.cuda.stream(stream):
-            self._dev[:n].copy_(self._stage[:n], non_blocking=True)
-            if jp:
-                base = self._dev.data_ptr()
-                _lib.call("mpn_jpeg_decode", ctypes.c_void_p(base + lay['coef_base']), lay['coef_bytes'], ctypes.c_void_p(base),
-                          len(jp), _lib.ptr(sources), total, _lib.ptr(self._work), self._work.numel(),
-                          ctypes.c_void_p(stream.cuda_stream))
             for k, i in enumerate(px):
                 at, size = lay['pix_at'][k], entries[i].size
-                sources[offsets[i]:offsets[i] + size].copy_(self._dev[at:at + size], non_blocking=True)
+                sources[offsets[i]:offsets[i] + size].copy_(dev[at:at + size], non_blocking=True)
             self._done = torch.cuda.Event()
             self._done.record(stream)
 

@@ -88,3 +88,36 @@ def test_a_descriptor_that_does_not_fit_is_refused_on_the_host(cuda):
         dec.decode([entry], sources, [16])
     with pytest.raises(ValueError, match="multiple of 16"):
         dec.decode([entry], torch.zeros(48 * 64 * 3 + 64, dtype=torch.uint8, device=cuda), [8])
+
+
+def test_a_larger_second_batch_grows_every_buffer_behind_a_queued_first(cuda):
+    """One decoder, a batch of one 8x8 image (1 KB of staging), then - with no synchronise in between - a batch of all three
+    kinds of entry that outgrows the staging, its device copy, the inverse-DCT planes and the device's coefficient buffer:
+    replacing a buffer must wait for the work that is still queued on it. Both batches equal Pillow's pixels.
+    What this holds is the decoder's bookkeeping of its buffers across growth: the buffers of the Scan path are first
+    allocations here, not growth, and an allocator that recycles freed blocks in stream order can hide a missing synchronise."""
+    g = goldens()
+    dec = J.JpegBatchDecoder(cuda)
+    small = g["8x8_444"][1]
+    first = torch.full((16 + small.size + 16,), SENTINEL, dtype=torch.uint8, device=cuda)
+    dec.decode([J.prepare(g["8x8_444"][0])], first, [16])
+    before = {name: buf.numel() for name, buf in dec._buf.items()}
+    assert before == {'stage': 1024, 'dev': 1024, 'work': 256} and dec.staged_bytes == 896
+    array = np.random.RandomState(11).randint(0, 256, (17, 17, 3)).astype(np.uint8)
+    entries = [J.prepare(g["120x160_420"][0]), J.prepare(g["37x53_422_rst_blocks"][0], entropy='device'), array]
+    assert [type(e) for e in entries] == [J.Coefficients, J.Scan, np.ndarray]
+    wants = [g["120x160_420"][1], g["37x53_422_rst_blocks"][1], array]
+    offsets = [16, 16 + 57616, 16 + 57616 + 5904]              # 120 * 160 * 3 = 57600, 37 * 53 * 3 = 5883, each + a gap
+    second = torch.full((offsets[2] + array.size + 16,), SENTINEL, dtype=torch.uint8, device=cuda)
+    dec.decode(entries, second, offsets)
+    torch.cuda.synchronize()
+    assert all(dec._buf[name].numel() > n for name, n in before.items())
+    assert dec._buf['scan_coefs'].numel() >= entries[1].total_blocks * 128 and dec.fallbacks == 0
+    host = first.cpu().numpy()
+    np.testing.assert_array_equal(host[16:16 + small.size].reshape(small.shape), small)
+    assert (host[:16] == SENTINEL).all() and (host[16 + small.size:] == SENTINEL).all()
+    host, outside = second.cpu().numpy(), np.ones(second.numel(), bool)
+    for w, off in zip(wants, offsets):
+        np.testing.assert_array_equal(host[off:off + w.size].reshape(w.shape), w)
+        outside[off:off + w.size] = False
+    assert (host[outside] == SENTINEL).all(), "bytes outside the images were written"

@@ -187,6 +187,36 @@ def test_damaged_streams_return_an_error_or_a_complete_output():
     assert seen['error'] > 50 and seen['complete'] > 50, seen
 
 
+def test_host_entry_points_reproduce_the_frozen_verdicts():
+    """Every host entry point answers the corpus of make_jpeg_host_verdicts.py (87 files, 501 inputs each: the file, 400
+    replacements in its headers, 60 anywhere, 40 prefixes) as tests/golden/jpeg_host_verdicts.npz recorded it before the
+    one-scan and the multi-scan parser became one: return codes, verdicts, and a CRC32 of every output a call defines.
+    The corpus must keep its point: the inputs on which the two policies part ("JPEG host front end") are 16.7 %
+    of it as recorded, and at least 10 % are asked for. (The slowest host test: 43 587 inputs through five calls each,
+    about 10 s on 8 cores; the counts are what keeps 200+ header mutations per file.)"""
+    import make_jpeg_host_verdicts as M
+    with np.load(os.path.join(os.path.dirname(GOLDEN), "jpeg_host_verdicts.npz")) as z:
+        want = {k: z[k] for k in ('names', 'rc', 'verdict', 'crc')}
+    got = M.run()
+    names = [str(n) for n in want['names']]
+    assert [str(n) for n in got['names']] == names and want['crc'].shape == (len(names), M.PER_FILE)
+
+    def where(key, labels):
+        """The first inputs whose `key` is not the recorded one: file, mutation index, entry point, recorded -> now."""
+        out = []
+        for at in np.argwhere(got[key] != want[key])[:8]:
+            f, m = int(at[0]), int(at[1])
+            which = labels[at[2]] if len(at) == 3 else "outputs of " + ", ".join(e for e, r in zip(M.ENTRY_POINTS, got['rc'][f, m]) if r == 0)
+            out.append(f"{names[f]}, mutation {m}, {which}: {want[key][tuple(at)]} -> {got[key][tuple(at)]}")
+        return "\n".join(out)
+
+    assert (got['rc'] == want['rc']).all(), where('rc', M.ENTRY_POINTS)
+    assert (got['verdict'] == want['verdict']).all(), where('verdict', M.VERDICTS)
+    assert (got['crc'] == want['crc']).all(), where('crc', None)
+    share = M.differ(want['rc'], want['verdict']).mean()
+    assert share >= 0.10, share
+
+
 def test_eight_threads_equal_the_serial_result():
     g = goldens()
     names = [c[0] for c in supported_cases()] * 8

@@ -76,11 +76,11 @@ def device_leg(jpegs, iters):
     dec.decode(entries, sources, offsets)                   # stages coefficients and descriptors on the device
     torch.cuda.synchronize()
     _, _, lay = dec.plan(entries, offsets)
-    base = dec._dev.data_ptr()
+    base = dec._buf['dev'].data_ptr()
 
     def launch():
         _lib.call("mpn_jpeg_decode", ctypes.c_void_p(base + lay['coef_base']), lay['coef_bytes'], ctypes.c_void_p(base), len(entries),
-                  _lib.ptr(sources), sources.numel(), _lib.ptr(dec._work), dec._work.numel(), _lib.stream_ptr())
+                  _lib.ptr(sources), sources.numel(), _lib.ptr(dec._buf['work']), dec._buf['work'].numel(), _lib.stream_ptr())
     for _ in range(20):
         launch()
     torch.cuda.synchronize()

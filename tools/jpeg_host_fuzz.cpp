@@ -1,13 +1,13 @@
-// Memory-safety check of the multi-scan JPEG host stage (csrc/jpeg_scans.hip: mpn_jpeg_scans_info, mpn_jpeg_scans_decode),
-// meant to be built with -fsanitize=address,undefined and run on the CPU: tools/jpeg_scans_fuzz.sh does both. It links
-// nothing but that one source, compiled as plain C++.
+// Memory-safety check of the JPEG host front end (csrc/jpeg_host.hip: mpn_jpeg_info, mpn_jpeg_entropy_decode,
+// mpn_jpeg_scan_prepare, mpn_jpeg_scans_info, mpn_jpeg_scans_decode), meant to be built with -fsanitize=address,undefined and
+// run on the CPU: tools/jpeg_host_fuzz.sh does both. It links nothing but that one source, compiled as plain C++.
 //
-//   jpeg_scans_fuzz FILE...      the first three FILEs are also fed as every one of their prefixes
+//   jpeg_host_fuzz FILE...      the first three FILEs are also fed as every one of their prefixes
 //
-// Inputs: every file as it is (it must decode, unless its name holds "damaged_": then it may be refused); every prefix of the first three; kCorruptions single-byte corruptions of files
-// drawn with the seeded generator below. The input bytes and the coefficient buffer are heap blocks of exactly nbytes and
-// coef_bytes, so a read or a write one byte outside either is an AddressSanitizer report. Exit status 0 = every call
-// returned MPN_OK or a documented error.
+// Inputs: every file as it is (it must decode, unless its name holds "damaged_": then it may be refused); every prefix of
+// the first three; kCorruptions single-byte corruptions of files drawn with the seeded generator below. The input bytes, the
+// coefficient buffers and every struct an entry point fills are heap blocks of exactly their size, so a read or a write one
+// byte outside any of them is an AddressSanitizer report. Exit status 0 = every call returned MPN_OK or a documented error.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -36,23 +36,39 @@ uint64_t next(uint64_t& s) {                    // xorshift64
     return s;
 }
 
-// One input through both entry points. Returns false on a return code the header does not document.
+template <class T>
+T* block() { return (T*)malloc(sizeof(T)); }       // an exact-size block: writing past the struct is a report
+
+// One input through the five entry points. Returns false on a return code the header does not document, or when the
+// one-scan and the multi-scan view of a file both decode and disagree about its size.
 bool feed(const uint8_t* bytes, size_t n, Tally& t, bool must_decode) {
     uint8_t* data = (uint8_t*)malloc(n ? n : 1);        // an exact-size block: reading past n is a report
     memcpy(data, bytes, n);
-    mpn_jpeg_scans_header h;
-    int rc = mpn_jpeg_scans_info(data, n, &h);
+    mpn_jpeg_header* one = block<mpn_jpeg_header>();
+    mpn_jpeg_scan_desc* prepared = block<mpn_jpeg_scan_desc>();
+    mpn_jpeg_scans_header* h = block<mpn_jpeg_scans_header>();
+    mpn_jpeg_desc* desc = block<mpn_jpeg_desc>();
+    int rc = mpn_jpeg_info(data, n, one);
     bool fine = rc == MPN_OK || rc == MPN_ERR_BAD_DATA;
-    if (rc == MPN_OK && h.route != MPN_JPEG_ROUTE_LIBRARY) {
-        int16_t* coefs = (int16_t*)malloc((size_t)h.coef_bytes);
-        mpn_jpeg_desc desc;
-        rc = mpn_jpeg_scans_decode(data, n, coefs, (size_t)h.coef_bytes, &desc);
-        fine = rc == MPN_OK || rc == MPN_ERR_BAD_DATA;
+    if (rc == MPN_OK && one->supported) {
+        int16_t* coefs = (int16_t*)malloc((size_t)one->coef_bytes);
+        rc = mpn_jpeg_entropy_decode(data, n, coefs, (size_t)one->coef_bytes, desc);
+        fine = fine && (rc == MPN_ERR_BAD_DATA || (rc == MPN_OK && desc->width == one->width && desc->total_blocks == one->total_blocks));
+        free(coefs);
+    }
+    rc = mpn_jpeg_scan_prepare(data, n, prepared);
+    fine = fine && (rc == MPN_ERR_BAD_DATA || (rc == MPN_OK && (!prepared->supported || (size_t)prepared->scan_offset <= n)));
+    rc = mpn_jpeg_scans_info(data, n, h);
+    fine = fine && (rc == MPN_OK || rc == MPN_ERR_BAD_DATA);
+    if (rc == MPN_OK && h->route != MPN_JPEG_ROUTE_LIBRARY) {
+        int16_t* coefs = (int16_t*)malloc((size_t)h->coef_bytes);
+        rc = mpn_jpeg_scans_decode(data, n, coefs, (size_t)h->coef_bytes, desc);
         if (rc == MPN_OK) {
             ++t.ok;
-            fine = desc.width == h.width && desc.height == h.height && desc.total_blocks == h.total_blocks;
+            fine = fine && desc->width == h->width && desc->height == h->height && desc->total_blocks == h->total_blocks;
         } else {
             ++t.refused;
+            fine = fine && rc == MPN_ERR_BAD_DATA;
         }
         free(coefs);
     } else if (rc == MPN_OK) {
@@ -60,6 +76,10 @@ bool feed(const uint8_t* bytes, size_t n, Tally& t, bool must_decode) {
     } else {
         ++t.refused;
     }
+    free(desc);
+    free(h);
+    free(prepared);
+    free(one);
     free(data);
     return fine && (!must_decode || rc == MPN_OK);
 }
@@ -82,7 +102,7 @@ int main(int argc, char** argv) {
         files.push_back(b);
     }
     if ((int)files.size() < kPrefixFiles) {
-        fprintf(stderr, "usage: jpeg_scans_fuzz FILE FILE FILE [FILE...]\n");
+        fprintf(stderr, "usage: jpeg_host_fuzz FILE FILE FILE [FILE...]\n");
         return 2;
     }
     Tally whole, prefixes, corrupted;
