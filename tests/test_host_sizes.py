@@ -88,3 +88,42 @@ def test_decode_render_and_l2_workspaces():
     n = (ctypes.c_longlong * 3)(5521492, 1 << 33, 7)
     assert lib.mpn_l2_loss_batched_workspace_bytes(3, n) > 0
     assert lib.mpn_gemm_nt_num_parts(56 * 36 * 17) > 0
+
+
+# (N, H, W, C, stride) -> mpn_dwconv_num_parts, mpn_dwconv_bwd_data_bn_num_parts, mpn_dwconv_wgrad_num_parts,
+# mpn_dwconv_bwd_fused_supported, mpn_dwconv_bwd_data_add_supported; the same in bf16 and f32. Recorded at 256 compute units
+# (the count the library assumes without a device, and the MI355X's). The nine bench layers, then the corners of the geometry: the
+# 1 x 1 stride-2 map (the one stride-2 shape whose output is as large as its input), maps narrower than a block, odd sizes, the
+# 24-channel maps that take the LDS-tile weight gradient, the strip heights of 64 / 32 rows, and a wide one-row stride-2 map.
+DWCONV_GEOMETRY = {
+    (32, 256, 256, 32, 1): (768, 1024, 512, 1, 0),
+    (32, 256, 256, 64, 2): (1024, 1024, 1024, 1, 1),
+    (32, 128, 128, 128, 1): (768, 1024, 512, 1, 0),
+    (32, 128, 128, 128, 2): (512, 512, 512, 1, 1),
+    (32, 64, 64, 256, 1): (384, 256, 256, 1, 0),
+    (32, 64, 64, 256, 2): (256, 256, 256, 1, 1),
+    (32, 32, 32, 512, 1): (128, 128, 128, 1, 0),
+    (32, 32, 32, 512, 2): (64, 128, 128, 1, 1),
+    (32, 16, 16, 1024, 1): (32, 32, 32, 1, 0),
+    (1, 1, 1, 16, 2): (1, 0, 1, 0, 0),
+    (1, 1, 5, 8, 2): (1, 0, 1, 0, 0),
+    (2, 7, 1, 64, 2): (2, 0, 2, 0, 0),
+    (1, 9, 7, 64, 1): (1, 1, 1, 1, 0),
+    (1, 9, 7, 64, 2): (1, 0, 1, 0, 0),
+    (1, 70, 33, 128, 1): (15, 9, 9, 1, 0),
+    (1, 14, 10, 24, 1): (1, 0, 2, 0, 0),
+    (1, 14, 10, 24, 2): (1, 0, 2, 0, 0),
+    (1, 130, 70, 32, 1): (18, 10, 6, 1, 0),
+    # a one-row stride-2 map wider than a block: 300 output columns, 128 lanes of one column each -> 3 column blocks. (The weight gradient used to take
+    # H == OH for stride 1 here: it counted 2 and left the right part of the row out.)
+    (1, 1, 600, 8, 2): (3, 0, 3, 0, 0),
+}
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+def test_dwconv_launch_geometry_table(dtype):
+    lib = L()
+    fns = ("mpn_dwconv_num_parts", "mpn_dwconv_bwd_data_bn_num_parts", "mpn_dwconv_wgrad_num_parts",
+           "mpn_dwconv_bwd_fused_supported", "mpn_dwconv_bwd_data_add_supported")
+    got = {shape: tuple(getattr(lib, f)(*shape, dtype) for f in fns) for shape in DWCONV_GEOMETRY}
+    assert got == DWCONV_GEOMETRY

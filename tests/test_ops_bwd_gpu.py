@@ -59,7 +59,9 @@ def test_conv_wgrad(cuda, dtype, case):
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)
 @pytest.mark.parametrize("N,H,W,C,stride", [(2, 16, 16, 32, 1), (2, 16, 16, 64, 2), (1, 12, 20, 128, 1), (1, 14, 10, 256, 2),
                                             (1, 9, 7, 64, 2), (2, 8, 8, 1024, 1), (1, 32, 32, 512, 2),
-                                            (1, 9, 7, 64, 1), (2, 5, 13, 32, 1), (1, 70, 33, 128, 1)])   # odd widths, strips of 64 rows
+                                            (1, 9, 7, 64, 1), (2, 5, 13, 32, 1), (1, 70, 33, 128, 1),   # odd widths, strips of 64 rows
+                                            (1, 1, 1, 16, 2),     # the one stride-2 map whose output is as large as its input
+                                            (1, 1, 600, 8, 2)])   # one row, stride 2, three column blocks: every column reaches the weight gradient
 def test_dwconv_backward(cuda, dtype, N, H, W, C, stride):
     ops = _ops()
     rs = np.random.RandomState(C + stride)
