@@ -1337,6 +1337,43 @@ size_t mpn_jpeg_entropy_encode_workspace_bytes(long long total_blocks, long long
 int mpn_jpeg_entropy_encode(const int16_t* coefs, size_t coef_bytes, const void* descs, int B, uint8_t* out, size_t out_bytes,
                             void* records, void* work, size_t work_bytes, mpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Test-time augmentation of the joint inference graph: heatmaps averaged over the image, its mirror and further input sizes,
+ * on the device (multiposenet_amd/inference/detector.py: flip=, scales=). tests/tta_ref.py restates both in numpy float32;
+ * the kernels equal it bit for bit.
+ *
+ *   mpn_mirror_images   in, out uint8 [n,h,w,3], DIFFERENT buffers: out[i,y,x,:] = in[i,y,w-1-x,:]. Any n, h, w >= 1 with
+ *                       n*h*w < 2^31 (MPN_ERR_BAD_SHAPE).
+ *   mpn_tta_merge       sources: num_sources (1 .. MPN_TTA_MAX_SOURCES) mpn_tta_source in HOST memory, read before the
+ *                       launch and passed to the kernel by value: heat f32 [B,h,w,17] (sigmoid heatmaps) and seg f32 [B,h,w]
+ *                       (the raw mask channel), DEVICE, of the same B images at the source's own size h x w.
+ *                       heat_out f32 [B,h0,w0,17], seg_out f32 [B,h0,w0], no source's buffer. Per output value, every
+ *                       operation a separately rounded IEEE f32 operation, nothing contracted:
+ *                         un-mirror  element (y, x, c) of a mirrored source's map is heat[y, w-1-x, FLIP_ORDER[c]] and
+ *                                    seg[y, w-1-x]; FLIP_ORDER = 0, 2,1, 4,3, ..., 16,15 (keypoint_augment.FLIP_ORDER)
+ *                         resize     of that un-mirrored map to h0 x w0, bilinear, half-pixel centres, clamped edges:
+ *                                    sy = (y + 0.5f) * ((float)h / (float)h0) - 0.5f clamped to [0, h-1], y0 = floor(sy),
+ *                                    y1 = min(y0+1, h-1), fy = sy - y0; the same along x; top = a00 + (a01 - a00) * fx,
+ *                                    bot = a10 + (a11 - a10) * fx, v = top + (bot - top) * fy. A source with h == h0 and
+ *                                    w == w0 is read directly.
+ *                         average    sum = v_0, then sum = sum + v_k for k = 1, 2, ... in the order given;
+ *                                    out = sum / (float)num_sources.
+ *                       Checked before the launch: null pointers, num_sources, a source that is an output (MPN_ERR_BAD_ARG);
+ *                       B, h0, w0, h, w >= 1, B*h0*w0*18 and every B*h*w*17 < 2^31 (MPN_ERR_BAD_SHAPE).
+ * One launch each; grid and block sizes depend on the shapes alone, so the calls can be captured.
+ */
+#define MPN_TTA_MAX_SOURCES 8
+typedef struct mpn_tta_source {
+    const float* heat;
+    const float* seg;
+    int32_t h, w;
+    int32_t mirrored;                           /* non-zero: the maps of the mirrored input */
+    int32_t reserved;
+} mpn_tta_source;
+int mpn_mirror_images(const uint8_t* in, int n, int h, int w, uint8_t* out, mpn_stream_t stream);
+int mpn_tta_merge(const mpn_tta_source* sources, int num_sources, int B, int h0, int w0, float* heat_out, float* seg_out,
+                  mpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

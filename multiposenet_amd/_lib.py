@@ -175,6 +175,8 @@ SIGNATURES = {
     "mpn_jpeg_forward": (_I, [_P, _Z, _P, _I, _P, _Z, _P]),
     "mpn_jpeg_entropy_encode_workspace_bytes": (_Z, [_L, _L]),
     "mpn_jpeg_entropy_encode": (_I, [_P, _Z, _P, _I, _P, _Z, _P, _P, _Z, _P]),
+    "mpn_mirror_images": (_I, [_P, _I, _I, _I, _P, _P]),
+    "mpn_tta_merge": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

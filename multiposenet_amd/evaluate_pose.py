@@ -3,13 +3,15 @@
     python -m multiposenet_amd.evaluate_pose --val-dataset DIR | --annotations JSON --images DIR
         [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32]
         [--batch 16] [--size W H] [--keep-aspect-ratio] [--score-threshold 0.05] [--score box|box*keypoints] [--out FILE]
+        [--flip] [--scales W H [W H ...]]
 
 --val-dataset: TFRecord shards of the keypoint contract (input_pipeline/tfrecord.py; tools/make_toy_tfrecords.py writes toy
 ones). Their JPEG bytes go through `Detector.predict_jpegs`, their persons become the ground truth
 (`pose_metrics.groundtruth_from_record`: box areas, no dropped persons - a yardstick between runs, not the official number).
 --annotations / --images: COCO's person_keypoints_*.json and the directory of its JPEG files; COCO's own areas and crowds.
 The matching runs inside the Detector's captured graph (`groundtruth=`); the ten numbers are printed and appended to --out
-as one JSON line. Without a model file the weights are seeded random ones: the numbers then only show that the path runs."""
+as one JSON line. --flip and --scales are the Detector's test-time augmentation (`flip=`, `scales=`): heatmaps averaged on the
+device over the mirror image and over further input sizes of --size's aspect ratio. Without a model file the weights are seeded random ones: the numbers then only show that the path runs."""
 import argparse
 import json
 import os
@@ -65,11 +67,21 @@ def main(argv=None):
     ap.add_argument("--score-threshold", type=float, default=0.05)
     ap.add_argument("--score", choices=("box", "box*keypoints"), default="box")
     ap.add_argument("--out", default="pose_eval.jsonl")
+    ap.add_argument("--flip", action="store_true", help="average the heatmaps with those of the mirror image")
+    ap.add_argument("--scales", type=int, nargs="+", default=[], metavar="N", help="further network input sizes: W H [W H ...]")
     args = ap.parse_args(argv)
     if bool(args.val_dataset) == bool(args.annotations):
         ap.error("give --val-dataset DIR, or --annotations JSON with --images DIR")
     if args.annotations and not args.images:
         ap.error("--annotations needs --images DIR")
+    if len(args.scales) % 2:
+        ap.error("--scales takes pairs: W H [W H ...]")
+    scales = [(args.scales[i], args.scales[i + 1]) for i in range(0, len(args.scales), 2)]
+    from .inference.detector import check_tta
+    try:
+        check_tta(args.flip, scales, args.size[1], args.size[0])
+    except ValueError as e:
+        ap.error(str(e))
 
     import torch
     from .inference import Detector
@@ -86,15 +98,18 @@ def main(argv=None):
     images = persons = 0
     for jpegs, gts in batches:
         outs = det.predict_jpegs(jpegs, size=(args.size[1], args.size[0]), keep_aspect_ratio=args.keep_aspect_ratio,
-                                 score_threshold=args.score_threshold, groundtruth=gts)
+                                 score_threshold=args.score_threshold, groundtruth=gts, flip=args.flip, scales=scales)
         evaluator.update(outs, gts)
         images += len(jpegs)
         persons += sum(len(o["scores"]) for o in outs)
     stats = evaluator.evaluate()
+    if args.flip or scales:
+        print(f"[evaluate_pose] test-time augmentation: flip {args.flip}, scales {scales}")
     for name in STAT_NAMES:
         print(f"{name:5s} {stats[name]:.4f}")
     line = dict(stats, images=images, detections=persons, groundtruth=int(evaluator.num_groundtruth[0]), dtype=args.dtype,
-                size=list(args.size), keep_aspect_ratio=args.keep_aspect_ratio, score_threshold=args.score_threshold, score=args.score)
+                size=list(args.size), keep_aspect_ratio=args.keep_aspect_ratio, score_threshold=args.score_threshold, score=args.score,
+                flip=args.flip, scales=[list(s) for s in scales])
     with open(args.out, "a") as f:
         f.write(json.dumps(line) + "\n")
     print(json.dumps(line))

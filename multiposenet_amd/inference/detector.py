@@ -13,7 +13,7 @@ import torch
 from .. import _lib
 from .. import pose_metrics
 from ..net import KeypointNet
-from . import draw, jpeg, maps, resample
+from . import draw, jpeg, maps, resample, tta
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -82,6 +82,34 @@ def check_plot_maps(plot_maps, heatmap_outputs):
     return bool(plot_maps)
 
 
+def check_tta(flip, scales, height, width):
+    """The `flip` and `scales` arguments of the predict_* methods for a height x width network input -> the tail of the
+    entry's key: () for a plain call, else ('tta', flip, ((W_k, H_k), ...)). scales: at most tta.MAX_SCALES further network
+    input sizes (width, height), multiples of 128 with the base's aspect ratio, each once and none the base itself."""
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError(f"flip must be False or True (got {flip!r})")
+    sizes = []
+    for s in (() if scales is None else scales):
+        try:
+            wk, hk = (int(v) for v in s)
+        except (TypeError, ValueError):
+            raise ValueError(f"a scale must be (width, height) (got {s!r})")
+        if wk < 128 or hk < 128 or wk % 128 or hk % 128:
+            raise ValueError(f"a scale must be positive multiples of 128 (got {wk} x {hk})")
+        if wk * height != hk * width:
+            raise ValueError(f"scale {wk} x {hk} has another aspect ratio than the {width} x {height} base")
+        if (wk, hk) == (width, height):
+            raise ValueError(f"scale {wk} x {hk} is the base size itself")
+        if (wk, hk) in sizes:
+            raise ValueError(f"scale {wk} x {hk} is given twice")
+        sizes.append((wk, hk))
+    if len(sizes) > tta.MAX_SCALES:
+        raise ValueError(f"at most {tta.MAX_SCALES} extra scales are merged in one launch (got {len(sizes)})")
+    if not flip and not sizes:
+        return ()
+    return ('tta', bool(flip), tuple(sizes))
+
+
 def _encode_plan(sizes, src_offsets, jp):
     """The encode of the annotated frames where mpn_draw_detections writes them (RGBA, draw.layout's offsets)."""
     _, frames, _ = draw.layout(sizes, src_offsets)
@@ -97,10 +125,11 @@ class _Entry:
     """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
     input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
-    ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
+    entry (a tta.Buffers), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -296,7 +325,7 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None):
+                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -322,6 +351,17 @@ class Detector:
                 truth (`pose_metrics.PoseEvaluator.update` takes the dicts as they are), made by one mpn_oks_match launch
                 behind the gather inside the captured graph - a graph of its own per (b, height, width, threshold,
                 self.oks_score, self.oks_max_dets) that follows each call's ground truth; every other key is unchanged.
+            flip: True averages every image's heatmaps and mask with those of its mirror image (test-time augmentation): the
+                backbone and the keypoint subnet run once over 2b images, the second half mirrored on the device; the mirror's
+                maps are un-mirrored (columns reversed, left / right keypoint channels swapped) and ONE mpn_tta_merge launch
+                averages them into the maps that the PRN, plot_maps, 'keypoint_heatmaps' and 'segmentation_masks' then read.
+                Boxes come from the unmirrored pass alone. A graph of its own; the averaged maps never leave the device
+                unless return_heatmaps asks for them.
+            scales: a list of at most 3 further network input sizes (width, height), multiples of 128 with the images' aspect
+                ratio: the batch is resized to each on the device (mpn_image_resize: Pillow's bicubic), backbone and subnet
+                run at that size (over the mirrors too with flip), and the maps are resized to the base size (bilinear,
+                half-pixel centres) and averaged in the same launch, in the order base, base mirrored, scale 1, scale 1
+                mirrored, ... (include/mpn.h states the arithmetic). Part of the graph's key, like flip.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
@@ -330,7 +370,7 @@ class Detector:
         b, h, w = check_batch(images)
         thr = float(score_threshold)
         oks = self._check_groundtruth(groundtruth, b)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w))
         if oks:
             ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
         if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
@@ -341,10 +381,17 @@ class Detector:
         else:
             for i, im in enumerate(images):
                 stage[i] = im
-        ent.x.copy_(ent.stage, non_blocking=True)                   # ONE host-to-device copy
+        ent.x[:b].copy_(ent.stage, non_blocking=True)               # ONE host-to-device copy
         outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps,
-                                                              oks=ent.oks))
+                                                              oks=ent.oks, aug=ent.tta))
         return self._finish(ent, outs, b, return_heatmaps)
+
+    def _check_tta(self, flip, scales, h, w):
+        """check_tta for this Detector: averaging heatmaps needs the keypoint subnet's heatmap head."""
+        key = check_tta(flip, scales, h, w)
+        if key and not self._has_heatmaps():
+            raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
+        return key
 
     def _check_groundtruth(self, groundtruth, b):
         """The `groundtruth` argument of the predict_* methods -> () or the tail of the entry's key."""
@@ -413,22 +460,23 @@ class Detector:
                 p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=()):
-        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks]): pinned staging, the device input, fixed drawing and
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=()):
+        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks][, tta]): pinned staging, the device input (with the
+        mirrors behind the batch and the inputs of the extra scales for a check_tta key), fixed drawing and
         encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
         if annotate:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
         if plot_maps:
             key += ('maps',)
-        key += oks
+        key += oks + tta_key
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
             return ent
         dev = self.net.device
-        ent = _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory(),
-                     x=torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev))
+        ent = _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory())
+        self._place_input(ent, b, h, w, tta_key)
         if annotate:                                                # the frames are the batch itself: fixed descriptors
             ent.draw = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
             ent.draw.place(*_batch_frames(b, h, w))
@@ -444,8 +492,16 @@ class Detector:
         store[key] = ent
         return ent
 
+    def _place_input(self, ent, b, h, w, tta_key):
+        """The device input of a new entry: uint8 [b, h, w, 3], or the tta.Buffers of a check_tta key and their base input."""
+        if tta_key:
+            ent.tta = tta.Buffers(tta_key[1], tta_key[2], b, h, w, self.net.device)
+            ent.x = ent.tta.x
+        else:
+            ent.x = torch.empty((b, h, w, 3), dtype=torch.uint8, device=self.net.device)
+
     def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None,
-                           oks=None):
+                           oks=None, aug=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
@@ -454,12 +510,25 @@ class Detector:
         place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'.
         plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
         oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
-        the record in the same buffer, so that they reach the host in the record's copy."""
+        the record in the same buffer, so that they reach the host in the record's copy.
+        aug (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
+        mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
+        launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
         net = self.net
+        if aug is not None and aug.flip:
+            tta.mirror_images(x[:aug.b], x[aug.b:])
+        heat, seg, feats = self._keypoint_pass(x)
+        if aug is not None:
+            b = aug.b
+            sources = self._tta_sources(heat, seg, aug)
+            for xk, meta, work in aug.scales:
+                aug.fill(x, xk, meta, work)
+                sources += self._tta_sources(*self._keypoint_pass(xk)[:2], aug)
+            heat, seg = aug.heat, aug.seg
+            tta.merge(sources, heat, seg)
+            x = x[:b]                                               # N is the outermost axis: contiguous prefixes
+            feats = {k: (raw[:b], aff) for k, (raw, aff) in feats.items()}
         b, h, w, _ = x.shape
-        bufs = net._buffers(b, h, w)
-        feats = net.backbone_forward(x, False, bufs)
-        heat, seg = net.subnet_forward(feats, False, bufs, inference_outputs=True)
         dev = {'heat': heat, 'seg': seg}
         if plotter is not None:
             dev['maps'] = plotter.launch(x, heat, seg, normalise=True)
@@ -497,6 +566,21 @@ class Detector:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
         return self._encode_frames(dev, encode)
 
+    def _keypoint_pass(self, x):
+        """Backbone and keypoint subnet over a uint8 batch: (sigmoid heatmaps, mask, backbone features)."""
+        net = self.net
+        n, h, w, _ = x.shape
+        bufs = net._buffers(n, h, w)
+        feats = net.backbone_forward(x, False, bufs)
+        heat, seg = net.subnet_forward(feats, False, bufs, inference_outputs=True)
+        return heat, seg, feats
+
+    @staticmethod
+    def _tta_sources(heat, seg, aug):
+        """The merge sources of one pass: its first b images plain, then (flip) its second b images as mirrored maps."""
+        b = aug.b
+        return [(heat[:b], seg[:b], False)] + ([(heat[b:], seg[b:], True)] if aug.flip else [])
+
     @staticmethod
     def _encode_frames(dev, encode):
         if encode is not None:
@@ -506,7 +590,8 @@ class Detector:
 
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
-                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None):
+                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
+                       flip=False, scales=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -527,6 +612,9 @@ class Detector:
             jpeg_quality, jpeg_subsampling: as for `predict_batch`.
             plot_maps: as for `predict_batch`; the picture shows the network's input, the resized CANVAS (padding included).
             groundtruth: as for `predict_batch`, in the pixels of the SOURCE images (where 'keypoints' are returned).
+            flip, scales: as for `predict_batch`, of the network CANVAS: its mirror (with keep_aspect_ratio the padding then
+                lies on the other side) and the canvas resized to each (width, height) of `scales`, which have the aspect
+                ratio of `size` - not the source frames resized again.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -537,6 +625,7 @@ class Detector:
         items = resample.check_images(images)
         height, width = resample.check_size(size)
         plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
+        tta_key = self._check_tta(flip, scales, height, width)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -544,12 +633,13 @@ class Detector:
                 stage[at:at + im.size] = im.reshape(-1)
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
-        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth)
+        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
+                                     tta_key)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None):
+                      groundtruth=None, flip=False, scales=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -566,6 +656,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
+            flip, scales: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -581,6 +672,7 @@ class Detector:
         infos = [jpeg.jpeg_info(j) for j in items]
         height, width = resample.check_size(size)
         plan = resample.Plan([(i['height'], i['width']) for i in infos], height, width, keep_aspect_ratio, align=16)
+        tta_key = self._check_tta(flip, scales, height, width)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -591,17 +683,18 @@ class Detector:
                 ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
             self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
-        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth)
+        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
+                                     tta_key)
 
     def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False,
-                         groundtruth=None):
+                         groundtruth=None, tta_key=()):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
         one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
         b, thr = plan.b, float(score_threshold)
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
         oks = self._check_groundtruth(groundtruth, b)
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks)
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
@@ -618,21 +711,22 @@ class Detector:
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=()):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=(), tta_key=()):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
         exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
         output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
         capacity also covers the encoder's coefficients, streams and workspace. plot_maps: an entry of its own with a
-        MapPlotter for the canvas batch. oks (groundtruth=): an entry of its own with the ground-truth buffers."""
+        MapPlotter for the canvas batch. oks (groundtruth=): an entry of its own with the ground-truth buffers. tta_key (flip=,
+        scales=): an entry of its own whose canvas batch has the mirrors behind it, with the inputs of the extra scales."""
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
         base = ('images', b, h, w, thr)
         tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
         if plot_maps:
             tail += ('maps',)
-        tail += oks
+        tail += oks + tta_key
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -652,8 +746,8 @@ class Detector:
                      sources=torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
                      meta_stage=torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
                      meta=torch.zeros(meta_words, dtype=torch.int32, device=dev),
-                     work=torch.empty(work_bytes, dtype=torch.uint8, device=dev),
-                     x=torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev))
+                     work=torch.empty(work_bytes, dtype=torch.uint8, device=dev))
+        self._place_input(ent, b, h, w, tta_key)
         if annotate:
             ent.draw = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
         if eplan:
@@ -669,13 +763,14 @@ class Detector:
     def _device_side_images(self, ent, thr):
         """mpn_image_resize (ragged sources -> the uint8 canvas batch) -> _device_side_batch with mpn_pose_gather_sized last."""
         x, meta = ent.x, ent.meta
-        b, h, w, _ = x.shape
+        _, h, w, _ = x.shape
+        b = ent.tta.b if ent.tta is not None else x.shape[0]
         extent = meta[b * resample.DESC_WORDS:b * (resample.DESC_WORDS + 4)].view(torch.float32).view(b, 4)
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
         return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps,
-                                       oks=ent.oks)
+                                       oks=ent.oks, aug=ent.tta)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)
