@@ -820,6 +820,63 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
                   mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Person identities across the frames of a video: the record's persons of every frame are matched greedily against the
+ * tracks the earlier frames left, one block per stream.
+ *
+ *   mpn_pose_track   record: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place exactly as
+ *                     mpn_oks_match reads it (the header's total and counts, clamped the same way; only rows 0 .. total-1;
+ *                     of a row its box, score and keypoints).
+ *                   Streams: B = streams * F. Stream s owns images s*F .. s*F+F-1 in time order: one camera with a batch of
+ *                     consecutive frames is streams = 1, B cameras with one frame each is streams = B. Ids are per stream.
+ *                   PURE: the launch reads prev and writes the COMPLETE new state to next and the rows to out; it never
+ *                     writes prev, and running it twice in a row gives the same bytes. The caller advances the state by
+ *                     copying next over prev behind the launch (a few KB). A capture / replay front end runs its device
+ *                     side eagerly and then replays it on an entry's first call; an in-place update would count every track
+ *                     twice there. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   State, prev and next, mpn_pose_track_state_bytes(streams, max_tracks) bytes DEVICE, per stream in 32-bit
+ *                     words: int32 next_id (a value < 1 reads as 1), int32 dropped (detections that found no free slot,
+ *                     cumulative), two zero words; then max_tracks slots of 60 words: int32 id (0 = free), hits (frames
+ *                     matched, the first included), age (frames since the first, that one included), misses (frames in a row
+ *                     without a match), f32 box[4], score, keypoints[17][3], copied from the record row last matched. A free
+ *                     slot is all zero in next. An all-zero state is the valid empty state.
+ *                   Similarity of a live track (a) and a detection of the frame (b), without contraction:
+ *                     similarity 0, IoU in f32 of the two record boxes (ymin, xmin, ymax, xmax): x0 = a.xmin > b.xmin ?
+ *                       a.xmin : b.xmin, x1 = a.xmax < b.xmax ? a.xmax : b.xmax, iw = x1 - x0, iw = iw > 0 ? iw : 0, ih
+ *                       likewise; inter = iw * ih; area = (xmax - xmin) * (ymax - ymin); union = area_a + area_b - inter;
+ *                       inter / union if union > 0 else 0. Needs no keypoints.
+ *                     similarity 1, OKS in f64 (mpn_oks_match's arithmetic): the track's stored keypoints are the ground
+ *                       truth with all 17 visible, area = (max x - min x) * (max y - min y) of those keypoints (min / max in
+ *                       f32), e = (dx^2 + dy^2) / vars / (area + 2^-52) / 2 with dx = detection - track, OKS = sum of
+ *                       exp(-e) in keypoint order / 17.
+ *                   Per frame, in this order:
+ *                     1. among the pairs (live slot t, unmatched detection d) with similarity >= match_threshold (compared
+ *                        in f64; a NaN never matches) the largest similarity is matched, ties to the smaller t, then the
+ *                        smaller d; repeated until no pair is left.
+ *                     2. a matched track takes the detection's box, score and keypoints; misses = 0, hits += 1, age += 1.
+ *                     3. an unmatched live track: misses += 1, age += 1; freed (the slot zeroed) when misses > max_misses.
+ *                     4. the unmatched detections with score >= new_track_score, in row order, take the lowest free slots
+ *                        (those freed in step 3 included): id = next_id++, hits = 1, age = 1, misses = 0. With no free slot
+ *                        left the detection stays untracked, its overflow flag is set and dropped += 1. Detections below
+ *                        new_track_score stay untracked.
+ *                     A frame without detections still ages the tracks.
+ *                   out: mpn_pose_track_out_bytes(B, max_boxes) bytes DEVICE, one row of 24 bytes per record row, aligned
+ *                     with the record's rows 0 .. total-1, every other row zero: int32 track_id (0 = untracked), int32 slot
+ *                     (-1 = none), int32 hits, int32 flags (bit 0 = new this frame, bit 1 = overflow), f64 similarity to the
+ *                     matched track (0 when new or untracked).
+ *                   Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); streams >= 1, B % streams == 0,
+ *                     1 <= max_tracks <= 64, 1 <= max_boxes <= 64, B * max_boxes <= 4096, similarity in {0, 1},
+ *                     max_misses >= 0 (MPN_ERR_BAD_SHAPE); record 16-byte and prev / next / out 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN); prev == next (MPN_ERR_BAD_ARG). The grid depends on streams alone: a captured
+ *                     launch serves any later record and state.
+ *   mpn_pose_track_state_bytes, mpn_pose_track_out_bytes   0 for arguments out of range.
+ */
+size_t mpn_pose_track_state_bytes(int streams, int max_tracks);
+size_t mpn_pose_track_out_bytes(int B, int max_boxes);
+int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                   float match_threshold, float new_track_score, int max_misses, const void* prev, void* next, void* out,
+                   mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

@@ -12,13 +12,14 @@
 // All arithmetic is IEEE float64 in COCOeval's order, contraction off; exp is the device library's (<= 1 ulp).
 // Latency-bound glue like mpn_pose_gather (B blocks of work measured in microseconds): not tuned, and not worth tuning.
 #include "common.h"
+#include "oks_math.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kK = 17;
+constexpr int kK = kOksKeypoints;
 constexpr int kMaxGt = 64;              // the matched set of a lane is one 64-bit mask
 constexpr int kMaxDets = 20;            // rows of the OKS matrix in LDS
 constexpr int kMaxT = 10;               // thresholds a row has room for
@@ -35,15 +36,9 @@ static_assert(kOutIgnore + 4 * kRanges + 4 == kOutBytes && kOutBytes % 8 == 0, "
 
 inline size_t header_words(int B) { return ((size_t)(2 * B + 2) + 3) / 4 * 4; }
 
-// cocoeval.py Params.setKpParams: kpt_oks_sigmas; computeOks: vars = (sigmas * 2)**2
-#define S(x) (((x) / 10.0 * 2) * ((x) / 10.0 * 2))
-__constant__ double kVars[kK] = {S(.26), S(.25), S(.25), S(.35), S(.35), S(.79), S(.79), S(.72), S(.72), S(.62), S(.62), S(1.07), S(1.07),
-                                 S(.87), S(.87), S(.89), S(.89)};
-#undef S
 // Params.setKpParams: areaRng all, medium, large
 __constant__ double kAreaLo[kRanges] = {0.0, 32.0 * 32.0, 96.0 * 96.0};
 __constant__ double kAreaHi[kRanges] = {1e5 * 1e5, 96.0 * 96.0, 1e5 * 1e5};
-constexpr double kEps = 2.220446049250313e-16;      // np.spacing(1)
 
 struct OksArgs {
     const int* header;
@@ -75,8 +70,7 @@ __device__ double oks_of(const float* kp, const double* g) {
             dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1);
             dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
         }
-        const double e = (dx * dx + dy * dy) / kVars[k] / denom / 2;
-        sum += exp(-e);
+        sum += oks_term(dx, dy, k, denom);
     }
     return sum / (double)(k1 > 0 ? k1 : kK);
 }
@@ -127,13 +121,7 @@ __global__ __launch_bounds__(kThreads) void oks_match_kernel(OksArgs a) {
             s = s * (m / 17.0f);
         }
         score[i] = s;
-        const float* kp = row + kOffKeypoints;
-        float xl = kp[0], xh = kp[0], yl = kp[1], yh = kp[1];
-        for (int k = 1; k < kK; ++k) {
-            xl = fminf(xl, kp[3 * k]); xh = fmaxf(xh, kp[3 * k]);
-            yl = fminf(yl, kp[3 * k + 1]); yh = fmaxf(yh, kp[3 * k + 1]);
-        }
-        area[i] = ((double)xh - (double)xl) * ((double)yh - (double)yl);
+        area[i] = keypoint_extent_area(row + kOffKeypoints);
     }
     __syncthreads();
     for (int i = tid; i < n; i += kThreads) {

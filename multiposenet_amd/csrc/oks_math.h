@@ -1,0 +1,36 @@
+// The arithmetic of object keypoint similarity that oks.hip (detections against ground truth) and pose_track.hip (detections
+// against the tracks of the previous frames) share: COCO's per-keypoint variances, one keypoint's exp term and the area of a
+// keypoint set's bounding box. IEEE float64 in COCOeval's order, contraction off; exp is the device library's (<= 1 ulp).
+#pragma once
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kOksKeypoints = 17;
+
+// cocoeval.py Params.setKpParams: kpt_oks_sigmas; computeOks: vars = (sigmas * 2)**2
+#define S(x) (((x) / 10.0 * 2) * ((x) / 10.0 * 2))
+__constant__ double kVars[kOksKeypoints] = {S(.26), S(.25), S(.25), S(.35), S(.35), S(.79), S(.79), S(.72), S(.72), S(.62), S(.62),
+                                            S(1.07), S(1.07), S(.87), S(.87), S(.89), S(.89)};
+#undef S
+constexpr double kEps = 2.220446049250313e-16;      // np.spacing(1)
+
+// computeOks, one keypoint: exp(-e), e = (dx^2 + dy^2) / vars[k] / (area + eps) / 2; denom = area + eps
+__device__ __forceinline__ double oks_term(double dx, double dy, int k, double denom) {
+    const double e = (dx * dx + dy * dy) / kVars[k] / denom / 2;
+    return exp(-e);
+}
+
+// (max x - min x) * (max y - min y) of keypoints[17][3] = (x, y, score): min / max in f32, the differences and the product in f64
+__device__ __forceinline__ double keypoint_extent_area(const float* kp) {
+    float xl = kp[0], xh = kp[0], yl = kp[1], yh = kp[1];
+    for (int k = 1; k < kOksKeypoints; ++k) {
+        xl = fminf(xl, kp[3 * k]); xh = fmaxf(xh, kp[3 * k]);
+        yl = fminf(yl, kp[3 * k + 1]); yh = fmaxf(yh, kp[3 * k + 1]);
+    }
+    return ((double)xh - (double)xl) * ((double)yh - (double)yl);
+}
+
+}  // namespace

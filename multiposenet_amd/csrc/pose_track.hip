@@ -1,0 +1,293 @@
+// Person identities across the frames of a video, on the device: greedy matching of a frame's detections (the record
+// mpn_pose_gather wrote) against the tracks the earlier frames left, by box IoU (f32) or keypoint OKS (f64).
+//   mpn_pose_track   record (read in place) + prev state -> next state + one 24-byte row per record row
+//                    {track_id, slot, hits, flags, similarity}. PURE: prev is never written; the caller advances the state by
+//                    copying next over prev (include/mpn.h says why: a captured launch runs twice on an entry's first call).
+// ONE block per stream (B = streams * F images, stream s owns images s*F .. s*F+F-1 in time order); the block walks its F frames
+// in order with the working state in LDS. Per frame:
+//   phase A  the extent area of every live track's keypoints (OKS), the per-detection tables cleared
+//   phase B  the similarity of every (live track, detection) pair -> LDS, transposed [detection][track]: 64 x 64 f64 = 32 KB
+//   phase C  greedy matching by wave 0, lane = track slot: every lane keeps the best open detection of its row (ties: the
+//            smaller detection), a 6-step xor butterfly takes the largest (ties: the smaller slot); a lane rescans its row
+//            only when the detection it held was taken. No barrier inside the rounds, at most min(tracks, detections) of them.
+//   phase D  hits / age / misses of the live tracks, tracks past max_misses freed
+//   phase E  births in row order into the lowest free slots: two ballots and popcounts, no serial walk
+//   phase F  the detections' box, score and keypoints copied into their slots, free slots zeroed, the output rows
+// Latency-bound glue like mpn_oks_match (microseconds behind a network pass of milliseconds): not tuned beyond that.
+#include "common.h"
+#include "oks_math.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxTracks = 64;          // one lane of wave 0 per slot; the free set is one 64-bit ballot
+constexpr int kMaxBoxes = 64;           // the taken set of a frame's detections is one 64-bit mask
+constexpr int kMaxRows = 4096;          // mpn_pose_gather's own limit on B * max_boxes
+// the record's row (pose_gather.hip), in 32-bit words
+constexpr int kRowWords = 108, kOffBox = 1, kOffScore = 5, kOffKeypoints = 57;
+// the state of one stream, in 32-bit words: {next_id, dropped, 0, 0}, then max_tracks slots of
+// {id, hits, age, misses, box[4], score, keypoints[17][3]}
+constexpr int kStateHeaderWords = 4, kSlotInts = 4, kSlotData = 5 + 3 * kOksKeypoints, kSlotWords = kSlotInts + kSlotData;
+constexpr int kDataKeypoints = 5;       // keypoints within a slot's data words (behind box[4] and score)
+static_assert(kSlotWords == 60 && kSlotWords % 4 == 0 && kOffScore == kOffBox + 4, "state slot layout");
+// an output row: int32 track_id, slot, hits, flags, f64 similarity
+constexpr int kOutBytes = 24;
+constexpr int kFlagNew = 1, kFlagOverflow = 2;
+
+inline size_t header_words(int B) { return ((size_t)(2 * B + 2) + 3) / 4 * 4; }
+__host__ __device__ inline size_t stream_words(int max_tracks) { return kStateHeaderWords + (size_t)max_tracks * kSlotWords; }
+
+struct TrackArgs {
+    const int* header;
+    const float* rows;
+    const int* prev;
+    int* next;
+    unsigned char* out;
+    int B, max_boxes, streams, max_tracks, similarity, max_misses;
+    float match_threshold, new_track_score;
+};
+
+// IoU of two record boxes (ymin, xmin, ymax, xmax) in f32; every min / max is a comparison (a NaN operand takes the other
+// branch the same way in the numpy transcription), every operation correctly rounded
+__device__ __forceinline__ float iou_of(const float* a, const float* b) {
+    const float x0 = a[1] > b[1] ? a[1] : b[1], x1 = a[3] < b[3] ? a[3] : b[3];
+    const float y0 = a[0] > b[0] ? a[0] : b[0], y1 = a[2] < b[2] ? a[2] : b[2];
+    float iw = x1 - x0, ih = y1 - y0;
+    iw = iw > 0.f ? iw : 0.f;
+    ih = ih > 0.f ? ih : 0.f;
+    const float inter = iw * ih;
+    const float area_a = (a[3] - a[1]) * (a[2] - a[0]), area_b = (b[3] - b[1]) * (b[2] - b[0]);
+    const float uni = area_a + area_b - inter;
+    return uni > 0.f ? inter / uni : 0.f;
+}
+
+// computeOks with the track's stored keypoints in the ground-truth role, all 17 visible; area = their extent area
+__device__ __forceinline__ double oks_track(const float* track_kp, double area, const float* det_kp) {
+    const double denom = area + kEps;
+    double sum = 0.0;
+    for (int k = 0; k < kOksKeypoints; ++k) {
+        const double dx = (double)det_kp[3 * k] - (double)track_kp[3 * k];
+        const double dy = (double)det_kp[3 * k + 1] - (double)track_kp[3 * k + 1];
+        sum += oks_term(dx, dy, k, denom);
+    }
+    return sum / (double)kOksKeypoints;
+}
+
+__global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
+    __shared__ double sim[kMaxBoxes][kMaxTracks];         // [detection][slot]: lane = slot reads consecutive doubles
+    __shared__ float data[kMaxTracks][kSlotData];         // box[4], score, keypoints[17][3] of every slot
+    __shared__ int id[kMaxTracks], hits[kMaxTracks], age[kMaxTracks], misses[kMaxTracks];
+    __shared__ double tarea[kMaxTracks];
+    __shared__ double dsim[kMaxBoxes];                    // similarity of a matched detection
+    __shared__ int dslot[kMaxBoxes];                      // the slot a detection's data goes to, -1 = untracked
+    __shared__ int dflags[kMaxBoxes];
+    __shared__ int free_slot[kMaxTracks];                 // the r-th free slot
+    __shared__ int counters[2];                           // next_id, dropped
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = a.max_tracks, F = a.B / a.streams;
+    const int all_rows = a.B * a.max_boxes;
+    const int* pst = a.prev + (size_t)s * stream_words(T);
+    int* nst = a.next + (size_t)s * stream_words(T);
+
+    for (int i = tid; i < T * kSlotData; i += kThreads) {
+        const int t = i / kSlotData, w = i - t * kSlotData;
+        data[t][w] = __int_as_float(pst[kStateHeaderWords + t * kSlotWords + kSlotInts + w]);
+    }
+    if (tid < T) {
+        const int* p = pst + kStateHeaderWords + tid * kSlotWords;
+        id[tid] = p[0]; hits[tid] = p[1]; age[tid] = p[2]; misses[tid] = p[3];
+    }
+    if (tid == 0) {
+        counters[0] = pst[0] < 1 ? 1 : pst[0];            // an all-zero state is the empty state: next_id reads as 1
+        counters[1] = pst[1];
+    }
+
+    // the record's counts, clamped as mpn_oks_match clamps them: nothing is indexed out of range
+    int total = a.header[0];
+    total = total < 0 ? 0 : (total > all_rows ? all_rows : total);
+    // rows behind the record's total are zero: the blocks share them
+    for (long long w = (long long)total * (kOutBytes / 4) + s * kThreads + tid; w < (long long)all_rows * (kOutBytes / 4);
+         w += (long long)a.streams * kThreads)
+        ((unsigned*)a.out)[w] = 0u;
+    int ahead = 0;                                        // kept rows of the images before the frame
+    for (int i = 0; i < s * F; ++i) {
+        ahead += a.header[1 + i] > 0 ? a.header[1 + i] : 0;
+        if (ahead > all_rows) ahead = all_rows;           // (past the total either way; the sum cannot wrap)
+    }
+    __syncthreads();
+
+    for (int f = 0; f < F; ++f) {
+        const int b = s * F + f;
+        int n = a.header[1 + b];
+        int first = ahead;
+        ahead += n > 0 ? n : 0;
+        if (ahead > all_rows) ahead = all_rows;
+        n = n < 0 ? 0 : (n > a.max_boxes ? a.max_boxes : n);
+        if (first > total) first = total;
+        if (first + n > total) n = total - first;
+        const float* rows = a.rows + (size_t)first * kRowWords;
+
+        // phase A
+        if (tid < T && a.similarity == 1 && id[tid] != 0) tarea[tid] = keypoint_extent_area(&data[tid][kDataKeypoints]);
+        if (tid < kMaxBoxes) { dslot[tid] = -1; dflags[tid] = 0; dsim[tid] = 0.0; }
+        __syncthreads();
+
+        // phase B
+        for (int i = tid; i < T * n; i += kThreads) {
+            const int d = i / T, t = i - d * T;
+            double v = 0.0;
+            if (id[t] != 0) {
+                const float* row = rows + (size_t)d * kRowWords;
+                v = a.similarity == 0 ? (double)iou_of(&data[t][0], row + kOffBox)
+                                      : oks_track(&data[t][kDataKeypoints], tarea[t], row + kOffKeypoints);
+            }
+            sim[d][t] = v;
+        }
+        __syncthreads();
+
+        // phases C and D
+        if (wave == 0) {
+            const int t = lane;
+            const bool live = t < T && id[t] != 0;
+            const double thr = (double)a.match_threshold;
+            unsigned long long taken = 0ull;
+            bool open = live, rescan = true;
+            double best = 0.0, mine_sim = 0.0;
+            int best_d = -1, mine = -1;
+            for (int round = 0; round < n; ++round) {
+                if (open && rescan) {
+                    best_d = -1;
+                    for (int d = 0; d < n; ++d) {
+                        if ((taken >> d) & 1ull) continue;
+                        const double v = sim[d][t];
+                        if (v >= thr && (best_d < 0 || v > best)) { best = v; best_d = d; }   // a NaN never passes v >= thr
+                    }
+                    rescan = false;
+                }
+                double v = best;
+                int ct = (open && best_d >= 0) ? t : -1, cd = best_d;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const double v2 = __shfl_xor(v, o, 64);
+                    const int t2 = __shfl_xor(ct, o, 64), d2 = __shfl_xor(cd, o, 64);
+                    if (t2 >= 0 && (ct < 0 || v2 > v || (v2 == v && t2 < ct))) { v = v2; ct = t2; cd = d2; }
+                }
+                if (ct < 0) break;                        // (every lane holds the same winner: a uniform exit)
+                taken |= 1ull << cd;
+                if (ct == t) { open = false; mine = cd; mine_sim = v; }
+                else if (best_d == cd) rescan = true;
+            }
+            if (live) {
+                if (mine >= 0) {
+                    misses[t] = 0; hits[t] += 1; age[t] += 1;
+                    dslot[mine] = t; dsim[mine] = mine_sim;
+                } else {
+                    misses[t] += 1; age[t] += 1;
+                    if (misses[t] > a.max_misses) { id[t] = 0; hits[t] = 0; age[t] = 0; misses[t] = 0; }
+                }
+            }
+        }
+        __syncthreads();
+
+        // phase E
+        bool want = false;
+        unsigned long long want_mask = 0ull;
+        int num_free = 0;
+        if (wave == 0) {
+            want = lane < n && dslot[lane] < 0 && rows[(size_t)lane * kRowWords + kOffScore] >= a.new_track_score;
+            const bool is_free = lane < T && id[lane] == 0;
+            want_mask = __ballot(want);
+            const unsigned long long free_mask = __ballot(is_free);
+            num_free = __popcll(free_mask);
+            if (is_free) free_slot[__popcll(free_mask & ((1ull << lane) - 1ull))] = lane;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const int next_id = counters[0];
+            const int r = __popcll(want_mask & ((1ull << lane) - 1ull)), num_want = __popcll(want_mask);
+            if (want) {
+                if (r < num_free) {
+                    const int t = free_slot[r];
+                    id[t] = next_id + r; hits[t] = 1; age[t] = 1; misses[t] = 0;
+                    dslot[lane] = t; dflags[lane] = kFlagNew;
+                } else {
+                    dflags[lane] = kFlagOverflow;
+                }
+            }
+            if (lane == 0) {
+                counters[0] = next_id + (num_want < num_free ? num_want : num_free);
+                counters[1] += num_want > num_free ? num_want - num_free : 0;
+            }
+        }
+        __syncthreads();
+
+        // phase F (a free slot and a slot that takes a detection are never the same one)
+        for (int i = tid; i < T * kSlotData; i += kThreads) {
+            const int t = i / kSlotData, w = i - t * kSlotData;
+            if (id[t] == 0) data[t][w] = 0.f;
+        }
+        for (int i = tid; i < n * kSlotData; i += kThreads) {
+            const int d = i / kSlotData, w = i - d * kSlotData;
+            const int t = dslot[d];
+            if (t >= 0) data[t][w] = rows[(size_t)d * kRowWords + (w < kDataKeypoints ? kOffBox + w : kOffKeypoints + w - kDataKeypoints)];
+        }
+        if (tid < n) {
+            unsigned char* o = a.out + (size_t)(first + tid) * kOutBytes;
+            const int t = dslot[tid];
+            ((int*)o)[0] = t >= 0 ? id[t] : 0;
+            ((int*)o)[1] = t;
+            ((int*)o)[2] = t >= 0 ? hits[t] : 0;
+            ((int*)o)[3] = dflags[tid];
+            *(double*)(o + 16) = dsim[tid];
+        }
+        __syncthreads();
+    }
+
+    for (int i = tid; i < T * kSlotData; i += kThreads) {
+        const int t = i / kSlotData, w = i - t * kSlotData;
+        nst[kStateHeaderWords + t * kSlotWords + kSlotInts + w] = __float_as_int(data[t][w]);
+    }
+    if (tid < T) {
+        int* p = nst + kStateHeaderWords + tid * kSlotWords;
+        p[0] = id[tid]; p[1] = hits[tid]; p[2] = age[tid]; p[3] = misses[tid];
+    }
+    if (tid < kStateHeaderWords) nst[tid] = tid < 2 ? counters[tid] : 0;
+}
+
+}  // namespace
+
+extern "C" size_t mpn_pose_track_state_bytes(int streams, int max_tracks) {
+    if (streams < 1 || streams > kMaxRows || max_tracks < 1 || max_tracks > kMaxTracks) return 0;
+    return (size_t)streams * stream_words(max_tracks) * 4;
+}
+
+extern "C" size_t mpn_pose_track_out_bytes(int B, int max_boxes) {
+    if (B < 1 || max_boxes < 1 || max_boxes > kMaxBoxes || (long long)B * max_boxes > kMaxRows) return 0;
+    return (size_t)B * max_boxes * kOutBytes;
+}
+
+extern "C" int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                              float match_threshold, float new_track_score, int max_misses, const void* prev, void* next,
+                              void* out, mpn_stream_t stream) {
+    MPN_REQUIRE(record && prev && next && out, MPN_ERR_BAD_ARG, "pose_track: null pointer");
+    MPN_REQUIRE(streams >= 1 && B >= 1 && B % streams == 0, MPN_ERR_BAD_SHAPE,
+                "pose_track: B = %d images are not streams = %d times a whole number of frames", B, streams);
+    MPN_REQUIRE(max_tracks >= 1 && max_tracks <= kMaxTracks, MPN_ERR_BAD_SHAPE,
+                "pose_track: max_tracks = %d, one lane of a wave per slot takes 1..%d", max_tracks, kMaxTracks);
+    MPN_REQUIRE(max_boxes >= 1 && max_boxes <= kMaxBoxes && (long long)B * max_boxes <= kMaxRows, MPN_ERR_BAD_SHAPE,
+                "pose_track: B = %d, max_boxes = %d (at most %d per image, %d rows)", B, max_boxes, kMaxBoxes, kMaxRows);
+    MPN_REQUIRE(similarity == 0 || similarity == 1, MPN_ERR_BAD_SHAPE, "pose_track: similarity must be 0 (IoU) or 1 (OKS)");
+    MPN_REQUIRE(max_misses >= 0, MPN_ERR_BAD_SHAPE, "pose_track: max_misses = %d is negative", max_misses);
+    MPN_REQUIRE(mpn_aligned16(record) && (((uintptr_t)prev | (uintptr_t)next | (uintptr_t)out) & 7u) == 0, MPN_ERR_BAD_ALIGN,
+                "pose_track: record must be 16-byte, prev / next / out 8-byte aligned");
+    MPN_REQUIRE(prev != next, MPN_ERR_BAD_ARG,
+                "pose_track: prev and next are one buffer; the launch is a pure function of (record, prev)");
+    TrackArgs a = {(const int*)record, (const float*)((const char*)record + header_words(B) * 4), (const int*)prev, (int*)next,
+                   (unsigned char*)out, B, max_boxes, streams, max_tracks, similarity, max_misses, match_threshold,
+                   new_track_score};
+    pose_track_kernel<<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+    MPN_LAUNCH_CHECK();
+    return MPN_OK;
+}

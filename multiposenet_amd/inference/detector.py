@@ -126,10 +126,11 @@ class _Entry:
     input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
-    entry (a tta.Buffers), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
+    buffers, so the entry keeps it alive), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -325,7 +326,7 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None):
+                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -362,6 +363,12 @@ class Detector:
                 run at that size (over the mirrors too with flip), and the maps are resized to the base size (bilinear,
                 half-pixel centres) and averaged in the same launch, in the order base, base mirrored, scale 1, scale 1
                 mirrored, ... (include/mpn.h states the arithmetic). Part of the graph's key, like flip.
+            track: a tracking.PoseTracker. The images are frames of its streams (stream s owns images s*F .. s*F+F-1 in time
+                order, b = streams * F). Adds 'track_ids' int32 [n] (a person's identity across the frames and calls of its
+                stream, 0 = untracked), 'track_hits' int32 [n], 'track_new' bool [n] and 'track_similarity' f64 [n] to
+                every dict: one mpn_pose_track launch behind the gather inside the captured graph - a graph of its own per
+                (tracker, b) - whose rows arrive with the record. The launch only reads the tracker's state; the call
+                advances it once, by a small device copy behind the graph. Every other key is unchanged.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
@@ -370,7 +377,8 @@ class Detector:
         b, h, w = check_batch(images)
         thr = float(score_threshold)
         oks = self._check_groundtruth(groundtruth, b)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w))
+        trk = self._check_track(track, b)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w), trk, track)
         if oks:
             ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
         if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
@@ -383,7 +391,9 @@ class Detector:
                 stage[i] = im
         ent.x[:b].copy_(ent.stage, non_blocking=True)               # ONE host-to-device copy
         outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps,
-                                                              oks=ent.oks, aug=ent.tta))
+                                                              oks=ent.oks, aug=ent.tta, track=ent.track))
+        if trk:
+            ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
         return self._finish(ent, outs, b, return_heatmaps)
 
     def _check_tta(self, flip, scales, h, w):
@@ -404,6 +414,26 @@ class Detector:
         if self.oks_score not in pose_metrics.SCORE_MODES:
             raise ValueError(f"oks_score must be one of {sorted(pose_metrics.SCORE_MODES)} (got {self.oks_score!r})")
         return ('oks', self.oks_score, int(self.oks_max_dets))
+
+    def _check_track(self, track, b):
+        """The `track` argument of the predict_* methods -> () or the tail of the entry's key. Before any device work."""
+        if track is None:
+            return ()
+        from ..tracking import PoseTracker
+        if not isinstance(track, PoseTracker):
+            raise ValueError("track must be a tracking.PoseTracker")
+        if self.retinanet is None:
+            raise ValueError("track= needs the person detector (detector_path): without it no persons are detected")
+        if track.similarity == 'oks' and self.assigner is None:
+            raise ValueError("track=: similarity='oks' compares keypoints, which need the PRN (prn_path); use similarity='iou'")
+        track.check_batch(b)
+        if track.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"track=: the tracker was made for max_boxes = {track.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if torch.device(track.device) != torch.device(self.net.device):
+            raise ValueError(f"track=: the tracker lives on {track.device}, this Detector on {self.net.device}")
+        track.out_bytes(b)
+        return ('track', track.serial, b)
 
     def _oks_buffers(self, b, oks):
         return pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, self.net.device, oks[1], oks[2])
@@ -443,6 +473,11 @@ class Detector:
                 at = _lib.lib().mpn_pose_gather_record_bytes(b, self.params['max_boxes'])
                 for p, table in zip(persons, ent.oks.unpack(record[at:], record[4:4 + 4 * b].view(np.int32))):
                     p['oks'] = table
+            if ent.track is not None:                               # the track rows lie behind those: the same copy
+                at = _lib.lib().mpn_pose_gather_record_bytes(b, self.params['max_boxes'])
+                at += ent.oks.out_bytes if ent.oks is not None else 0
+                for p, ids in zip(persons, ent.track.unpack(record[at:], record[4:4 + 4 * b].view(np.int32))):
+                    p.update(ids)
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -460,8 +495,8 @@ class Detector:
                 p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=()):
-        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks][, tta]): pinned staging, the device input (with the
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=(), trk=(), track=None):
+        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks][, tta][, track]): pinned staging, the device input (with the
         mirrors behind the batch and the inputs of the extra scales for a check_tta key), fixed drawing and
         encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
         key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
@@ -469,7 +504,7 @@ class Detector:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
         if plot_maps:
             key += ('maps',)
-        key += oks + tta_key
+        key += oks + tta_key + trk
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -489,6 +524,7 @@ class Detector:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
         if oks:
             ent.oks = self._oks_buffers(b, oks)
+        ent.track = track if trk else None
         store[key] = ent
         return ent
 
@@ -501,7 +537,7 @@ class Detector:
             ent.x = torch.empty((b, h, w, 3), dtype=torch.uint8, device=self.net.device)
 
     def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None,
-                           oks=None, aug=None):
+                           oks=None, aug=None, track=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
@@ -511,6 +547,8 @@ class Detector:
         plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
         oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
         the record in the same buffer, so that they reach the host in the record's copy.
+        track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
+        tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits).
         aug (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -549,7 +587,9 @@ class Detector:
         nbytes = lib.mpn_pose_gather_record_bytes(b, max_boxes)
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        whole = torch.empty(nbytes + (oks.out_bytes if oks is not None else 0), dtype=torch.uint8, device=net.device)
+        oks_bytes = oks.out_bytes if oks is not None else 0
+        track_bytes = track.out_bytes(b) if track is not None else 0
+        whole = torch.empty(nbytes + oks_bytes + track_bytes, dtype=torch.uint8, device=net.device)
         record = whole[:nbytes]
         if extent is None:
             _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
@@ -560,7 +600,9 @@ class Detector:
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
         if oks is not None:
-            oks.launch(record, whole[nbytes:])
+            oks.launch(record, whole[nbytes:nbytes + oks_bytes])
+        if track is not None:
+            track.launch(record, whole[nbytes + oks_bytes:], b)
         dev['record'] = whole
         if annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
@@ -591,7 +633,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None):
+                       flip=False, scales=None, track=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -615,6 +657,8 @@ class Detector:
             flip, scales: as for `predict_batch`, of the network CANVAS: its mirror (with keep_aspect_ratio the padding then
                 lies on the other side) and the canvas resized to each (width, height) of `scales`, which have the aspect
                 ratio of `size` - not the source frames resized again.
+            track: as for `predict_batch`; the tracker sees the boxes normalised to the source images and the keypoints in
+                source pixels, as they are returned.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -634,12 +678,12 @@ class Detector:
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
         return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key)
+                                     tta_key, track)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None, flip=False, scales=None):
+                      groundtruth=None, flip=False, scales=None, track=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -656,7 +700,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales: as for `predict_images`.
+            flip, scales, track: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -684,17 +728,18 @@ class Detector:
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
             self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
         return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key)
+                                     tta_key, track)
 
     def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False,
-                         groundtruth=None, tta_key=()):
+                         groundtruth=None, tta_key=(), track=None):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
         one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
         b, thr = plan.b, float(score_threshold)
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
         oks = self._check_groundtruth(groundtruth, b)
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key)
+        trk = self._check_track(track, b)
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key, trk, track)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
@@ -705,13 +750,17 @@ class Detector:
             self._place_encode(ent, eplan)
         if oks:
             ent.oks.place(groundtruth)
-        persons = self._finish(ent, self._run(ent, lambda: self._device_side_images(ent, thr)), b, return_heatmaps)
+        outs = self._run(ent, lambda: self._device_side_images(ent, thr))
+        if trk:
+            ent.track.commit()                                      # as in predict_batch: once per call, outside the graph
+        persons = self._finish(ent, outs, b, return_heatmaps)
         if return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=(), tta_key=()):
+    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=(), tta_key=(), trk=(),
+                      track=None):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
@@ -719,14 +768,15 @@ class Detector:
         output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
         capacity also covers the encoder's coefficients, streams and workspace. plot_maps: an entry of its own with a
         MapPlotter for the canvas batch. oks (groundtruth=): an entry of its own with the ground-truth buffers. tta_key (flip=,
-        scales=): an entry of its own whose canvas batch has the mirrors behind it, with the inputs of the extra scales."""
+        scales=): an entry of its own whose canvas batch has the mirrors behind it, with the inputs of the extra scales.
+        trk (track=): an entry of its own per tracker, whose graph reads and writes that tracker's state buffers."""
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
         base = ('images', b, h, w, thr)
         tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
         if plot_maps:
             tail += ('maps',)
-        tail += oks + tta_key
+        tail += oks + tta_key + trk
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -757,6 +807,7 @@ class Detector:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
         if oks:
             ent.oks = self._oks_buffers(b, oks)
+        ent.track = track if trk else None
         store[key] = ent
         return ent
 
@@ -770,7 +821,7 @@ class Detector:
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
         return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps,
-                                       oks=ent.oks, aug=ent.tta)
+                                       oks=ent.oks, aug=ent.tta, track=ent.track)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

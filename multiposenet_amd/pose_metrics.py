@@ -118,6 +118,39 @@ def pack_groundtruth(groundtruth, rows, counts):
         counts[i] = g
 
 
+def fill_record(outputs, b, max_boxes):
+    """b result dicts ('scores' and, where present, 'boxes', 'keypoint_scores', 'keypoint_positions', 'keypoints' as
+    `Detector.predict_batch` returns them) -> (record uint8 [record_bytes], counts int32 [b]) on the host: a record of
+    mpn_pose_gather's layout for (b, max_boxes), what `OksMatcher` and `tracking.PoseTracker.update` upload."""
+    from .inference.detector import _ROW
+    lib = _lib.lib()
+    record_bytes, first = lib.mpn_pose_gather_record_bytes(b, max_boxes), lib.mpn_pose_gather_row_offset(b, max_boxes, 0)
+    if len(outputs) != b:
+        raise ValueError(f"outputs must be a list of {b} dicts (got {len(outputs)})")
+    if _ROW.itemsize != lib.mpn_pose_gather_row_offset(b, max_boxes, 1) - first:
+        raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
+    record = np.zeros(record_bytes, np.uint8)
+    header = record[:first].view(np.int32)
+    rows = record[first:].view(_ROW)
+    s = 0
+    for i, o in enumerate(outputs):
+        n = len(o['scores'])
+        if n > max_boxes:
+            raise ValueError(f"outputs: image {i} has {n} detections, this matcher takes {max_boxes}")
+        r = rows[s:s + n]
+        r['image_index'], r['score'] = i, o['scores']
+        for k in ('keypoint_scores', 'keypoint_positions', 'keypoints'):
+            if k in o and len(o[k]) == n:
+                r[k] = o[k]
+        if 'boxes' in o and len(o['boxes']) == n:
+            r['box'] = o['boxes']
+        header[1 + i] = n
+        header[1 + b + i] = int(o.get('num_boxes', n))
+        s += n
+    header[0] = s
+    return record, header[1:1 + b].copy()
+
+
 class OksBuffers:
     """The device side of `mpn_oks_match` for one (b, max_boxes, max_gt): a pinned staging buffer and its device twin holding
     the thresholds, the ground-truth rows and their counts (`place`: one host-to-device copy), and the launch over a record
@@ -201,31 +234,7 @@ class OksMatcher:
 
     def fill_record(self, outputs):
         """b result dicts -> (record uint8 [record_bytes], counts int32 [b]) on the host."""
-        from .inference.detector import _ROW
-        if len(outputs) != self.b:
-            raise ValueError(f"outputs must be a list of {self.b} dicts (got {len(outputs)})")
-        if _ROW.itemsize != _lib.lib().mpn_pose_gather_row_offset(self.b, self.max_boxes, 1) - self.first:
-            raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
-        record = np.zeros(self.record_bytes, np.uint8)
-        header = record[:self.first].view(np.int32)
-        rows = record[self.first:].view(_ROW)
-        s = 0
-        for i, o in enumerate(outputs):
-            n = len(o['scores'])
-            if n > self.max_boxes:
-                raise ValueError(f"outputs: image {i} has {n} detections, this matcher takes {self.max_boxes}")
-            r = rows[s:s + n]
-            r['image_index'], r['score'] = i, o['scores']
-            for k in ('keypoint_scores', 'keypoint_positions', 'keypoints'):
-                if k in o and len(o[k]) == n:
-                    r[k] = o[k]
-            if 'boxes' in o and len(o['boxes']) == n:
-                r['box'] = o['boxes']
-            header[1 + i] = n
-            header[1 + self.b + i] = int(o.get('num_boxes', n))
-            s += n
-        header[0] = s
-        return record, header[1:1 + self.b].copy()
+        return fill_record(outputs, self.b, self.max_boxes)
 
     def __call__(self, outputs, groundtruth, return_oks=False):
         import torch

@@ -1,0 +1,101 @@
+"""Persons with persistent identities over the frames of a video.
+
+    python -m multiposenet_amd.track_frames --images DIR --out tracks.jsonl
+        [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32] [--size W H] [--batch 16]
+        [--similarity oks|iou] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
+        [--score-threshold 0.05]
+
+The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
+--batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
+state stays on the device between the batches. JPEG files go through `Detector.predict_jpegs` as the bytes they are (every
+route `jpeg.jpeg_support` names); a batch holding any other file is decoded by Pillow and goes through `predict_images`.
+The last, shorter batch runs at its own size (a second graph of that size): padding it with copies of the last frame would
+advance the tracks by frames the video does not have. --out gets one JSON line per frame: its name, and per person the
+track id (0 = untracked), the box (ymin, xmin, ymax, xmax, normalised to the frame) and the keypoints (x, y, score) in the
+frame's pixels. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+import argparse
+import json
+import os
+
+import numpy as np
+
+EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp")
+
+
+def _is_jpeg(data):
+    from .inference.jpeg import jpeg_support
+    try:
+        jpeg_support(data)
+    except ValueError:
+        return False
+    return True
+
+
+def _pixels(data):
+    import io
+
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--images", required=True, help="directory of frames; sorted by name")
+    ap.add_argument("--out", default="tracks.jsonl")
+    ap.add_argument("--model", help="keypoint model .npz (the shared backbone)")
+    ap.add_argument("--detector", help="person detector head .npz")
+    ap.add_argument("--prn", help="pose residual network .npz")
+    ap.add_argument("--dtype", choices=("bf16", "f32"), default="bf16")
+    ap.add_argument("--size", type=int, nargs=2, default=(640, 640), metavar=("W", "H"))
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--similarity", choices=("oks", "iou"), default="oks")
+    ap.add_argument("--match-threshold", type=float, default=0.3)
+    ap.add_argument("--max-misses", type=int, default=10)
+    ap.add_argument("--new-track-score", type=float, default=0.3)
+    ap.add_argument("--max-tracks", type=int, default=32)
+    ap.add_argument("--score-threshold", type=float, default=0.05)
+    args = ap.parse_args(argv)
+    if args.batch < 1:
+        ap.error("--batch must be at least 1")
+    names = sorted(f for f in os.listdir(args.images) if f.lower().endswith(EXTENSIONS))
+    if not names:
+        raise SystemExit(f"no image files {EXTENSIONS} under {args.images}")
+
+    import torch
+    from .evaluate_pose import _random_head
+    from .inference import Detector, PoseTracker
+    from .prn import initial_values
+    if args.detector is None or args.prn is None:
+        print("[track_frames] no --detector / --prn file: seeded random weights, the tracks mean nothing")
+    det = Detector(args.model, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
+                   detector_path=args.detector if args.detector is not None else _random_head(),
+                   prn_path=args.prn if args.prn is not None else initial_values(seed=0))
+    tracker = PoseTracker(streams=1, max_tracks=args.max_tracks, similarity=args.similarity, match_threshold=args.match_threshold,
+                          max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'])
+    size = (args.size[1], args.size[0])
+    frames = persons = 0
+    with open(args.out, "w") as out:
+        for at in range(0, len(names), args.batch):
+            batch = names[at:at + args.batch]
+            files = []
+            for name in batch:
+                with open(os.path.join(args.images, name), "rb") as f:
+                    files.append(f.read())
+            if all(_is_jpeg(data) for data in files):
+                outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker)
+            else:
+                outs = det.predict_images([_pixels(data) for data in files], size=size, score_threshold=args.score_threshold,
+                                          track=tracker)
+            for name, o in zip(batch, outs):
+                out.write(json.dumps({"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
+                                      "keypoints": o["keypoints"].tolist()}) + "\n")
+                persons += len(o["track_ids"])
+            frames += len(batch)
+    state = tracker.tracks(0)
+    print(json.dumps({"frames": frames, "persons": persons, "ids_given": state["next_id"] - 1, "live_tracks": len(state["ids"]),
+                      "dropped": state["dropped"], "similarity": args.similarity, "out": args.out}))
+    return state
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,159 @@
+"""Person identities across the frames of a video, on the device: `mpn_pose_track` (include/mpn.h) matches the persons of every
+frame greedily, by box IoU or keypoint OKS, against the tracks the earlier frames left.
+
+    tracker = PoseTracker(streams=1, similarity='oks')           # one camera; a batch is consecutive frames
+    for frames in batches:
+        for person in detector.predict_images(frames, track=tracker):
+            person['track_ids']                                  # int32 [n], 0 = untracked; also track_hits / _new / _similarity
+
+Inside the Detector the launch follows the gather in the captured graph and its rows arrive in the record's one copy. The
+launch is a PURE function of (record, prev): it writes the new state to `next` and never touches `prev`, because the Detector
+runs its device side eagerly and then replays the graph on an entry's first call (and again when the variables change) - an
+in-place update would step the state twice there. The state advances when `commit()` queues `prev.copy_(next)` behind the
+launch, outside the graph; the Detector does that once per call. `update()` is the same launch for host dicts.
+"""
+import itertools
+
+import numpy as np
+
+from . import _lib
+from .pose_metrics import fill_record
+
+SIMILARITIES = {'iou': 0, 'oks': 1}
+MAX_TRACKS = 64                          # slots per stream the kernel takes (one lane of a wave per slot)
+MAX_BOXES = 64                           # detections per image
+NUM_KEYPOINTS = 17
+FLAG_NEW, FLAG_OVERFLOW = 1, 2
+
+# a row of mpn_pose_track's output and the state of one stream (include/mpn.h)
+_OUT = np.dtype([('track_id', np.int32), ('slot', np.int32), ('hits', np.int32), ('flags', np.int32),
+                 ('similarity', np.float64)])
+_HEAD = np.dtype([('next_id', np.int32), ('dropped', np.int32), ('pad', np.int32, (2,))])
+_SLOT = np.dtype([('id', np.int32), ('hits', np.int32), ('age', np.int32), ('misses', np.int32), ('box', np.float32, (4,)),
+                  ('score', np.float32), ('keypoints', np.float32, (NUM_KEYPOINTS, 3))])
+
+_serials = itertools.count(1)
+
+
+class PoseTracker:
+    """The tracks of `streams` independent cameras, `max_tracks` slots each, on the device.
+
+    A call over b images sees b / streams consecutive frames per stream: stream s owns images s*F .. s*F+F-1 in time order.
+    similarity: 'oks' (float64 OKS with the track's last keypoints in the ground-truth role; needs a PRN) or 'iou' (float32
+    IoU of the boxes). A pair matches at similarity >= match_threshold, the largest first; a track unmatched for more than
+    max_misses frames in a row is dropped; an unmatched detection with score >= new_track_score starts a track in the lowest
+    free slot, or is counted in `dropped` when there is none. Ids count from 1 per stream and are never reused.
+    max_boxes: the detection slots per image of the records this tracker reads (the Detector's params['max_boxes'])."""
+
+    def __init__(self, streams=1, max_tracks=32, similarity='oks', match_threshold=0.3, max_misses=10, new_track_score=0.3,
+                 max_boxes=25, device=None):
+        if similarity not in SIMILARITIES:
+            raise ValueError(f"similarity must be one of {sorted(SIMILARITIES)} (got {similarity!r})")
+        self.streams, self.max_tracks, self.max_boxes = int(streams), int(max_tracks), int(max_boxes)
+        self.similarity, self.max_misses = similarity, int(max_misses)
+        self.match_threshold, self.new_track_score = float(match_threshold), float(new_track_score)
+        if self.streams < 1:
+            raise ValueError(f"streams must be at least 1 (got {streams})")
+        if not 1 <= self.max_tracks <= MAX_TRACKS:
+            raise ValueError(f"max_tracks must be in 1..{MAX_TRACKS} (got {max_tracks}): one lane of a wave per slot")
+        if not 1 <= self.max_boxes <= MAX_BOXES:
+            raise ValueError(f"max_boxes must be in 1..{MAX_BOXES} (got {max_boxes})")
+        if self.max_misses < 0:
+            raise ValueError(f"max_misses must not be negative (got {max_misses})")
+        import torch
+        lib = _lib.lib()
+        self.state_bytes = lib.mpn_pose_track_state_bytes(self.streams, self.max_tracks)
+        self.stream_bytes = _HEAD.itemsize + self.max_tracks * _SLOT.itemsize
+        if self.state_bytes == 0 or self.state_bytes != self.streams * self.stream_bytes:
+            raise _lib.MpnError("mpn_pose_track: the state's layout is not the one this binding was written against")
+        self.device = torch.device(device) if device is not None else _lib.current_device()
+        self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
+        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
+        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
+        self._update = {}                                           # update(): device record and rows per batch size
+
+    def check_batch(self, b):
+        """The number of images of a call -> frames per stream."""
+        if b < 1 or b % self.streams != 0:
+            raise ValueError(f"track=: {b} images are not a whole number of frames for each of {self.streams} streams")
+        return b // self.streams
+
+    def out_bytes(self, b):
+        self.check_batch(b)
+        n = _lib.lib().mpn_pose_track_out_bytes(b, self.max_boxes)
+        if n == 0 or n != b * self.max_boxes * _OUT.itemsize:
+            raise ValueError(f"mpn_pose_track: {b} x {self.max_boxes} slots are more than one launch takes")
+        return n
+
+    def launch(self, record, out, b):
+        """record: the uint8 device tensor mpn_pose_gather wrote for (b, max_boxes); out: uint8 device tensor of
+        `out_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`."""
+        self.check_batch(b)
+        _lib.call("mpn_pose_track", _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
+                  SIMILARITIES[self.similarity], self.match_threshold, self.new_track_score, self.max_misses,
+                  _lib.ptr(self.prev), _lib.ptr(self.next), _lib.ptr(out), _lib.stream_ptr())
+        return out
+
+    def commit(self):
+        """The last launch's state becomes the current one: one small device copy on the current stream."""
+        self.prev.copy_(self.next, non_blocking=True)
+
+    def reset(self, stream=None):
+        """Forget every track and start the ids at 1 again: of all streams, or of one."""
+        if stream is None:
+            self.prev.zero_()
+            self.next.zero_()
+            return
+        if not 0 <= int(stream) < self.streams:
+            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
+        at = int(stream) * self.stream_bytes
+        self.prev[at:at + self.stream_bytes].zero_()
+        self.next[at:at + self.stream_bytes].zero_()
+
+    def unpack(self, out, counts):
+        """A host copy of the output rows (uint8 array) and the record's per-image counts -> a list of dicts, one per image:
+        'track_ids' int32 [n] (0 = untracked), 'track_hits' int32 [n], 'track_new' bool [n], 'track_similarity' f64 [n],
+        in the image's record order."""
+        rows = np.frombuffer(out, np.uint8, len(counts) * self.max_boxes * _OUT.itemsize).view(_OUT)
+        res, s = [], 0
+        for n in counts:
+            r = rows[s:s + int(n)]
+            res.append({'track_ids': r['track_id'].copy(), 'track_hits': r['hits'].copy(),
+                        'track_new': (r['flags'] & FLAG_NEW) != 0, 'track_similarity': r['similarity'].copy()})
+            s += int(n)
+        return res
+
+    def tracks(self, stream=0):
+        """A host copy of one stream's current state: {'next_id', 'dropped', 'slots' int [m] (the live slots), 'ids', 'hits',
+        'age', 'misses' int32 [m], 'boxes' f32 [m,4], 'scores' f32 [m], 'keypoints' f32 [m,17,3]}."""
+        if not 0 <= int(stream) < self.streams:
+            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
+        at = int(stream) * self.stream_bytes
+        raw = self.prev[at:at + self.stream_bytes].cpu().numpy()
+        head = raw[:_HEAD.itemsize].view(_HEAD)[0]
+        slots = raw[_HEAD.itemsize:].view(_SLOT)
+        live = np.nonzero(slots['id'] != 0)[0]
+        s = slots[live]
+        return {'next_id': max(int(head['next_id']), 1), 'dropped': int(head['dropped']), 'slots': live,
+                'ids': s['id'].copy(), 'hits': s['hits'].copy(), 'age': s['age'].copy(), 'misses': s['misses'].copy(),
+                'boxes': s['box'].copy(), 'scores': s['score'].copy(), 'keypoints': s['keypoints'].copy()}
+
+    def update(self, outputs):
+        """The same launch for host arrays: b result dicts ('boxes', 'scores', 'keypoints' as `Detector.predict_*` returns
+        them; at most max_boxes persons each) are packed into a record, uploaded, tracked and committed. Returns what
+        `unpack` returns."""
+        import torch
+        outputs = list(outputs)
+        b = len(outputs)
+        nbytes = self.out_bytes(b)
+        record, counts = fill_record(outputs, b, self.max_boxes)
+        with torch.cuda.device(self.device):
+            if b not in self._update:
+                self._update[b] = (torch.zeros(len(record), dtype=torch.uint8, device=self.device),
+                                   torch.zeros(nbytes, dtype=torch.uint8, device=self.device))
+            dev_record, dev_out = self._update[b]
+            dev_record.copy_(torch.from_numpy(record))
+            self.launch(dev_record, dev_out, b)
+            self.commit()
+            out = dev_out.cpu().numpy()
+        return self.unpack(out, counts)
