@@ -141,7 +141,8 @@ __global__ __launch_bounds__(kThreads) void match_anchor_kernel(const float* __r
         const float v = live ? iou_f32(g, an) : 0.f;
         if (v > best_v) { best_v = v; best = n; }
         // anchors that do not overlap the box cannot become its forced match (a forced match needs iou >= 0.05): only the
-        // few thousand overlapping ones issue an atomic. A box nothing overlaps keeps key 0 = "no anchor".
+        // few thousand overlapping ones issue an atomic. A box nothing overlaps keeps key 0, which pass 2 reads as "anchor 0 at
+        // iou 0" (the arg-max of an all-zero row).
         // One atomic per wave and box: the lanes' keys are reduced first (a box overlapped by a few thousand anchors drew as
         // many contended atomics: 112 us of the detector step).
         unsigned long long key = v > 0.f ? ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)a) : 0ull;
@@ -167,19 +168,21 @@ __global__ __launch_bounds__(kThreads) void match_anchor_kernel(const float* __r
 
 // pass 2: forced matches (training_target_creation.py:101-121): groundtruth box n forces its best anchor f(n); the anchor
 // takes the SMALLEST n that forces it (argmax over the 0/1 indicator rows, computed before the is_okay mask) whenever ANY
-// box forcing it has iou >= 0.05. One block per image, one thread per box, O(N^2).
+// box forcing it has iou >= 0.05. A box with iou 0 against every anchor (key 0: a zero-area box, a box off the anchors) forces
+// ANCHOR 0, as tf.argmax of its all-zero row does: it never passes the 0.05 test itself, but it takes part in the smallest-n
+// rule of anchor 0, so it wins the anchor from a later box that does pass. One block per image, one thread per box, O(N^2).
 __global__ __launch_bounds__(kThreads) void match_forced_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ num_boxes,
                                                                 int A, int maxN, int* __restrict__ matches) {
     const int b = blockIdx.x;
     const int N = min(num_boxes[b], maxN);
+    const auto forced_anchor = [](unsigned long long key) { return key == 0ull ? 0u : 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull); };
     for (int n = threadIdx.x; n < N; n += kThreads) {
-        const unsigned long long kn = keys[(long long)b * maxN + n];
-        const unsigned f = 0xFFFFFFFFu - (unsigned)(kn & 0xFFFFFFFFull);
+        const unsigned f = forced_anchor(keys[(long long)b * maxN + n]);
         int row = n;
         bool ok = false;
         for (int j = 0; j < N; ++j) {
             const unsigned long long kj = keys[(long long)b * maxN + j];
-            if (0xFFFFFFFFu - (unsigned)(kj & 0xFFFFFFFFull) != f) continue;
+            if (forced_anchor(kj) != f) continue;
             if (j < row) row = j;
             ok = ok || (__uint_as_float((unsigned)(kj >> 32)) >= 0.05f);
         }

@@ -198,11 +198,11 @@ def match_boxes(anchors, groundtruth_boxes, positives_threshold=POSITIVES_THRESH
     return matches
 
 
-def get_training_targets(anchors, groundtruth_boxes):
+def get_training_targets(anchors, groundtruth_boxes, positives_threshold=POSITIVES_THRESHOLD, negatives_threshold=NEGATIVES_THRESHOLD):
     """training_target_creation.py:5-42 + create_targets :126-159. Returns (float32 [A,4], int32 [A])."""
     A = anchors.shape[0]
     if groundtruth_boxes.shape[0] > 0:
-        matches = match_boxes(anchors, groundtruth_boxes)
+        matches = match_boxes(anchors, groundtruth_boxes, positives_threshold, negatives_threshold)
     else:
         matches = np.full(A, -1, np.int32)
     targets = np.zeros((A, 4), np.float32)

@@ -6,7 +6,7 @@ import torch
 
 from oracle import network as onet
 from oracle import retinanet as R
-from util import dev, rnd
+from util import dev, level_tensors as _level_tensors, rnd
 
 pytestmark = pytest.mark.gpu
 HP = {"initial_learning_rate": 1e-3, "num_steps": 150000, "weight_decay": 5e-5, "localization_loss_weight": 1.0,
@@ -91,20 +91,6 @@ def test_anchor_matching_is_bit_exact(cuda):
             np.testing.assert_allclose(got_t[b], wt, rtol=2e-6, atol=2e-6)
             total += int((wm >= 0).sum())
         assert int(nm.item()) == total and total > 0
-
-
-def _level_tensors(flat_boxes, flat_logits, shapes, dtype):
-    """[B,A,4] / [B,A] in the reference's anchor order -> per-level NHWC tensors [B,h,w,24] / [B,h,w,8] (padding channels 0)."""
-    B = flat_boxes.shape[0]
-    bx, lg, off = [], [], 0
-    for (h, w) in shapes:
-        n = h * w * 6
-        bx.append(dev(flat_boxes[:, off:off + n].reshape(B, h, w, 24), dtype))
-        l8 = np.zeros((B, h, w, 8), np.float32)
-        l8[..., :6] = flat_logits[:, off:off + n].reshape(B, h, w, 6)
-        lg.append(dev(l8, dtype))
-        off += n
-    return bx, lg
 
 
 @pytest.mark.parametrize("H,W,B,mean", [(128, 256, 3, -3.0), (256, 256, 2, 1.0)], ids=["lds-candidates", "global-candidates"])

@@ -20,6 +20,20 @@ def dev(x, dtype=None):
     return t.contiguous().cuda()
 
 
+def level_tensors(flat_boxes, flat_logits, shapes, dtype):
+    """[B,A,4] / [B,A] in the reference's anchor order -> per-level NHWC tensors [B,h,w,24] / [B,h,w,8] (padding channels 0)."""
+    B = flat_boxes.shape[0]
+    bx, lg, off = [], [], 0
+    for (h, w) in shapes:
+        n = h * w * 6
+        bx.append(dev(flat_boxes[:, off:off + n].reshape(B, h, w, 24), dtype))
+        l8 = np.zeros((B, h, w, 8), np.float32)
+        l8[..., :6] = flat_logits[:, off:off + n].reshape(B, h, w, 6)
+        lg.append(dev(l8, dtype))
+        off += n
+    return bx, lg
+
+
 def nchw(x):
     return x.permute(0, 3, 1, 2)
 
