@@ -317,6 +317,24 @@ int mpn_dwconv_bwd_fused(const void* x, const void* dy, const float* w, void* dx
 int mpn_dwconv_bwd_fused_s2(const void* x, const void* dy, const float* w, void* dx, float* wpart, int N, int H, int W, int C,
                             int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean,
                             const float* invstd, float* bn_part, const void* addend, mpn_stream_t stream);
+/* ... with the backward APPLY pass of the depthwise conv's OWN batch-norm folded into the loads of dy (16-bit storage;
+ * mpn_dwconv_bwd_fused_apply_supported == 1: the shapes of mpn_dwconv_bwd_fused_supported, 0 for f32): g [dy's shape] = the gradient that
+ * mpn_bn_bwd_apply would turn into dy in place, y_raw = the conv's raw output (same shape), ap_* that batch-norm's affine, saved
+ * statistics and the k1 / k2 of mpn_bn_bwd_finalize. dx, wpart and bn_part are those of mpn_bn_bwd_apply followed by
+ * mpn_dwconv_bwd_fused[_s2], bit for bit; g and y_raw are not written. CONTRACT: g is already zero where ap_act blocks
+ * y_raw * ap_scale + ap_shift - the producers that reduce for this batch-norm (mpn_conv_bwd_data_bn, mpn_conv1x1_bwd_fused) write it
+ * so; the walk does not repeat the test (ap_shift and ap_act describe the batch-norm and are not read). */
+int mpn_dwconv_bwd_fused_apply_supported(int N, int H, int W, int C, int stride, int dtype);
+int mpn_dwconv_bwd_fused_apply(const void* x, const void* g, const void* y_raw, const float* w, void* dx, float* wpart, int N, int H,
+                               int W, int C, int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean,
+                               const float* invstd, float* bn_part, const float* ap_scale, const float* ap_shift,
+                               const float* ap_mean, const float* ap_invstd, const float* ap_k1, const float* ap_k2, int ap_act,
+                               mpn_stream_t stream);
+int mpn_dwconv_bwd_fused_s2_apply(const void* x, const void* g, const void* y_raw, const float* w, void* dx, float* wpart, int N, int H,
+                                  int W, int C, int dtype, const float* in_scale, const float* in_shift, int in_act,
+                                  const float* mean, const float* invstd, float* bn_part, const void* addend, const float* ap_scale,
+                                  const float* ap_shift, const float* ap_mean, const float* ap_invstd, const float* ap_k1,
+                                  const float* ap_k2, int ap_act, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * K1+K2  `2*x-1` + Conv2d_0 (3x3 stride 2 'SAME', 3 -> C0) fused

@@ -513,6 +513,9 @@ __device__ __forceinline__ void bn_bwd_apply_body(
             for (int j = 0; j < VE; ++j) {
                 const float pre = f[j] * sc[j] + sh[j];
                 const float g = (pre > lo && pre < hi) ? d[j] : 0.f;
+                // (DyApply in dwconv_walk.h reproduces this line AS COMPILED in bn_bwd_apply_kernel<bf16_t> - two nested FMAs, except channels
+                //  6, 7 of the vectors u = 0, 1, 3, which the vectoriser leaves as separate multiplies and adds; tests/test_dw_bwd_apply_gpu.py
+                //  fails when a change here or a compiler moves that)
                 d[j] = sc[j] * g + (cb[j] * f[j] + cc[j]);
             }
             if (add_ch0 != nullptr && vg == 0 && ii < nvec) d[0] += add_ch0[ii / cvec];

@@ -60,6 +60,14 @@ struct DwParams {
     float* wpart;       // fused backward (dwconv_bwd_*_kernel): the weight gradient's partial slab [units][9][C] (part: the fused reduction's)
     int swr;            // forward sliding window: output rows per strip (0: sw_rows(OH)); shorter strips where a launch without
                         // statistics would leave CUs idle (batch-1 inference: 13 launches of ~16 us each at 640 x 640)
+    // fused backward with the conv's OWN batch-norm backward apply on load (APPLY): dy is then the gradient BEFORE that pass
+    // (already masked by that batch-norm's activation), ap_y the conv's raw output (dy's shape)
+    const void* ap_y;
+    const float* ap_scale;
+    const float* ap_mean;
+    const float* ap_invstd;
+    const float* ap_k1;
+    const float* ap_k2;
 };
 
 __device__ __forceinline__ void load4(const float* p, float (&f)[4]) {
@@ -515,7 +523,13 @@ __global__ __launch_bounds__(kThreads) void dwconv_wgrad_sw2_kernel(const DwPara
 // p.x: raw input of the depthwise conv (= the fed layer's raw conv output) with its batch-norm affine in_scale / in_shift /
 // in_act (the mask test of the reduction is the same expression); p.dy: dY; p.y: dA; p.wpart: weight partials [units][9][C];
 // BNR: p.part [units][2][C] with p.bnr.mean / p.bnr.invstd.
-template <typename T, bool BNR>
+// APPLY (16-bit storage): p.dy is the gradient BEFORE the apply pass of this conv's own batch-norm; every piece that enters the window
+// becomes what that pass would have stored (DyApply, from the raw output p.ap_y at the same pixel), halo columns and the rows above
+// and below the strip included, and is zeroed outside the image afterwards as before. ONE raw-output row is in flight, requested
+// when the row before it has entered the window - a whole step ahead of its use, and before that step's dY and input requests, so
+// that waiting for it leaves those in flight. Three rows rotating with the dY rows (24 registers, with the 12 of constants) gave
+// 256 VGPRs + 20 AGPRs, one wave per SIMD; so did the window kept as packed storage values and unpacked at use (256 + 28).
+template <typename T, bool BNR, bool APPLY = false>
 __global__ __launch_bounds__(kThreads) void dwconv_bwd_sw2_kernel(const DwParams p, int ncg, int cols, int xblocks, int yblocks, int rows) {
     __shared__ __attribute__((aligned(16))) float red[9 * kThreads * 4];   // [tap][thread][4 channels]; afterwards [thread][8] of the reduction
     const SwLane l = sw_lane<2, true>(p.C, p.W, ncg, cols, xblocks, yblocks, p.cblocks);
@@ -536,7 +550,14 @@ __global__ __launch_bounds__(kThreads) void dwconv_bwd_sw2_kernel(const DwParams
     const long long img_off = (long long)l.img * p.H * p.W * p.C + l.cc;
     const T* ximg = reinterpret_cast<const T*>(p.x) + img_off;
     const T* dimg = reinterpret_cast<const T*>(p.dy) + img_off;
-    WinCols<T, 4> win;                                                 // (one set of columns for both tensors)
+    DyApply<T> ap;
+    const T* yimg = nullptr;
+    if constexpr (APPLY) {
+        ap.load(p.ap_scale, p.ap_mean, p.ap_invstd, p.ap_k1, p.ap_k2, l.cc);
+        yimg = reinterpret_cast<const T*>(p.ap_y) + img_off;
+    }
+    constexpr int NY = APPLY ? 4 : 1;
+    WinCols<T, 4> win;                                                 // (one set of columns for all tensors)
     win.init(l.ox - 1, l.ok, p.H, p.W, p.C);
     // (the zero-selects test a copy of their own: with WinCols' flags the optimiser lists the weight gradient's products in another
     //  order, another one of each pair is then fused into the sum, and the last bit of the weight partials changes)
@@ -544,15 +565,19 @@ __global__ __launch_bounds__(kThreads) void dwconv_bwd_sw2_kernel(const DwParams
 #pragma unroll
     for (int k = 0; k < 4; ++k) xok[k] = l.ok && l.ox - 1 + k >= 0 && l.ox - 1 + k < p.W;
     // a dY row into the window (zeros outside the image)
+    Raw4<T> yr[NY];                                                    // APPLY: the raw output at the next dY row's pieces
     auto dy_row = [&](const Raw4<T> (&r)[4], int iy, f32x2_t (&a)[4][2]) {
         const bool rowok = iy >= 0 && iy < p.H;
+        const unsigned erow = (unsigned)img_off + (unsigned)min(max(iy, 0), p.H - 1) * (unsigned)win.rstep;   // (the row win.load() took)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float f[4];
             raw_unpack(r[k], f);
+            if constexpr (APPLY) ap.apply(f, yr[k], erow + (unsigned)win.off[k]);
             zero_unless(rowok && xok[k], f);
             store_pairs(a[k], f);
         }
+        if constexpr (APPLY) win.load(yr, yimg, iy + 1);
     };
     // the activated input row (always inside the image: the strip's own rows; columns outside are the activated tensor's zero padding)
     auto in_row = [&](const Raw4<T> (&r)[4], f32x2_t (&a)[4][2]) {
@@ -605,6 +630,7 @@ __global__ __launch_bounds__(kThreads) void dwconv_bwd_sw2_kernel(const DwParams
     win.load(da, dimg, oy_begin - 1);
     win.load(db, dimg, oy_begin);
     win.load(dc, dimg, oy_begin + 1);
+    if constexpr (APPLY) win.load(yr, yimg, oy_begin - 1);
     win.load(xa, ximg, oy_begin);
     win.load(xb, ximg, oy_begin + 1);
     win.load(xc, ximg, oy_begin + 2);
@@ -768,7 +794,9 @@ __global__ __launch_bounds__(kThreads) void dwconv_dgrad_s2_sw_kernel(const T* _
 // separate launches read the input once for the weight gradient and once more for the reduction, and dY twice.
 // p.x: raw input with its batch-norm affine in_scale / in_shift / in_act; p.dy: dY [N,OH,OW,C]; p.y: dA [N,H,W,C]; p.wpart: weight
 // partials [units][9][C]; BNR: p.part [units][2][C] with p.bnr.mean / p.bnr.invstd; ADD: p.addend (dA's shape).
-template <typename T, bool BNR, bool ADD>
+// APPLY: as in dwconv_bwd_sw2_kernel - p.dy before the apply pass of this conv's own batch-norm, applied to both pieces of a dY row
+// (left neighbour and centre) from the raw output p.ap_y on their way into the window; one raw-output row in flight.
+template <typename T, bool BNR, bool ADD, bool APPLY = false>
 __global__ __launch_bounds__(kThreads) void dwconv_bwd_s2_kernel(const DwParams p, int ncg, int cols, int xblocks, int yblocks, int rows) {
     __shared__ __attribute__((aligned(16))) float red[9 * kThreads * 4];   // [tap][thread][4 channels]; afterwards [thread][8] of the reduction
     const int H = p.H, W = p.W, C = p.C, OH = p.OH, OW = p.OW;
@@ -789,24 +817,43 @@ __global__ __launch_bounds__(kThreads) void dwconv_bwd_s2_kernel(const DwParams 
     const bool right_ok = l.ok && 2 * l.ox + 2 < W;
     const bool left_ok = l.ox > 0;
     const T* dyimg = reinterpret_cast<const T*>(p.dy) + ((long long)l.img * OH * OW) * C + l.cc;
+    DyApply<T> ap;
+    if constexpr (APPLY) ap.load(p.ap_scale, p.ap_mean, p.ap_invstd, p.ap_k1, p.ap_k2, l.cc);
+    // (the raw output is addressed from dY's row pointer by the two tensors' uniform distance: a base pointer of its own is two more
+    //  registers per lane, and the walk with addend and reduction then no longer runs two waves per SIMD)
+    const long long ydist = APPLY ? reinterpret_cast<const char*>(p.ap_y) - reinterpret_cast<const char*>(p.dy) : 0;
+    constexpr int NY = APPLY ? 2 : 1;
     const int off_c = l.ox * C, off_l = (left_ok ? l.ox - 1 : 0) * C;
     auto dy_load = [&](Raw4<T> (&r)[2], int a) {
         const T* rowp = dyimg + (long long)min(max(a, 0), OH - 1) * OW * C;
         raw_load(r[0], rowp + off_l);
         raw_load(r[1], rowp + off_c);
     };
+    Raw4<T> y[NY];   // APPLY: the raw output at the pieces of the NEXT dY row to enter the window (one row in flight, as in dwconv_bwd_sw2_kernel)
+    auto y_load = [&](int a) {
+        if constexpr (APPLY) {
+            const T* rowp = dyimg + (long long)min(max(a, 0), OH - 1) * OW * C;
+            raw_load(y[0], reinterpret_cast<const T*>(reinterpret_cast<const char*>(rowp + off_l) + ydist));
+            raw_load(y[1], reinterpret_cast<const T*>(reinterpret_cast<const char*>(rowp + off_c) + ydist));
+        }
+    };
     auto dy_cvt = [&](const Raw4<T> (&r)[2], int a, f32x2_t (&v)[2][2]) {   // [left, centre][channel pair]; zero outside
         if (a < 0) {
             v[0][0] = v[0][1] = v[1][0] = v[1][1] = (f32x2_t){0.f, 0.f};
+            y_load(a + 1);
             return;
         }
+        const unsigned erow = (unsigned)(l.img * OH * OW * C + l.cc) + (unsigned)min(a, OH - 1) * (unsigned)(OW * C);   // (the row dy_load() took)
         float f[4];
         raw_unpack(r[0], f);
+        if constexpr (APPLY) ap.apply(f, y[0], erow + (unsigned)off_l);
 #pragma unroll
         for (int j = 0; j < 4; ++j) f[j] = left_ok ? f[j] : 0.f;   // (spelled out: through zero_unless() the bf16 kernels take 6 - 10 VGPRs more)
         v[0][0] = (f32x2_t){f[0], f[1]}; v[0][1] = (f32x2_t){f[2], f[3]};
         raw_unpack(r[1], f);
+        if constexpr (APPLY) ap.apply(f, y[1], erow + (unsigned)off_c);
         v[1][0] = (f32x2_t){f[0], f[1]}; v[1][1] = (f32x2_t){f[2], f[3]};
+        y_load(a + 1);
     };
     const T* ximg = reinterpret_cast<const T*>(p.x) + (long long)l.img * H * W * C + l.cc;
     const int xo0 = 2 * l.ox * C, xo1 = xo0 + C, xo2 = right_ok ? xo0 + 2 * C : xo0;
@@ -889,6 +936,7 @@ __global__ __launch_bounds__(kThreads) void dwconv_bwd_s2_kernel(const DwParams 
     dy_load(ra, a_begin - 1);
     dy_load(rb, a_begin);
     dy_load(rc, a_begin + 1);
+    y_load(a_begin - 1);
     x_load(xa, 2 * a_begin);
     dy_cvt(ra, a_begin - 1, v0);
     dy_load(ra, a_begin + 2);
@@ -1409,6 +1457,89 @@ extern "C" int mpn_dwconv_bwd_fused_supported(int N, int H, int W, int C, int st
     return (d.ok && d.ncg == g.ncg && d.cols == g.cols && d.xblocks == g.xblocks && d.yblocks == g.yblocks && dg_rows(p.OH) == g.rows) ? 1 : 0;
 }
 
+// the operands of the fused walks' APPLY variants: the conv's raw output and its own batch-norm (k1 / k2 from mpn_bn_bwd_finalize)
+struct DwApplyArgs {
+    const void* y;
+    const float *scale, *shift, *mean, *invstd, *k1, *k2;
+    int act;
+};
+static void dw_set_apply(DwParams& p, const DwApplyArgs& a) {
+    p.ap_y = a.y; p.ap_scale = a.scale; p.ap_mean = a.mean; p.ap_invstd = a.invstd; p.ap_k1 = a.k1; p.ap_k2 = a.k2;
+}
+// the APPLY variants exist for the 16-bit storage types: the f32 walks are at 256 VGPRs without the extra rows
+template <typename T> constexpr bool kDwApply = !std::is_same<T, float>::value;
+
+static int dw_bwd_fused_s1(const char* who, const void* x, const void* dy, const float* w, void* dx, float* wpart, int N, int H, int W, int C,
+                           int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean, const float* invstd,
+                           float* bn_part, const DwApplyArgs* ap, mpn_stream_t stream) {
+    MPN_REQUIRE(ap ? mpn_dwconv_bwd_fused_apply_supported(N, H, W, C, 1, dtype) : mpn_dwconv_bwd_fused_supported(N, H, W, C, 1, dtype),
+                MPN_ERR_BAD_SHAPE, "%s: shape or type not supported (mpn_dwconv_bwd_fused%s_supported == 0)", who, ap ? "_apply" : "");
+    MPN_REQUIRE(x && dy && w && dx && wpart && in_scale && in_shift, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(bn_part == nullptr || (mean && invstd), MPN_ERR_BAD_ARG, "%s: the reduction needs mean and invstd", who);
+    MPN_REQUIRE(dx != dy && dx != x, MPN_ERR_BAD_ARG, "%s: dx must not alias an input", who);
+    MPN_REQUIRE(!ap || (ap->y && ap->scale && ap->shift && ap->mean && ap->invstd && ap->k1 && ap->k2), MPN_ERR_BAD_ARG,
+                "%s: null pointer (y_raw or its batch-norm)", who);
+    MPN_REQUIRE(!ap || dx != ap->y, MPN_ERR_BAD_ARG, "%s: dx must not alias an input", who);
+    DwParams p = {};
+    if (int rc = fill_params(p, N, H, W, C, 1, dtype)) return rc;
+    p.x = x; p.dy = dy; p.w = w; p.y = dx; p.wpart = wpart; p.part = bn_part;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act; p.bnr.mean = mean; p.bnr.invstd = invstd;
+    if (ap) dw_set_apply(p, *ap);
+    const DwWgSwGeom g = dw_wg_sw_geom(p);
+    p.cblocks = g.cblocks;
+    unsigned grid;
+    if (int rc = dw_grid((long long)g.units * g.cblocks, who, &grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MPN_DISPATCH_DTYPE(dtype, {
+        if (ap) {
+            if constexpr (kDwApply<T>) {
+                if (bn_part) dwconv_bwd_sw2_kernel<T, true, true><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+                else dwconv_bwd_sw2_kernel<T, false, true><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+            }
+        } else if (bn_part) dwconv_bwd_sw2_kernel<T, true><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+        else dwconv_bwd_sw2_kernel<T, false><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+    });
+    MPN_LAUNCH_CHECK();
+    return MPN_OK;
+}
+
+static int dw_bwd_fused_s2(const char* who, const void* x, const void* dy, const float* w, void* dx, float* wpart, int N, int H, int W, int C,
+                           int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean, const float* invstd,
+                           float* bn_part, const void* addend, const DwApplyArgs* ap, mpn_stream_t stream) {
+    MPN_REQUIRE(ap ? mpn_dwconv_bwd_fused_apply_supported(N, H, W, C, 2, dtype) : mpn_dwconv_bwd_fused_supported(N, H, W, C, 2, dtype),
+                MPN_ERR_BAD_SHAPE, "%s: shape or type not supported (mpn_dwconv_bwd_fused%s_supported == 0)", who, ap ? "_apply" : "");
+    MPN_REQUIRE(x && dy && w && dx && wpart && in_scale && in_shift, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(bn_part == nullptr || (mean && invstd), MPN_ERR_BAD_ARG, "%s: the reduction needs mean and invstd", who);
+    MPN_REQUIRE(dx != dy && dx != x && dx != addend, MPN_ERR_BAD_ARG, "%s: dx must not alias an input", who);
+    MPN_REQUIRE(!ap || (ap->y && ap->scale && ap->shift && ap->mean && ap->invstd && ap->k1 && ap->k2), MPN_ERR_BAD_ARG,
+                "%s: null pointer (y_raw or its batch-norm)", who);
+    MPN_REQUIRE(!ap || dx != ap->y, MPN_ERR_BAD_ARG, "%s: dx must not alias an input", who);
+    DwParams p = {};
+    if (int rc = fill_params(p, N, H, W, C, 2, dtype)) return rc;
+    p.x = x; p.dy = dy; p.w = w; p.y = dx; p.wpart = wpart; p.part = bn_part; p.addend = addend;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act; p.bnr.mean = mean; p.bnr.invstd = invstd;
+    if (ap) dw_set_apply(p, *ap);
+    const DwWgSwGeom g = dw_wg_sw_geom(p);
+    p.cblocks = g.cblocks;
+    unsigned grid;
+    if (int rc = dw_grid((long long)g.units * g.cblocks, who, &grid)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MPN_DISPATCH_DTYPE(dtype, dw_with_bnr_add(bn_part != nullptr, addend != nullptr, [&](auto B, auto A) {
+        if (ap) {
+            if constexpr (kDwApply<T>)
+                dwconv_bwd_s2_kernel<T, decltype(B)::value, decltype(A)::value, true><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+        } else dwconv_bwd_s2_kernel<T, decltype(B)::value, decltype(A)::value><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
+    }));
+    MPN_LAUNCH_CHECK();
+    return MPN_OK;
+}
+
+/* 1 when mpn_dwconv_bwd_fused_apply (stride 1) / mpn_dwconv_bwd_fused_s2_apply (stride 2) takes this shape and type: the shapes of
+ * mpn_dwconv_bwd_fused_supported in 16-bit storage (the f32 walks have no registers left for the extra rows: they keep the separate pass) */
+extern "C" int mpn_dwconv_bwd_fused_apply_supported(int N, int H, int W, int C, int stride, int dtype) {
+    return dtype != MPN_F32 ? mpn_dwconv_bwd_fused_supported(N, H, W, C, stride, dtype) : 0;
+}
+
 /* Stride-1 depthwise backward in ONE pass over dy, x and dx (tf.nn.depthwise_conv2d's two gradients, mobilenet_v1.py:101, + the
  * batch-norm backward reduction of the layer that produced x): dx = data gradient [N,H,W,C]; wpart
  * [mpn_dwconv_wgrad_num_parts][9][C] = weight-gradient partials over act(x * in_scale + in_shift) (finish with mpn_reduce_partials);
@@ -1418,26 +1549,8 @@ extern "C" int mpn_dwconv_bwd_fused_supported(int N, int H, int W, int C, int st
 extern "C" int mpn_dwconv_bwd_fused(const void* x, const void* dy, const float* w, void* dx, float* wpart, int N, int H, int W, int C,
                                     int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean,
                                     const float* invstd, float* bn_part, mpn_stream_t stream) {
-    MPN_REQUIRE(mpn_dwconv_bwd_fused_supported(N, H, W, C, 1, dtype), MPN_ERR_BAD_SHAPE,
-                "dwconv_bwd_fused: shape not supported (mpn_dwconv_bwd_fused_supported == 0)");
-    MPN_REQUIRE(x && dy && w && dx && wpart && in_scale && in_shift, MPN_ERR_BAD_ARG, "dwconv_bwd_fused: null pointer");
-    MPN_REQUIRE(bn_part == nullptr || (mean && invstd), MPN_ERR_BAD_ARG, "dwconv_bwd_fused: the reduction needs mean and invstd");
-    MPN_REQUIRE(dx != dy && dx != x, MPN_ERR_BAD_ARG, "dwconv_bwd_fused: dx must not alias an input");
-    DwParams p = {};
-    if (int rc = fill_params(p, N, H, W, C, 1, dtype)) return rc;
-    p.x = x; p.dy = dy; p.w = w; p.y = dx; p.wpart = wpart; p.part = bn_part;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act; p.bnr.mean = mean; p.bnr.invstd = invstd;
-    const DwWgSwGeom g = dw_wg_sw_geom(p);
-    p.cblocks = g.cblocks;
-    unsigned grid;
-    if (int rc = dw_grid((long long)g.units * g.cblocks, "dwconv_bwd_fused", &grid)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    MPN_DISPATCH_DTYPE(dtype, {
-        if (bn_part) dwconv_bwd_sw2_kernel<T, true><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
-        else dwconv_bwd_sw2_kernel<T, false><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
-    });
-    MPN_LAUNCH_CHECK();
-    return MPN_OK;
+    return dw_bwd_fused_s1("dwconv_bwd_fused", x, dy, w, dx, wpart, N, H, W, C, dtype, in_scale, in_shift, in_act, mean, invstd, bn_part,
+                           nullptr, stream);
 }
 
 /* The stride-2 counterpart of mpn_dwconv_bwd_fused (even H and W; mpn_dwconv_bwd_fused_supported(.., stride 2, ..) == 1): x [N,H,W,C] the
@@ -1448,23 +1561,32 @@ extern "C" int mpn_dwconv_bwd_fused(const void* x, const void* dy, const float* 
 extern "C" int mpn_dwconv_bwd_fused_s2(const void* x, const void* dy, const float* w, void* dx, float* wpart, int N, int H, int W, int C,
                                        int dtype, const float* in_scale, const float* in_shift, int in_act, const float* mean,
                                        const float* invstd, float* bn_part, const void* addend, mpn_stream_t stream) {
-    MPN_REQUIRE(mpn_dwconv_bwd_fused_supported(N, H, W, C, 2, dtype), MPN_ERR_BAD_SHAPE,
-                "dwconv_bwd_fused_s2: shape not supported (mpn_dwconv_bwd_fused_supported == 0)");
-    MPN_REQUIRE(x && dy && w && dx && wpart && in_scale && in_shift, MPN_ERR_BAD_ARG, "dwconv_bwd_fused_s2: null pointer");
-    MPN_REQUIRE(bn_part == nullptr || (mean && invstd), MPN_ERR_BAD_ARG, "dwconv_bwd_fused_s2: the reduction needs mean and invstd");
-    MPN_REQUIRE(dx != dy && dx != x && dx != addend, MPN_ERR_BAD_ARG, "dwconv_bwd_fused_s2: dx must not alias an input");
-    DwParams p = {};
-    if (int rc = fill_params(p, N, H, W, C, 2, dtype)) return rc;
-    p.x = x; p.dy = dy; p.w = w; p.y = dx; p.wpart = wpart; p.part = bn_part; p.addend = addend;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act; p.bnr.mean = mean; p.bnr.invstd = invstd;
-    const DwWgSwGeom g = dw_wg_sw_geom(p);
-    p.cblocks = g.cblocks;
-    unsigned grid;
-    if (int rc = dw_grid((long long)g.units * g.cblocks, "dwconv_bwd_fused_s2", &grid)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    MPN_DISPATCH_DTYPE(dtype, dw_with_bnr_add(bn_part != nullptr, addend != nullptr, [&](auto B, auto A) {
-        dwconv_bwd_s2_kernel<T, decltype(B)::value, decltype(A)::value><<<grid, kThreads, 0, st>>>(p, g.ncg, g.cols, g.xblocks, g.yblocks, g.rows);
-    }));
-    MPN_LAUNCH_CHECK();
-    return MPN_OK;
+    return dw_bwd_fused_s2("dwconv_bwd_fused_s2", x, dy, w, dx, wpart, N, H, W, C, dtype, in_scale, in_shift, in_act, mean, invstd, bn_part,
+                           addend, nullptr, stream);
+}
+
+/* mpn_dwconv_bwd_fused / _s2 with the backward APPLY pass of the depthwise conv's OWN batch-norm folded into the loads of dy
+ * (mpn_dwconv_bwd_fused_apply_supported == 1): g [dy's shape] = the gradient that mpn_bn_bwd_apply would turn into dy in place, y_raw
+ * the conv's raw output (same shape), ap_* that batch-norm's affine, saved statistics and the k1 / k2 of mpn_bn_bwd_finalize. dx, wpart
+ * and bn_part come out bit for bit as from mpn_bn_bwd_apply followed by mpn_dwconv_bwd_fused[_s2]; g and y_raw are not written.
+ * CONTRACT: g is already zero where ap_act blocks y_raw * ap_scale + ap_shift (the producers that reduce for this batch-norm -
+ * mpn_conv_bwd_data_bn, mpn_conv1x1_bwd_fused - write it so); the walk does not repeat that test and reads neither ap_shift nor ap_act. */
+extern "C" int mpn_dwconv_bwd_fused_apply(const void* x, const void* g, const void* y_raw, const float* w, void* dx, float* wpart, int N,
+                                          int H, int W, int C, int dtype, const float* in_scale, const float* in_shift, int in_act,
+                                          const float* mean, const float* invstd, float* bn_part, const float* ap_scale,
+                                          const float* ap_shift, const float* ap_mean, const float* ap_invstd, const float* ap_k1,
+                                          const float* ap_k2, int ap_act, mpn_stream_t stream) {
+    const DwApplyArgs ap = {y_raw, ap_scale, ap_shift, ap_mean, ap_invstd, ap_k1, ap_k2, ap_act};
+    return dw_bwd_fused_s1("dwconv_bwd_fused_apply", x, g, w, dx, wpart, N, H, W, C, dtype, in_scale, in_shift, in_act, mean, invstd, bn_part,
+                           &ap, stream);
+}
+
+extern "C" int mpn_dwconv_bwd_fused_s2_apply(const void* x, const void* g, const void* y_raw, const float* w, void* dx, float* wpart, int N,
+                                             int H, int W, int C, int dtype, const float* in_scale, const float* in_shift, int in_act,
+                                             const float* mean, const float* invstd, float* bn_part, const void* addend,
+                                             const float* ap_scale, const float* ap_shift, const float* ap_mean, const float* ap_invstd,
+                                             const float* ap_k1, const float* ap_k2, int ap_act, mpn_stream_t stream) {
+    const DwApplyArgs ap = {y_raw, ap_scale, ap_shift, ap_mean, ap_invstd, ap_k1, ap_k2, ap_act};
+    return dw_bwd_fused_s2("dwconv_bwd_fused_s2_apply", x, g, w, dx, wpart, N, H, W, C, dtype, in_scale, in_shift, in_act, mean, invstd,
+                           bn_part, addend, &ap, stream);
 }

@@ -224,6 +224,59 @@ template <typename T> struct BnReduce {
         q01 += g01 * (x01 * is01 + nm01); q23 += g23 * (x23 * is23 + nm23);
     }
 };
+// The batch-norm backward APPLY pass of the depthwise conv's OWN batch-norm on the way into a gradient walk's dY window: the piece
+// becomes what mpn_bn_bwd_apply would have stored over it and the walk read back, bit for bit, rounded to the storage type.
+// NO mask test: g is already zero where that batch-norm's activation blocks (the producers of g that reduce for it mask with the
+// same expression on the same y), so the test of the separate pass changes nothing - shift, lo and hi would be 6 registers the
+// walks do not have.
+// "What the separate pass would have stored" is what bn_bwd_apply_kernel<bf16_t> (bn.hip) computes AS COMPILED, and that is not one
+// expression: sc * g + (cb * y + cc) is two nested fused multiply-adds for channels 0 .. 5 of a 16-byte vector, and for channels
+// 6, 7 of the third of the four vectors a thread takes per iteration (vector index / 256 % 4 == 2); in the other three the
+// vectoriser left that pair out of the packed operations and it is evaluated as (cc + cb * y) + sc * g with every product and sum
+// rounded. The two differ in the last bit of an f32, i.e. in the stored bf16 of about one element in 10^5 - and behind such an
+// element the whole backward pass below it. The walk therefore evaluates the pair both ways in the lanes that hold channels 6, 7
+// and selects by the piece's element index; tests/test_dw_bwd_apply_gpu.py pins the equality (it fails when a compiler lays that
+// kernel out differently - then this selection has to follow).
+template <typename T> struct DyApply {
+    f32x2_t sc01, sc23, cb01, cb23, cc01, cc23;
+    bool pair67;   // the lane's second pair is channels 6, 7 of a 16-byte vector
+    __device__ __forceinline__ void load(const float* scale, const float* mean, const float* invstd, const float* k1, const float* k2, int cc) {
+        const float4 s4 = *reinterpret_cast<const float4*>(scale + cc), m4 = *reinterpret_cast<const float4*>(mean + cc);
+        const float4 i4 = *reinterpret_cast<const float4*>(invstd + cc);
+        const float4 a4 = *reinterpret_cast<const float4*>(k1 + cc), b4 = *reinterpret_cast<const float4*>(k2 + cc);
+        const float ss[4] = {s4.x, s4.y, s4.z, s4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, ii[4] = {i4.x, i4.y, i4.z, i4.w};
+        const float aa[4] = {a4.x, a4.y, a4.z, a4.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w};
+        float cb[4], cc_[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {   // (the expressions of bn_bwd_apply_body: they contract alike - aa - (mm * ii) * bb is one fma)
+            cb[j] = -ss[j] * bb[j] * ii[j];
+            cc_[j] = -ss[j] * (aa[j] - mm[j] * ii[j] * bb[j]);
+        }
+        sc01 = (f32x2_t){ss[0], ss[1]}; sc23 = (f32x2_t){ss[2], ss[3]};
+        cb01 = (f32x2_t){cb[0], cb[1]}; cb23 = (f32x2_t){cb[2], cb[3]};
+        cc01 = (f32x2_t){cc_[0], cc_[1]}; cc23 = (f32x2_t){cc_[2], cc_[3]};
+        pair67 = (cc & 4) != 0;
+    }
+    static __device__ __forceinline__ f32x2_t unfused(f32x2_t sc, f32x2_t g, f32x2_t cb, f32x2_t y, f32x2_t cc) {
+#pragma clang fp contract(off)
+        const f32x2_t t = cb * y, u = sc * g;
+        return (cc + t) + u;
+    }
+    // f: the unpacked piece of g, in place; yr: the conv's raw output at the same pixel; elem: the piece's element index in the
+    // tensor (its low 32 bits)
+    __device__ __forceinline__ void apply(float (&f)[4], const Raw4<T>& yr, unsigned elem) const {
+        f32x2_t y01, y23;
+        raw_unpack2(yr, y01, y23);
+        const f32x2_t g01 = {f[0], f[1]}, g23 = {f[2], f[3]};
+        const f32x2_t o01 = __builtin_elementwise_fma(sc01, g01, __builtin_elementwise_fma(cb01, y01, cc01));
+        f32x2_t o23 = __builtin_elementwise_fma(sc23, g23, __builtin_elementwise_fma(cb23, y23, cc23));
+        const f32x2_t v23 = unfused(sc23, g23, cb23, y23, cc23);
+        if (pair67 && ((elem >> 11) & 3u) != 2u) o23 = v23;   // (elem >> 3: the 16-byte vector; / 256 % 4: which of the thread's four)
+        const f32x2_t r01 = round_storage<T>(o01), r23 = round_storage<T>(o23);
+        f[0] = r01.x; f[1] = r01.y; f[2] = r23.x; f[3] = r23.y;
+    }
+};
+
 // block epilogue of the sums: the block's columns summed per 4-channel group in a fixed order -> row `l.unit` of part [units][2][C].
 // red: kThreads * 8 floats of LDS, [thread][8] (barrier first where it held something else).
 __device__ __forceinline__ void write_sums_row(float* red, const SwLane& l, int ncg, int cols, int C, float* part, f32x2_t s01, f32x2_t s23,

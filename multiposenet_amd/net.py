@@ -212,6 +212,9 @@ class KeypointNet(ModelState):
         # depthwise data gradients also reduce for the batch-norm they feed (mpn_dwconv_bwd_data_bn and the one-walk backward,
         # mpn_dwconv_bwd_fused[_s2]); False: the separate reduction, the reference of the tests
         self.fuse_dw_bn = True
+        # the fused depthwise walks also apply the backward of the depthwise conv's own batch-norm on load (16-bit storage);
+        # False: the separate apply pass, the reference of the tests
+        self.fuse_dw_apply = True
         # ... and so do the subnet's 3x3 data gradients (mpn_conv_bwd_data_bn_grouped: bn1 under conv2's, p{l}_batch_norm under
         # conv1's); set before the first backward pass of a shape (the finalize tables are built once)
         self.fuse_conv_bn = True
@@ -667,18 +670,40 @@ class KeypointNet(ModelState):
                 ops.add_inplace(dA, g["c"][feature])
             # (block 13's rows, if any, come from lateral5's data gradient, which sums g * x with the raw x; the depthwise data
             #  gradients sum g * xhat themselves)
-            dY = self._backward_pointwise(b, g, sp, slab, i, dA, reduced, raw=i == last)
-            dA, reduced, lateral_added = self._backward_depthwise(b, g, sp, slab, i, dY)
+            dY, applied = self._backward_pointwise(b, g, sp, slab, i, dA, reduced, raw=i == last, fold=self._dw_folds_apply(b, g, i))
+            dA, reduced, lateral_added = self._backward_depthwise(b, g, sp, slab, i, dY, apply=not applied)
         if phase == 1:
             g["bb_chain"] = (dA, reduced, lateral_added)
             return
         ops.bn_backward(self.stem_bn, g["stem"], b["stem"], sp, reduced_parts=reduced)
         ops.stem_conv_bwd_weight(images, g["stem"], self.stem_dw, slab[id(self.stem_dw)], reduce=False)
 
-    def _backward_pointwise(self, b, g, sp, slab, i, dA, reduced, raw):
+    def _dw_lateral(self, g, i):
+        """The FPN lateral's gradient into the feature map that block i's depthwise conv reads (None: it feeds no lateral)."""
+        return g["c"][FEATURE_BLOCKS[self.blocks[i - 1]["i"]]] if i > 0 and self.blocks[i - 1]["i"] in FEATURE_BLOCKS else None
+
+    def _dw_walks_fused(self, b, g, i):
+        """Block i's depthwise backward is ONE walk (ops.dwconv_bwd_fused): at stride 1 only where no lateral's gradient is to
+        be added."""
+        s, (N, _, _, C) = self.blocks[i]["stride"], b["dw"][i].shape
+        return (self.fuse_dw_bn and (s == 2 or self._dw_lateral(g, i) is None)
+                and ops.dwconv_bwd_fused_supported(N, *b["hw"][i], C, s, self.dtype))
+
+    def _dw_folds_apply(self, b, g, i):
+        """That walk also takes the apply pass of the depthwise batch-norm (on load, instead of a launch that rewrites dY in
+        place) wherever the walk has the variant (16-bit storage). No policy by shape: each of the backbone's nine layer shapes
+        at batch 32 @ 512 x 512 is faster folded than as apply launch + walk, by 4 - 29 us against a spread of 0.2 - 5 us
+        (tools/time_dw_bwd.py --apply, profiles/dw_apply_on_load.txt)."""
+        s, (N, _, _, C) = self.blocks[i]["stride"], b["dw"][i].shape
+        return (self.fuse_dw_apply and self._dw_walks_fused(b, g, i)
+                and ops.dwconv_bwd_fused_apply_supported(N, *b["hw"][i], C, s, self.dtype))
+
+    def _backward_pointwise(self, b, g, sp, slab, i, dA, reduced, raw, fold=False):
         """Block i's pointwise layer: dA (gradient w.r.t. its activated output; `reduced` rows of its batch-norm's reduction
-        already in `sp`, `raw` sums) -> the gradient w.r.t. the depthwise layer's raw output below, returned; the weight
-        gradient into its slab."""
+        already in `sp`, `raw` sums) -> the gradient w.r.t. the depthwise layer's raw output below; the weight gradient into its
+        slab. Returns (that gradient, whether the depthwise batch-norm's apply pass ran over it). fold: the depthwise walk can
+        apply on load - the pass is then left to it when this layer's data gradient reduced for the depthwise batch-norm, i.e.
+        wrote the gradient already masked by its activation (the walk does not repeat the mask test)."""
         blk = self.blocks[i]
         pw, x, dY = blk["pw"], b["dw"][i], g["dw"][i]
         # the thin layers: weight gradient, data gradient and the reduction for the depthwise batch-norm below in ONE pass over
@@ -699,26 +724,30 @@ class KeypointNet(ModelState):
                     rows = ops.conv_bwd_data_bn(dA, pw.packed.bwd, pw.cin, 1, blk["dw_bn"], x, dY, sp)
                 else:
                     ops.conv_fwd(dA, pw.packed.bwd, pw.cin, 1, None, out=dY)
-        ops.bn_backward(blk["dw_bn"], dY, x, sp, reduced_parts=rows, raw=True)
-        return dY
+        applied = not (fold and rows > 0)
+        ops.bn_backward(blk["dw_bn"], dY, x, sp, reduced_parts=rows, raw=True, apply=applied)
+        return dY, applied
 
-    def _backward_depthwise(self, b, g, sp, slab, i, dY):
-        """Block i's depthwise layer: dY (gradient w.r.t. its raw output, through its batch-norm) -> the gradient w.r.t. the
-        activated output of the layer below; the weight gradient into its slab. Returns (that gradient, the rows already reduced
-        for the batch-norm below - 0: none, whether the FPN lateral's gradient is already added to it)."""
+    def _backward_depthwise(self, b, g, sp, slab, i, dY, apply=False):
+        """Block i's depthwise layer: dY (gradient w.r.t. its raw output, through its batch-norm; apply: BEFORE that batch-norm's
+        apply pass, which the fused walk then does on load) -> the gradient w.r.t. the activated output of the layer below; the
+        weight gradient into its slab. Returns (that gradient, the rows already reduced for the batch-norm below - 0: none,
+        whether the FPN lateral's gradient is already added to it)."""
         blk = self.blocks[i]
         x, bn, dA = (b["pw"][i - 1], self.blocks[i - 1]["pw_bn"], g["pw"][i - 1]) if i > 0 else (b["stem"], self.stem_bn, g["stem"])
         N, hw, C, s = dA.shape[0], b["hw"][i], dA.shape[3], blk["stride"]
         # c2..c4 have two consumers (the next depthwise conv and an FPN lateral, mobilenet_v1.py:76-79): the lateral's gradient
         # is added inside the data-gradient kernel where it can be (stride-2 layers with even maps - all three at the
         # reference's input sizes), otherwise by add_inplace before the block below
-        lateral = g["c"][FEATURE_BLOCKS[self.blocks[i - 1]["i"]]] if i > 0 and self.blocks[i - 1]["i"] in FEATURE_BLOCKS else None
+        lateral = self._dw_lateral(g, i)
         # both gradients and the reduction for the batch-norm below in one walk over dY, x and dA (three tensor passes instead
-        # of five); at stride 1 only where no lateral's gradient is to be added
-        if self.fuse_dw_bn and (s == 2 or lateral is None) and ops.dwconv_bwd_fused_supported(N, *hw, C, s, self.dtype):
+        # of five)
+        if self._dw_walks_fused(b, g, i):
             _, reduced = ops.dwconv_bwd_fused(x, dY, blk["dw_w"], bn, None, out=dA, wpart=slab[id(blk["dw_dw"])], bn_part=sp,
-                                              reduce=False, stride=s, addend=lateral)
+                                              reduce=False, stride=s, addend=lateral, apply_bn=blk["dw_bn"] if apply else None,
+                                              y_raw=b["dw"][i] if apply else None)
             return dA, reduced, lateral is not None
+        assert not apply, "only the fused depthwise walk applies the batch-norm backward on load"
         ops.dwconv_bwd_weight(x, dY, s, bn.affine, blk["dw_dw"], slab[id(blk["dw_dw"])], reduce=False)
         late = lateral is not None and not ops.dwconv_bwd_data_add_supported(N, *hw, C, s, self.dtype)
         addend = None if late else lateral

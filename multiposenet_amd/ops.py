@@ -584,15 +584,29 @@ def dwconv_bwd_fused_supported(N, H, W, C, stride, dtype):
     return _lib.lib().mpn_dwconv_bwd_fused_supported(N, H, W, C, stride, _lib.dtype_code(dtype)) == 1
 
 
-def dwconv_bwd_fused(x, dy, w, bn, dw_out, out=None, wpart=None, bn_part=None, reduce=True, reduce_bn=True, stride=1, addend=None):
+def dwconv_bwd_fused_apply_supported(N, H, W, C, stride, dtype):
+    """True when dwconv_bwd_fused(apply_bn=...) takes this layer: the shapes of dwconv_bwd_fused_supported in 16-bit storage."""
+    return _lib.lib().mpn_dwconv_bwd_fused_apply_supported(N, H, W, C, stride, _lib.dtype_code(dtype)) == 1
+
+
+def dwconv_bwd_fused(x, dy, w, bn, dw_out, out=None, wpart=None, bn_part=None, reduce=True, reduce_bn=True, stride=1, addend=None,
+                     apply_bn=None, y_raw=None):
     """Stride-1 depthwise backward in one pass: x = the conv's RAW input (the raw output of the layer with batch-norm state `bn`,
     whose affine + activation the forward applied on load), dy = gradient w.r.t. the conv's output. Writes the data gradient to
     `out`, the weight-gradient partials to `wpart` (reduced into dw_out when reduce) and, when reduce_bn, the partial sums of
-    that batch-norm's backward reduction to `bn_part`; returns (out, rows) - pass rows to bn_backward(reduced_parts=rows)."""
+    that batch-norm's backward reduction to `bn_part`; returns (out, rows) - pass rows to bn_backward(reduced_parts=rows).
+    apply_bn / y_raw: the conv's OWN batch-norm state (k1 / k2 filled by its finalize) and raw output - dy is then the gradient
+    BEFORE that batch-norm's apply pass (bn_backward(..., apply=False)), already zero where its activation blocks, and the walk
+    applies it on load; dy is not written."""
     N, H, W, C = x.shape
     dc = _lib.dtype_code(x.dtype)
     if not dwconv_bwd_fused_supported(N, H, W, C, stride, x.dtype):
         raise ValueError("dwconv_bwd_fused: shape not supported")
+    if apply_bn is not None:
+        if not dwconv_bwd_fused_apply_supported(N, H, W, C, stride, x.dtype):
+            raise ValueError("dwconv_bwd_fused: apply_bn not supported for this shape or dtype")
+        if y_raw is None or y_raw.shape != dy.shape or y_raw.dtype != dy.dtype or not y_raw.is_contiguous():
+            raise ValueError("dwconv_bwd_fused: apply_bn needs y_raw of dy's shape and dtype")
     if addend is not None and (stride != 2 or addend.shape != x.shape or addend.dtype != x.dtype or not addend.is_contiguous()):
         raise ValueError("dwconv_bwd_fused: addend needs stride 2 and the result's shape and dtype")
     if out is None:
@@ -604,7 +618,13 @@ def dwconv_bwd_fused(x, dy, w, bn, dw_out, out=None, wpart=None, bn_part=None, r
         bn_part = _f32(rows * 2 * C, x.device)
     if wpart.numel() < rows * 9 * C or (reduce_bn and bn_part.numel() < rows * 2 * C):
         raise ValueError("dwconv_bwd_fused: partial slab too small")
-    if stride == 2:
+    ab = apply_bn
+    if ab is not None:
+        aps = (ptr(ab.scale), ptr(ab.shift), ptr(ab.mean), ptr(ab.invstd), ptr(ab.k1), ptr(ab.k2), int(ab.act))
+        name, add = ("mpn_dwconv_bwd_fused_s2_apply", (ptr(addend),)) if stride == 2 else ("mpn_dwconv_bwd_fused_apply", ())
+        call(name, ptr(x), ptr(dy), ptr(y_raw), ptr(w), ptr(out), ptr(wpart), N, H, W, C, dc, ptr(bn.scale), ptr(bn.shift), int(bn.act),
+             ptr(bn.mean), ptr(bn.invstd), ptr(bn_part) if reduce_bn else None, *add, *aps, stream_ptr())
+    elif stride == 2:
         call("mpn_dwconv_bwd_fused_s2", ptr(x), ptr(dy), ptr(w), ptr(out), ptr(wpart), N, H, W, C, dc, ptr(bn.scale), ptr(bn.shift),
              int(bn.act), ptr(bn.mean), ptr(bn.invstd), ptr(bn_part) if reduce_bn else None, ptr(addend), stream_ptr())
     else:
