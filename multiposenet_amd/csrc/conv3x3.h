@@ -1,5 +1,6 @@
 // 3x3 convolution, 16-bit storage, 256-pixel x 128-channel block tiles (conv3x3.hip). Shared with conv_mfma.hip, which
-// owns the C ABI entry points (mpn_conv_fwd, mpn_conv_fwd_grouped, the weight packers) and routes eligible layers here.
+// owns the C ABI entry points (mpn_conv_fwd[_grouped], mpn_conv_bwd_data_bn[_grouped], the weight packers), checks their jobs
+// (conv_check_job) and routes eligible layers here, their Jobs filled by its c3_fill_job.
 #pragma once
 #include "common.h"
 

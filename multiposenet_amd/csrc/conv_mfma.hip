@@ -876,88 +876,130 @@ static int launch_conv_rb(const ConvParams& p, int m_tiles, hipStream_t st) {
     return MPN_OK;
 }
 
-template <typename T, int TAPS, int BN>
-static int launch_conv(const ConvParams& p, int m_tiles, hipStream_t st) {
-    if (p.row_bytes == 256) return launch_conv_rb<T, TAPS, BN, 256>(p, m_tiles, st);
-    return launch_conv_rb<T, TAPS, BN, 128>(p, m_tiles, st);
+template <typename T, int TAPS>
+static int launch_conv(const ConvParams& p, int BN, int m_tiles, hipStream_t st) {
+    if (p.row_bytes == 256) return BN == 128 ? launch_conv_rb<T, TAPS, 128, 256>(p, m_tiles, st) : launch_conv_rb<T, TAPS, 64, 256>(p, m_tiles, st);
+    return BN == 128 ? launch_conv_rb<T, TAPS, 128, 128>(p, m_tiles, st) : launch_conv_rb<T, TAPS, 64, 128>(p, m_tiles, st);
 }
 
-static int conv_fill_params(ConvParams& p, const PackGeom& g, const void* x, const void* w_packed, void* y, int N, int H, int W,
-                            int Cin, int Cout, int x_stride, int y_stride, int ksize, const float* in_scale,
-                            const float* in_shift, int in_act, float* stats_part, const void* up_res) {
-    p.x = x; p.wp = w_packed; p.y = y;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act;
-    p.stats_part = stats_part; p.up_res = up_res;
-    p.bnr_x = nullptr; p.bnr_scale = nullptr; p.bnr_shift = nullptr; p.bnr_act = MPN_ACT_NONE; p.bnr_xs = 0;
+// One convolution as an entry point receives it, single or as job j of a group: the layer (shared by the jobs of a group) and the
+// job. Every entry point below builds these, has them CHECKED by conv_check_job (and conv_check_bnr) and FILLED into the kernel's
+// parameters by conv_fill_params / c3_fill_job, whichever kernel the geometry is routed to: these functions are THE place to extend.
+struct ConvLayer {
+    int N, Cin, Cout, ksize, dtype, in_act, bn_act;
+    int ve() const { return dtype == MPN_F32 ? 4 : 8; }   // channels per 16-byte vector
+};
+struct ConvJob {
+    const void* x; const void* wp; void* y;
+    int H, W, x_stride, y_stride;   // pixel strides in elements (channel slices of wider tensors), 0 = dense
+    const float* in_scale; const float* in_shift;
+    float* stats_part;
+    const void* up_res;
+    // data gradients that reduce for the batch-norm they feed (mpn_conv_bwd_data_bn[_grouped]), else null
+    const void* bn_x; const float* bn_scale; const float* bn_shift; int bn_x_stride;
+};
+
+// the batch-norm-reduction fields (ConvParams and mpn_c3::Job name them alike)
+template <typename P>
+static void conv_set_bnr(P& p, const ConvLayer& l, const ConvJob& j) {
+    p.bnr_x = j.bn_x; p.bnr_scale = j.bn_scale; p.bnr_shift = j.bn_shift;
+    p.bnr_act = j.bn_x ? l.bn_act : MPN_ACT_NONE;
+    p.bnr_xs = j.bn_x ? (j.bn_x_stride > 0 ? j.bn_x_stride : l.Cout) : 0;
+}
+
+static void conv_fill_params(ConvParams& p, const PackGeom& g, const ConvLayer& l, const ConvJob& j) {
+    p.x = j.x; p.wp = j.wp; p.y = j.y;
+    p.in_scale = j.in_scale; p.in_shift = j.in_shift; p.in_act = l.in_act;
+    p.stats_part = j.stats_part; p.up_res = j.up_res;
+    conv_set_bnr(p, l, j);
 #ifdef MPN_DIAG
     p.dbg = (unsigned long long*)g_conv_dbg;
 #endif
     // measured: +10..14 % on 1x1 layers with several n-tiles (A rows re-read from the same L2), -4 % on single-n-tile layers
-    p.xcd_remap = (ksize == 1 && g.n_tiles > 1);
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.x_stride = x_stride > 0 ? x_stride : Cin;
-    p.y_stride = y_stride > 0 ? y_stride : Cout;
-    p.tiles_x = (W + 15) / 16; p.tiles_y = (H + 7) / 8;
-    p.M = (long long)N * H * W;
+    p.xcd_remap = (l.ksize == 1 && g.n_tiles > 1);
+    p.N = l.N; p.H = j.H; p.W = j.W; p.Cin = l.Cin; p.Cout = l.Cout;
+    p.x_stride = j.x_stride > 0 ? j.x_stride : l.Cin;
+    p.y_stride = j.y_stride > 0 ? j.y_stride : l.Cout;
+    p.tiles_x = (j.W + 15) / 16; p.tiles_y = (j.H + 7) / 8;
+    p.M = (long long)l.N * j.H * j.W;
     p.row_bytes = g.row_bytes; p.nchunk = g.nchunk; p.n_tiles = g.n_tiles; p.wp_tile_bytes = g.tile_bytes;
+}
+
+static void c3_fill_job(mpn_c3::Job& c, const ConvLayer& l, const ConvJob& j) {
+    c.x = j.x; c.wp = j.wp; c.y = j.y; c.in_scale = j.in_scale; c.in_shift = j.in_shift; c.stats_part = j.stats_part; c.in_act = l.in_act;
+    c.N = l.N; c.H = j.H; c.W = j.W; c.Cin = l.Cin; c.Cout = l.Cout;
+    c.xs = j.x_stride > 0 ? j.x_stride : l.Cin; c.ys = j.y_stride > 0 ? j.y_stride : l.Cout;
+    conv_set_bnr(c, l, j);
+#ifdef MPN_DIAG
+    c.dbg = (unsigned long long*)g_conv_dbg;
+#endif
+}
+
+// `who` names the entry point in the messages
+static int conv_check_layer(const char* who, const ConvLayer& l) {
+    MPN_REQUIRE(l.ksize == 1 || l.ksize == 3, MPN_ERR_BAD_SHAPE, "%s: ksize must be 1 or 3 (got %d)", who, l.ksize);
+    MPN_REQUIRE(l.dtype == MPN_F32 || l.dtype == MPN_BF16 || l.dtype == MPN_F16, MPN_ERR_BAD_DTYPE, "%s: dtype %d", who, l.dtype);
+    MPN_REQUIRE(l.N > 0 && l.Cin > 0 && l.Cout > 0 && l.Cin % l.ve() == 0 && l.Cout % l.ve() == 0, MPN_ERR_BAD_SHAPE,
+                "%s: bad shape (N %d; Cin %d and Cout %d must be multiples of %d)", who, l.N, l.Cin, l.Cout, l.ve());
     return MPN_OK;
 }
 
-static void c3_fill_job(mpn_c3::Job& j, const void* x, const void* w_packed, void* y, int N, int H, int W, int Cin, int Cout,
-                        int x_stride, int y_stride, const float* in_scale, const float* in_shift, int in_act, float* stats_part) {
-    j.x = x; j.wp = w_packed; j.y = y; j.in_scale = in_scale; j.in_shift = in_shift; j.stats_part = stats_part; j.in_act = in_act;
-    j.N = N; j.H = H; j.W = W; j.Cin = Cin; j.Cout = Cout;
-    j.xs = x_stride > 0 ? x_stride : Cin; j.ys = y_stride > 0 ? y_stride : Cout;
-    j.bnr_x = nullptr; j.bnr_scale = nullptr; j.bnr_shift = nullptr; j.bnr_act = MPN_ACT_NONE; j.bnr_xs = 0;
-#ifdef MPN_DIAG
-    j.dbg = (unsigned long long*)g_conv_dbg;
-#endif
+// a pixel stride is 0 (dense) or at least the channel count, in whole 16-byte vectors
+static bool conv_stride_ok(int stride, int ch, int ve) { return stride == 0 || (stride >= ch && stride % ve == 0); }
+static int stride_at(const int* strides, int j) { return strides ? strides[j] : 0; }
+
+static int conv_check_job(const char* who, const ConvLayer& l, const ConvJob& j) {
+    MPN_REQUIRE(j.x && j.wp && j.y, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(mpn_aligned16(j.x) && mpn_aligned16(j.wp) && mpn_aligned16(j.y), MPN_ERR_BAD_ALIGN, "%s: pointers must be 16-byte aligned", who);
+    MPN_REQUIRE((j.in_scale == nullptr) == (j.in_shift == nullptr), MPN_ERR_BAD_ARG, "%s: scale/shift mismatch", who);
+    MPN_REQUIRE(j.H > 0 && j.W > 0, MPN_ERR_BAD_SHAPE, "%s: bad size %d x %d", who, j.H, j.W);
+    MPN_REQUIRE(conv_stride_ok(j.x_stride, l.Cin, l.ve()) && conv_stride_ok(j.y_stride, l.Cout, l.ve()), MPN_ERR_BAD_SHAPE,
+                "%s: pixel strides (%d, %d) must be 0 or multiples of %d not below the channel counts", who, j.x_stride, j.y_stride, l.ve());
+    return MPN_OK;
 }
+
+// ... and what a data gradient with the batch-norm reduction passes on top. vec_affine: the tiled kernel and the GEMM kernel fetch
+// bn_scale / bn_shift as 16-byte vectors, the persistent 3x3 kernel element by element.
+static int conv_check_bnr(const char* who, const ConvLayer& l, const ConvJob& j, bool vec_affine) {
+    MPN_REQUIRE(j.bn_x && j.bn_scale && j.bn_shift && j.stats_part, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(mpn_aligned16(j.bn_x) && (!vec_affine || (mpn_aligned16(j.bn_scale) && mpn_aligned16(j.bn_shift))), MPN_ERR_BAD_ALIGN,
+                "%s: pointers must be 16-byte aligned", who);
+    MPN_REQUIRE(conv_stride_ok(j.bn_x_stride, l.Cout, l.ve()), MPN_ERR_BAD_SHAPE, "%s: bad pixel stride %d of bn_x", who, j.bn_x_stride);
+    return MPN_OK;
+}
+
+// one CHECKED job to the kernel that takes its geometry (with the batch-norm reduction: the 1x1 layers - 3x3 ones run as a group of one)
+static int conv_launch(const PackGeom& g, const ConvLayer& l, const ConvJob& j, hipStream_t st) {
+    if (g.row_bytes < 0) {    // 3x3, 16-bit storage, Cin % 64 == 0, Cout % 128 == 0: 256-pixel tiles, one 8-wave block per CU
+        mpn_c3::Job job;
+        c3_fill_job(job, l, j);
+        return mpn_c3::launch(&job, 1, l.dtype, st);
+    }
+    if (g.row_bytes == 0) {   // deep 1x1 layer: the GEMM kernel (weights packed as [Cout][Cin])
+        MPN_REQUIRE(j.up_res == nullptr, MPN_ERR_BAD_ARG, "conv: the upsample-add epilogue needs Cout < 256 or Cin < 256");
+        return pw_gemm_launch(j.x, j.wp, j.y, (long long)l.N * j.H * j.W, l.Cin, l.Cout, j.x_stride > 0 ? j.x_stride : l.Cin,
+                              j.y_stride > 0 ? j.y_stride : l.Cout, j.in_scale, j.in_shift, l.in_act, j.stats_part, st,
+                              j.bn_x, j.bn_x ? (j.bn_x_stride > 0 ? j.bn_x_stride : l.Cout) : 0, j.bn_scale, j.bn_shift, l.bn_act);
+    }
+    ConvParams p;
+    conv_fill_params(p, g, l, j);
+    const int m_tiles = mpn_conv_num_parts(l.N, j.H, j.W, l.ksize);
+    if (j.bn_x) return g.BN == 128 ? launch_conv_rb<bf16_t, 1, 128, 128, true>(p, m_tiles, st) : launch_conv_rb<bf16_t, 1, 64, 128, true>(p, m_tiles, st);
+    MPN_DISPATCH_DTYPE3(l.dtype, return (l.ksize == 3 ? launch_conv<T, 9>(p, g.BN, m_tiles, st) : launch_conv<T, 1>(p, g.BN, m_tiles, st)));
+}
+
+static PackGeom pack_geom(const ConvLayer& l) { return pack_geom(l.Cin, l.Cout, l.ksize * l.ksize, l.dtype == MPN_F32 ? 4 : 2, l.dtype); }
 
 extern "C" int mpn_conv_fwd(const void* x, const void* w_packed, void* y, int N, int H, int W, int Cin, int Cout,
                             int x_stride, int y_stride, int ksize, int dtype, const float* in_scale, const float* in_shift,
                             int in_act, float* stats_part, const void* up_res, mpn_stream_t stream) {
-    MPN_REQUIRE(ksize == 1 || ksize == 3, MPN_ERR_BAD_SHAPE, "conv: ksize must be 1 or 3 (got %d)", ksize);
-    MPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, MPN_ERR_BAD_SHAPE, "conv: bad shape");
-    MPN_REQUIRE(dtype == MPN_F32 || dtype == MPN_BF16 || dtype == MPN_F16, MPN_ERR_BAD_DTYPE, "conv: dtype %d", dtype);
-    const int es = dtype == MPN_F32 ? 4 : 2;
-    const int ve = 16 / es;
-    MPN_REQUIRE(Cin % ve == 0 && Cout % ve == 0, MPN_ERR_BAD_SHAPE,
-                "conv: Cin (%d) and Cout (%d) must be multiples of %d", Cin, Cout, ve);
-    MPN_REQUIRE((x_stride == 0 || (x_stride >= Cin && x_stride % ve == 0)) && (y_stride == 0 || (y_stride >= Cout && y_stride % ve == 0)),
-                MPN_ERR_BAD_SHAPE, "conv: pixel strides (%d, %d) must be 0 or multiples of %d not below the channel counts", x_stride,
-                y_stride, ve);
-    MPN_REQUIRE(x && w_packed && y, MPN_ERR_BAD_ARG, "conv: null pointer");
-    MPN_REQUIRE(mpn_aligned16(x) && mpn_aligned16(w_packed) && mpn_aligned16(y), MPN_ERR_BAD_ALIGN,
-                "conv: pointers must be 16-byte aligned");
-    MPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), MPN_ERR_BAD_ARG, "conv: scale/shift mismatch");
+    const ConvLayer l = {N, Cin, Cout, ksize, dtype, in_act};
+    const ConvJob j = {x, w_packed, y, H, W, x_stride, y_stride, in_scale, in_shift, stats_part, up_res};
+    if (int rc = conv_check_layer("conv", l)) return rc;
+    if (int rc = conv_check_job("conv", l, j)) return rc;
     MPN_REQUIRE(up_res == nullptr || (ksize == 1 && H % 2 == 0 && W % 2 == 0), MPN_ERR_BAD_ARG,
                 "conv: upsample-add epilogue needs ksize 1 and even H, W");
-    const PackGeom g = pack_geom(Cin, Cout, ksize * ksize, es, dtype);
-    if (g.row_bytes < 0) {    // 3x3, 16-bit storage, Cin % 64 == 0, Cout % 128 == 0: 256-pixel tiles, one 8-wave block per CU
-        mpn_c3::Job job;
-        c3_fill_job(job, x, w_packed, y, N, H, W, Cin, Cout, x_stride, y_stride, in_scale, in_shift, in_act, stats_part);
-        return mpn_c3::launch(&job, 1, dtype, (hipStream_t)stream);
-    }
-    if (g.row_bytes == 0) {   // deep 1x1 layer: the GEMM kernel (weights packed as [Cout][Cin])
-        MPN_REQUIRE(up_res == nullptr, MPN_ERR_BAD_ARG, "conv: the upsample-add epilogue needs Cout < 256 or Cin < 256");
-        return pw_gemm_launch(x, w_packed, y, (long long)N * H * W, Cin, Cout, x_stride > 0 ? x_stride : Cin,
-                              y_stride > 0 ? y_stride : Cout, in_scale, in_shift, in_act, stats_part, (hipStream_t)stream);
-    }
-    ConvParams p;
-    conv_fill_params(p, g, x, w_packed, y, N, H, W, Cin, Cout, x_stride, y_stride, ksize, in_scale, in_shift, in_act, stats_part, up_res);
-    const int m_tiles = mpn_conv_num_parts(N, H, W, ksize);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPN_F32) {
-        if (ksize == 3) return g.BN == 128 ? launch_conv<float, 9, 128>(p, m_tiles, st) : launch_conv<float, 9, 64>(p, m_tiles, st);
-        return g.BN == 128 ? launch_conv<float, 1, 128>(p, m_tiles, st) : launch_conv<float, 1, 64>(p, m_tiles, st);
-    }
-    if (dtype == MPN_F16) {
-        if (ksize == 3) return g.BN == 128 ? launch_conv<half_t, 9, 128>(p, m_tiles, st) : launch_conv<half_t, 9, 64>(p, m_tiles, st);
-        return g.BN == 128 ? launch_conv<half_t, 1, 128>(p, m_tiles, st) : launch_conv<half_t, 1, 64>(p, m_tiles, st);
-    }
-    if (ksize == 3) return g.BN == 128 ? launch_conv<bf16_t, 9, 128>(p, m_tiles, st) : launch_conv<bf16_t, 9, 64>(p, m_tiles, st);
-    return g.BN == 128 ? launch_conv<bf16_t, 1, 128>(p, m_tiles, st) : launch_conv<bf16_t, 1, 64>(p, m_tiles, st);
+    return conv_launch(pack_geom(l), l, j, (hipStream_t)stream);
 }
 
 template <int BN, bool BNR = false>
@@ -968,6 +1010,20 @@ static int launch_conv_grouped(const ConvGroup& grp, int grid, hipStream_t st) {
     conv_mfma_grouped_kernel<bf16_t, 9, BN, 128, BNR><<<dim3((unsigned)grid), dim3(kThreads), smem, st>>>(grp);
     MPN_LAUNCH_CHECK();
     return MPN_OK;
+}
+
+// lays the filled jobs grp.p[0..njobs) of the tiled 3x3 kernel into one grid, one behind the other; returns the grid size
+static int conv_group_lay(ConvGroup& grp, int njobs) {
+    int begin = 0;
+    for (int j = 0; j < njobs; ++j) {
+        ConvParams& p = grp.p[j];
+        p.xcd_remap = 0;
+        grp.begin[j] = begin;
+        begin += mpn_conv_num_parts(p.N, p.H, p.W, 3) * p.n_tiles;
+    }
+    for (int j = njobs; j <= kMaxGroup; ++j) grp.begin[j] = begin;
+    grp.njobs = njobs;
+    return begin;
 }
 
 /* Several independent 3x3 convolutions of the same channel geometry in ONE grid (the four pyramid levels of a subnet
@@ -981,55 +1037,32 @@ extern "C" int mpn_conv_fwd_grouped(int njobs, const void* const* x, const void*
                                     float* const* stats_part, mpn_stream_t stream) {
     MPN_REQUIRE(njobs > 0 && x && w_packed && y && H && W && in_scale && in_shift && stats_part, MPN_ERR_BAD_ARG,
                 "conv grouped: bad arguments");
-    const int es = dtype == MPN_F32 ? 4 : 2;
-    const PackGeom g = pack_geom(Cin, Cout, ksize * ksize, es, dtype);
+    const ConvLayer l = {N, Cin, Cout, ksize, dtype, in_act};
+    auto job = [&](int j) {
+        return ConvJob{x[j], w_packed[j], y[j], H[j], W[j], stride_at(x_stride, j), stride_at(y_stride, j), in_scale[j], in_shift[j], stats_part[j]};
+    };
+    if (int rc = conv_check_layer("conv grouped", l)) return rc;
     bool same_variant = true;   // (affine on load or not: one kernel instance per grid)
-    for (int j = 1; j < njobs; ++j) same_variant = same_variant && ((in_scale[j] == nullptr) == (in_scale[0] == nullptr));
-    if (g.row_bytes < 0 && njobs <= mpn_c3::kMaxJobs && same_variant) {
-        MPN_REQUIRE(N > 0, MPN_ERR_BAD_SHAPE, "conv grouped: bad shape");
-        mpn_c3::Job jobs[mpn_c3::kMaxJobs];
-        for (int j = 0; j < njobs; ++j) {
-            MPN_REQUIRE(x[j] && w_packed[j] && y[j] && H[j] > 0 && W[j] > 0, MPN_ERR_BAD_ARG, "conv grouped: null pointer / bad size");
-            MPN_REQUIRE(mpn_aligned16(x[j]) && mpn_aligned16(w_packed[j]) && mpn_aligned16(y[j]), MPN_ERR_BAD_ALIGN,
-                        "conv grouped: pointers must be 16-byte aligned");
-            MPN_REQUIRE((in_scale[j] == nullptr) == (in_shift[j] == nullptr), MPN_ERR_BAD_ARG, "conv grouped: scale/shift mismatch");
-            const int ys = y_stride ? y_stride[j] : 0, xs = x_stride ? x_stride[j] : 0;
-            MPN_REQUIRE((ys == 0 || (ys >= Cout && ys % 8 == 0)) && (xs == 0 || (xs >= Cin && xs % 8 == 0)), MPN_ERR_BAD_SHAPE,
-                        "conv grouped: bad pixel strides %d, %d", xs, ys);
-            c3_fill_job(jobs[j], x[j], w_packed[j], y[j], N, H[j], W[j], Cin, Cout, xs, ys, in_scale[j], in_shift[j], in_act, stats_part[j]);
-        }
-        return mpn_c3::launch(jobs, njobs, dtype, (hipStream_t)stream);
+    for (int j = 0; j < njobs; ++j) {
+        if (int rc = conv_check_job("conv grouped", l, job(j))) return rc;
+        same_variant = same_variant && ((in_scale[j] == nullptr) == (in_scale[0] == nullptr));
     }
-    const bool fast = dtype == MPN_BF16 && ksize == 3 && njobs <= kMaxGroup && g.row_bytes == 128;
-    if (!fast) {
+    const PackGeom g = pack_geom(l);
+    hipStream_t st = (hipStream_t)stream;
+    if (g.row_bytes < 0 && njobs <= mpn_c3::kMaxJobs && same_variant) {
+        mpn_c3::Job jobs[mpn_c3::kMaxJobs];
+        for (int j = 0; j < njobs; ++j) c3_fill_job(jobs[j], l, job(j));
+        return mpn_c3::launch(jobs, njobs, dtype, st);
+    }
+    if (!(dtype == MPN_BF16 && ksize == 3 && njobs <= kMaxGroup && g.row_bytes == 128)) {
         for (int j = 0; j < njobs; ++j)
-            if (int rc = mpn_conv_fwd(x[j], w_packed[j], y[j], N, H[j], W[j], Cin, Cout, x_stride ? x_stride[j] : 0,
-                                      y_stride ? y_stride[j] : 0, ksize, dtype,
-                                      in_scale[j], in_shift[j], in_act, stats_part[j], nullptr, stream))
-                return rc;
+            if (int rc = conv_launch(g, l, job(j), st)) return rc;
         return MPN_OK;
     }
-    MPN_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, MPN_ERR_BAD_SHAPE, "conv grouped: bad shape");
     ConvGroup grp = {};
-    int begin = 0;
-    for (int j = 0; j < njobs; ++j) {
-        MPN_REQUIRE(x[j] && w_packed[j] && y[j] && H[j] > 0 && W[j] > 0, MPN_ERR_BAD_ARG, "conv grouped: null pointer / bad size");
-        MPN_REQUIRE(mpn_aligned16(x[j]) && mpn_aligned16(w_packed[j]) && mpn_aligned16(y[j]), MPN_ERR_BAD_ALIGN,
-                    "conv grouped: pointers must be 16-byte aligned");
-        MPN_REQUIRE((in_scale[j] == nullptr) == (in_shift[j] == nullptr), MPN_ERR_BAD_ARG, "conv grouped: scale/shift mismatch");
-        const int ys = y_stride ? y_stride[j] : 0, xs = x_stride ? x_stride[j] : 0;
-        MPN_REQUIRE((ys == 0 || (ys >= Cout && ys % 8 == 0)) && (xs == 0 || (xs >= Cin && xs % 8 == 0)), MPN_ERR_BAD_SHAPE,
-                    "conv grouped: bad pixel strides %d, %d", xs, ys);
-        conv_fill_params(grp.p[j], g, x[j], w_packed[j], y[j], N, H[j], W[j], Cin, Cout, xs, ys, 3, in_scale[j], in_shift[j], in_act,
-                         stats_part[j], nullptr);
-        grp.p[j].xcd_remap = 0;
-        grp.begin[j] = begin;
-        begin += mpn_conv_num_parts(N, H[j], W[j], 3) * g.n_tiles;
-    }
-    for (int j = njobs; j <= kMaxGroup; ++j) grp.begin[j] = begin;
-    grp.njobs = njobs;
-    hipStream_t st = (hipStream_t)stream;
-    return g.BN == 128 ? launch_conv_grouped<128>(grp, begin, st) : launch_conv_grouped<64>(grp, begin, st);
+    for (int j = 0; j < njobs; ++j) conv_fill_params(grp.p[j], g, l, job(j));
+    const int grid = conv_group_lay(grp, njobs);
+    return g.BN == 128 ? launch_conv_grouped<128>(grp, grid, st) : launch_conv_grouped<64>(grp, grid, st);
 }
 
 
@@ -1058,49 +1091,33 @@ extern "C" int mpn_conv_bwd_data_bn_grouped(int njobs, const void* const* dy, co
                                             int dtype, const void* const* bn_x, const int* bn_x_stride,
                                             const float* const* bn_scale, const float* const* bn_shift, int bn_act,
                                             float* const* part, mpn_stream_t stream) {
+    const char* who = "conv_bwd_data_bn";
     MPN_REQUIRE(njobs > 0 && njobs <= mpn_c3::kMaxJobs && dy && w_packed_t && dx && H && W && bn_x && bn_scale && bn_shift && part,
-                MPN_ERR_BAD_ARG, "conv_bwd_data_bn: bad arguments");
-    MPN_REQUIRE(mpn_conv_bwd_data_bn_supported(K, C, 3, dtype), MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: geometry not covered (K %d, C %d)", K, C);
-    MPN_REQUIRE(N > 0, MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: bad shape");
-    const PackGeom pg = pack_geom(K, C, 9, 2, dtype);
-    if (pg.row_bytes == 128) {   // the tiled kernel (thin K: not a geometry of the persistent 3x3 kernel)
-        MPN_REQUIRE(njobs <= kMaxGroup, MPN_ERR_BAD_ARG, "conv_bwd_data_bn: at most %d jobs", kMaxGroup);
+                MPN_ERR_BAD_ARG, "%s: bad arguments", who);
+    MPN_REQUIRE(mpn_conv_bwd_data_bn_supported(K, C, 3, dtype), MPN_ERR_BAD_SHAPE, "%s: geometry not covered (K %d, C %d)", who, K, C);
+    MPN_REQUIRE(N > 0, MPN_ERR_BAD_SHAPE, "%s: bad shape", who);
+    const ConvLayer l = {N, K, C, 3, dtype, MPN_ACT_NONE, bn_act};
+    auto job = [&](int j) {
+        return ConvJob{dy[j], w_packed_t[j], dx[j], H[j], W[j], stride_at(dy_stride, j), stride_at(dx_stride, j), nullptr, nullptr, part[j], nullptr,
+                       bn_x[j], bn_scale[j], bn_shift[j], stride_at(bn_x_stride, j)};
+    };
+    const PackGeom g = pack_geom(l);
+    const bool tiled = g.row_bytes == 128;   // (thin K: not a geometry of the persistent 3x3 kernel)
+    MPN_REQUIRE(!tiled || njobs <= kMaxGroup, MPN_ERR_BAD_ARG, "%s: at most %d jobs", who, kMaxGroup);
+    for (int j = 0; j < njobs; ++j) {
+        if (int rc = conv_check_job(who, l, job(j))) return rc;
+        if (int rc = conv_check_bnr(who, l, job(j), tiled)) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (tiled) {
         ConvGroup grp = {};
-        int begin = 0;
-        for (int j = 0; j < njobs; ++j) {
-            MPN_REQUIRE(dy[j] && w_packed_t[j] && dx[j] && bn_x[j] && bn_scale[j] && bn_shift[j] && part[j] && H[j] > 0 && W[j] > 0,
-                        MPN_ERR_BAD_ARG, "conv_bwd_data_bn: null pointer / bad size");
-            MPN_REQUIRE(mpn_aligned16(dy[j]) && mpn_aligned16(w_packed_t[j]) && mpn_aligned16(dx[j]) && mpn_aligned16(bn_x[j]) &&
-                            mpn_aligned16(bn_scale[j]) && mpn_aligned16(bn_shift[j]), MPN_ERR_BAD_ALIGN, "conv_bwd_data_bn: pointers must be 16-byte aligned");
-            const int ys = dx_stride ? dx_stride[j] : 0, xs = dy_stride ? dy_stride[j] : 0, bs = bn_x_stride ? bn_x_stride[j] : 0;
-            MPN_REQUIRE((ys == 0 || (ys >= C && ys % 8 == 0)) && (xs == 0 || (xs >= K && xs % 8 == 0)) && (bs == 0 || (bs >= C && bs % 8 == 0)),
-                        MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: bad pixel strides %d, %d, %d", xs, ys, bs);
-            conv_fill_params(grp.p[j], pg, dy[j], w_packed_t[j], dx[j], N, H[j], W[j], K, C, xs, ys, 3, nullptr, nullptr, MPN_ACT_NONE,
-                             part[j], nullptr);
-            grp.p[j].bnr_x = bn_x[j]; grp.p[j].bnr_scale = bn_scale[j]; grp.p[j].bnr_shift = bn_shift[j]; grp.p[j].bnr_act = bn_act;
-            grp.p[j].bnr_xs = bs > 0 ? bs : C;
-            grp.p[j].xcd_remap = 0;
-            grp.begin[j] = begin;
-            begin += mpn_conv_num_parts(N, H[j], W[j], 3) * pg.n_tiles;
-        }
-        for (int j = njobs; j <= kMaxGroup; ++j) grp.begin[j] = begin;
-        grp.njobs = njobs;
-        return pg.BN == 128 ? launch_conv_grouped<128, true>(grp, begin, (hipStream_t)stream) : launch_conv_grouped<64, true>(grp, begin, (hipStream_t)stream);
+        for (int j = 0; j < njobs; ++j) conv_fill_params(grp.p[j], g, l, job(j));
+        const int grid = conv_group_lay(grp, njobs);
+        return g.BN == 128 ? launch_conv_grouped<128, true>(grp, grid, st) : launch_conv_grouped<64, true>(grp, grid, st);
     }
     mpn_c3::Job jobs[mpn_c3::kMaxJobs];
-    for (int j = 0; j < njobs; ++j) {
-        MPN_REQUIRE(dy[j] && w_packed_t[j] && dx[j] && bn_x[j] && bn_scale[j] && bn_shift[j] && part[j] && H[j] > 0 && W[j] > 0,
-                    MPN_ERR_BAD_ARG, "conv_bwd_data_bn: null pointer / bad size");
-        MPN_REQUIRE(mpn_aligned16(dy[j]) && mpn_aligned16(w_packed_t[j]) && mpn_aligned16(dx[j]) && mpn_aligned16(bn_x[j]), MPN_ERR_BAD_ALIGN,
-                    "conv_bwd_data_bn: pointers must be 16-byte aligned");
-        const int ys = dx_stride ? dx_stride[j] : 0, xs = dy_stride ? dy_stride[j] : 0, bs = bn_x_stride ? bn_x_stride[j] : 0;
-        MPN_REQUIRE((ys == 0 || (ys >= C && ys % 8 == 0)) && (xs == 0 || (xs >= K && xs % 8 == 0)) && (bs == 0 || (bs >= C && bs % 8 == 0)),
-                    MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: bad pixel strides %d, %d, %d", xs, ys, bs);
-        c3_fill_job(jobs[j], dy[j], w_packed_t[j], dx[j], N, H[j], W[j], K, C, xs, ys, nullptr, nullptr, MPN_ACT_NONE, part[j]);
-        jobs[j].bnr_x = bn_x[j]; jobs[j].bnr_scale = bn_scale[j]; jobs[j].bnr_shift = bn_shift[j]; jobs[j].bnr_act = bn_act;
-        jobs[j].bnr_xs = bs > 0 ? bs : C;
-    }
-    return mpn_c3::launch(jobs, njobs, dtype, (hipStream_t)stream);
+    for (int j = 0; j < njobs; ++j) c3_fill_job(jobs[j], l, job(j));
+    return mpn_c3::launch(jobs, njobs, dtype, st);
 }
 
 /* One layer (1x1 through the GEMM kernel of pointwise.hip: the data gradients of Conv2d_5..13_pointwise, which feed the
@@ -1109,25 +1126,15 @@ extern "C" int mpn_conv_bwd_data_bn_grouped(int njobs, const void* const* dy, co
 extern "C" int mpn_conv_bwd_data_bn(const void* dy, const void* w_packed_t, void* dx, int N, int H, int W, int K, int C,
                                     int dy_stride, int dx_stride, int ksize, int dtype, const void* bn_x, int bn_x_stride,
                                     const float* bn_scale, const float* bn_shift, int bn_act, float* part, mpn_stream_t stream) {
-    MPN_REQUIRE(mpn_conv_bwd_data_bn_supported(K, C, ksize, dtype), MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: geometry not covered (K %d, C %d, k %d)", K, C, ksize);
-    if (ksize == 3) {
-        const int h = H, w = W;
-        return mpn_conv_bwd_data_bn_grouped(1, &dy, &w_packed_t, &dx, N, &h, &w, K, C, &dy_stride, &dx_stride, dtype, &bn_x, &bn_x_stride,
+    const char* who = "conv_bwd_data_bn";
+    MPN_REQUIRE(mpn_conv_bwd_data_bn_supported(K, C, ksize, dtype), MPN_ERR_BAD_SHAPE, "%s: geometry not covered (K %d, C %d, k %d)", who, K, C, ksize);
+    if (ksize == 3)
+        return mpn_conv_bwd_data_bn_grouped(1, &dy, &w_packed_t, &dx, N, &H, &W, K, C, &dy_stride, &dx_stride, dtype, &bn_x, &bn_x_stride,
                                             &bn_scale, &bn_shift, bn_act, &part, stream);
-    }
-    MPN_REQUIRE(dy && w_packed_t && dx && bn_x && bn_scale && bn_shift && part && N > 0 && H > 0 && W > 0, MPN_ERR_BAD_ARG, "conv_bwd_data_bn: bad arguments");
-    MPN_REQUIRE(mpn_aligned16(dy) && mpn_aligned16(w_packed_t) && mpn_aligned16(dx) && mpn_aligned16(bn_x) && mpn_aligned16(bn_scale) && mpn_aligned16(bn_shift),
-                MPN_ERR_BAD_ALIGN, "conv_bwd_data_bn: pointers must be 16-byte aligned");
-    MPN_REQUIRE((dy_stride == 0 || (dy_stride >= K && dy_stride % 8 == 0)) && (dx_stride == 0 || (dx_stride >= C && dx_stride % 8 == 0)) &&
-                (bn_x_stride == 0 || (bn_x_stride >= C && bn_x_stride % 8 == 0)), MPN_ERR_BAD_SHAPE, "conv_bwd_data_bn: bad pixel strides");
-    if (pw_gemm_eligible(K, C, 1, 2))
-        return pw_gemm_launch(dy, w_packed_t, dx, (long long)N * H * W, K, C, dy_stride > 0 ? dy_stride : K, dx_stride > 0 ? dx_stride : C, nullptr, nullptr,
-                              MPN_ACT_NONE, part, (hipStream_t)stream, bn_x, bn_x_stride > 0 ? bn_x_stride : C, bn_scale, bn_shift, bn_act);
-    const PackGeom g = pack_geom(K, C, 1, 2, dtype);
-    ConvParams p;
-    conv_fill_params(p, g, dy, w_packed_t, dx, N, H, W, K, C, dy_stride, dx_stride, 1, nullptr, nullptr, MPN_ACT_NONE, part, nullptr);
-    p.bnr_x = bn_x; p.bnr_scale = bn_scale; p.bnr_shift = bn_shift; p.bnr_act = bn_act; p.bnr_xs = bn_x_stride > 0 ? bn_x_stride : C;
-    const int m_tiles = mpn_conv_num_parts(N, H, W, 1);
-    return g.BN == 128 ? launch_conv_rb<bf16_t, 1, 128, 128, true>(p, m_tiles, (hipStream_t)stream)
-                       : launch_conv_rb<bf16_t, 1, 64, 128, true>(p, m_tiles, (hipStream_t)stream);
+    MPN_REQUIRE(N > 0, MPN_ERR_BAD_SHAPE, "%s: bad shape", who);
+    const ConvLayer l = {N, K, C, 1, dtype, MPN_ACT_NONE, bn_act};
+    const ConvJob j = {dy, w_packed_t, dx, H, W, dy_stride, dx_stride, nullptr, nullptr, part, nullptr, bn_x, bn_scale, bn_shift, bn_x_stride};
+    if (int rc = conv_check_job(who, l, j)) return rc;
+    if (int rc = conv_check_bnr(who, l, j, true)) return rc;
+    return conv_launch(pack_geom(l), l, j, (hipStream_t)stream);
 }

@@ -963,16 +963,69 @@ WgradGeom wgrad_geom(int N, int H, int W, int Cin, int Cout, int ksize, int es) 
     return g;
 }
 
-template <typename T, int TAPS, int RBA, int RBD, int WM, bool STAGGER>
-int launch_wgrad_bf16(const WgradParams& p, hipStream_t st) {
-    constexpr int NPIXA = TAPS == 9 ? kHaloW * kHaloH : 128;
-    constexpr int smem = 2 * NPIXA * (RBA + 32) + 2 * 128 * (RBD + 32) + 2 * (RBA / 2) * (int)sizeof(float);
+// LDS bytes of the 16-bit kernel (stand-alone or grouped): two stages of the A and dY images and the producer's affine
+template <int TAPS, int RBA, int RBD> constexpr int wgrad16_smem_bytes() {
+    constexpr int smem = 2 * (TAPS == 9 ? kHaloW * kHaloH : 128) * (RBA + 32) + 2 * 128 * (RBD + 32) + 2 * (RBA / 2) * (int)sizeof(float);
     static_assert(smem <= 160 * 1024, "LDS budget");
+    return smem;
+}
+
+// a geometry of the 16-bit kernel, as an argument the launchers deduce their template parameters from
+template <int TAPS, int RBA, int RBD, int WM, bool STAGGER> struct Wgrad16 {};
+
+template <typename T, int TAPS, int RBA, int RBD, int WM, bool STAGGER>
+int launch_wgrad_bf16_grouped(Wgrad16<TAPS, RBA, RBD, WM, STAGGER>, const WgradGroup& g, int blocks, hipStream_t st) {
+    constexpr int smem = wgrad16_smem_bytes<TAPS, RBA, RBD>();
+    static mpn_attr_mask_t attr_mask{0};
+    MPN_HIP(mpn_ensure_dynamic_lds((const void*)conv_wgrad_bf16_grouped_kernel<T, TAPS, RBA, RBD, WM, STAGGER>, smem, &attr_mask));
+    conv_wgrad_bf16_grouped_kernel<T, TAPS, RBA, RBD, WM, STAGGER><<<dim3((unsigned)blocks), dim3(512), smem, st>>>(g);
+    MPN_LAUNCH_CHECK();
+    return MPN_OK;
+}
+
+// lays the filled jobs grp.p[0..njobs) into one grid, one behind the other; returns the grid size. A job keeps its XCD-aware work
+// map where its first block lands on XCD 0 (a job alone: always)
+int wgrad_group_lay(WgradGroup& grp, int njobs) {
+    int begin = 0;
+    for (int j = 0; j < njobs; ++j) {
+        WgradParams& p = grp.p[j];
+        const int blocks = p.n_cg * p.n_cb * p.nsplit;
+        if (njobs > 1) p.xcd_remap = (begin % 8 == 0 && blocks % 8 == 0) ? 1 : 0;
+        grp.begin[j] = begin;
+        begin += blocks;
+    }
+    for (int j = njobs; j <= kMaxWgradGroup; ++j) grp.begin[j] = begin;
+    grp.njobs = njobs;
+    return begin;
+}
+
+template <typename T, int TAPS, int RBA, int RBD, int WM, bool STAGGER>
+int launch_wgrad_bf16(Wgrad16<TAPS, RBA, RBD, WM, STAGGER>, const WgradParams& p, hipStream_t st) {
+    constexpr int smem = wgrad16_smem_bytes<TAPS, RBA, RBD>();
     static mpn_attr_mask_t attr_mask{0};
     MPN_HIP(mpn_ensure_dynamic_lds((const void*)conv_wgrad_bf16_kernel<T, TAPS, RBA, RBD, WM, STAGGER>, smem, &attr_mask));
     conv_wgrad_bf16_kernel<T, TAPS, RBA, RBD, WM, STAGGER><<<dim3((unsigned)(p.n_cg * p.n_cb * p.nsplit)), dim3(512), smem, st>>>(p);
     MPN_LAUNCH_CHECK();
     return MPN_OK;
+}
+// A single 3x3 layer with more than 64 outputs runs as a group of one: as a kernel of its own (the parameters in the kernel's
+// arguments instead of behind the job index) hipcc spills four registers of this 256-register geometry.
+template <typename T>
+int launch_wgrad_bf16(Wgrad16<9, 128, 256, 4, true> wide, const WgradParams& p, hipStream_t st) {
+    WgradGroup grp = {};
+    grp.p[0] = p;
+    const int blocks = wgrad_group_lay(grp, 1);
+    return launch_wgrad_bf16_grouped<T>(wide, grp, blocks, st);
+}
+
+// THE choice of the 16-bit geometry: launch(geometry) is one of the launchers above. The two wave groups run staggered by half a
+// period on the 3x3 geometries, in step on 1x1 (measured best per geometry).
+template <typename Launch>
+int wgrad16_dispatch(int Cin, int Cout, int ksize, Launch&& launch) {
+    if (wgrad_thin1x1(Cin, Cout, ksize)) return launch(Wgrad16<1, 64, 128, 2, false>{});
+    if (ksize == 1) return launch(Wgrad16<1, 256, 256, 4, false>{});
+    if (Cout <= 64) return launch(Wgrad16<9, 256, 128, 4, true>{});   // narrow 3x3
+    return launch(Wgrad16<9, 128, 256, 4, true>{});
 }
 
 template <typename T, int TAPS, int RBA, int RBD>
@@ -997,6 +1050,43 @@ int launch_wgrad(const WgradParams& p, hipStream_t st) {
 void* g_wgrad_dbg = nullptr;
 #endif
 
+// The argument checks of the weight-gradient entry points (single, grouped, fused 1x1) and THE place to extend them: the layer
+// (before any geometry is computed from it) ...
+int wgrad_check_layer(const char* who, int N, int Cin, int Cout, int ksize, int dtype) {
+    MPN_REQUIRE(ksize == 1 || ksize == 3, MPN_ERR_BAD_SHAPE, "%s: ksize must be 1 or 3", who);
+    MPN_REQUIRE(dtype == MPN_F32 || dtype == MPN_BF16 || dtype == MPN_F16, MPN_ERR_BAD_DTYPE, "%s: dtype %d", who, dtype);
+    const int ve = dtype == MPN_F32 ? 4 : 8;
+    MPN_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && Cin % ve == 0 && Cout % ve == 0, MPN_ERR_BAD_SHAPE,
+                "%s: bad shape (channels must be multiples of %d)", who, ve);
+    return MPN_OK;
+}
+
+// ... and ONE job, whose parameters it fills from the job's geometry and split count (strides in elements, 0 = dense)
+int wgrad_fill_job(WgradParams& p, const char* who, const void* x, const void* dy, float* part, int N, int H, int W, int Cin, int Cout,
+                   int x_stride, int dy_stride, int ksize, int es, const float* in_scale, const float* in_shift, int in_act,
+                   const WgradGeom& g, int nsplit) {
+    const int ve = 16 / es;
+    MPN_REQUIRE(x && dy && part, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(mpn_aligned16(x) && mpn_aligned16(dy), MPN_ERR_BAD_ALIGN, "%s: pointers must be 16-byte aligned", who);
+    MPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), MPN_ERR_BAD_ARG, "%s: scale/shift mismatch", who);
+    MPN_REQUIRE(N > 0 && H > 0 && W > 0, MPN_ERR_BAD_SHAPE, "%s: bad size %d x %d x %d", who, N, H, W);
+    p = {};
+    p.x = x; p.dy = dy; p.part = part;
+    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    p.xs = x_stride > 0 ? x_stride : Cin; p.dys = dy_stride > 0 ? dy_stride : Cout;
+    MPN_REQUIRE(p.xs >= Cin && p.dys >= Cout && p.xs % ve == 0 && p.dys % ve == 0, MPN_ERR_BAD_SHAPE,
+                "%s: pixel strides (%d, %d) must be multiples of %d not below the channel counts", who, x_stride, dy_stride, ve);
+    p.M = (long long)N * H * W;
+    MPN_REQUIRE(p.M * p.xs < (1ll << 31) && p.M * p.dys < (1ll << 31), MPN_ERR_BAD_SHAPE, "%s: tensors must span fewer than 2^31 elements", who);
+    // (the 16-bit 1x1 kernel addresses its tiles with 32-bit byte offsets and keeps 2^31 as the out-of-range offset)
+    MPN_REQUIRE(ksize != 1 || es != 2 || (p.M * p.xs < (1ll << 30) && p.M * p.dys < (1ll << 30)), MPN_ERR_BAD_SHAPE,
+                "%s: 16-bit 1x1 tensors must span fewer than 2^31 bytes", who);
+    p.tiles_x = (W + 15) / 16; p.tiles_y = (H + 7) / 8;
+    p.ntiles = g.ntiles; p.nsplit = nsplit; p.n_cg = g.n_cg; p.n_cb = g.n_cb; p.xcd_remap = 1;
+    return MPN_OK;
+}
+
 }  // namespace
 
 #ifdef MPN_DIAG
@@ -1008,70 +1098,25 @@ extern "C" int mpn_conv_wgrad_num_parts(int N, int H, int W, int Cin, int Cout, 
     return wgrad_geom(N, H, W, Cin, Cout, ksize, dtype == MPN_F32 ? 4 : 2).nsplit;
 }
 
-namespace {
-template <typename T, int TAPS, int RBA, int RBD, int WM, bool STAGGER>
-int launch_wgrad_bf16_grouped(const WgradGroup& g, int blocks, hipStream_t st);
-// A single 3x3 layer with more than 64 outputs runs as a group of one: as a kernel of its own (the parameters in the kernel's
-// arguments instead of behind the job index) hipcc spills four registers of this 256-register geometry.
-template <typename T>
-int launch_wgrad_single_as_group(const WgradParams& p, hipStream_t st) {
-    WgradGroup grp = {};
-    grp.p[0] = p;
-    const int blocks = p.n_cg * p.n_cb * p.nsplit;
-    grp.begin[0] = 0;
-    for (int j = 1; j <= kMaxWgradGroup; ++j) grp.begin[j] = blocks;
-    grp.njobs = 1;
-    return launch_wgrad_bf16_grouped<T, 9, 128, 256, 4, true>(grp, blocks, st);
-}
-}  // namespace
-
 /* part: [mpn_conv_wgrad_num_parts()][ksize*ksize][Cin][Cout] f32 (HWIO per split); finish with mpn_reduce_partials */
 extern "C" int mpn_conv_bwd_weight(const void* x, const void* dy, float* part, int N, int H, int W, int Cin, int Cout,
                                    int x_stride, int dy_stride, int ksize, int dtype, const float* in_scale,
                                    const float* in_shift, int in_act, mpn_stream_t stream) {
-    MPN_REQUIRE(ksize == 1 || ksize == 3, MPN_ERR_BAD_SHAPE, "conv wgrad: ksize must be 1 or 3");
-    MPN_REQUIRE(dtype == MPN_F32 || dtype == MPN_BF16 || dtype == MPN_F16, MPN_ERR_BAD_DTYPE, "conv wgrad: dtype %d", dtype);
+    if (int rc = wgrad_check_layer("conv wgrad", N, Cin, Cout, ksize, dtype)) return rc;
     const int es = dtype == MPN_F32 ? 4 : 2;
-    const int ve = 16 / es;
-    MPN_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % ve == 0 && Cout % ve == 0, MPN_ERR_BAD_SHAPE,
-                "conv wgrad: bad shape (channels must be multiples of %d)", ve);
-    MPN_REQUIRE(x && dy && part, MPN_ERR_BAD_ARG, "conv wgrad: null pointer");
-    MPN_REQUIRE(mpn_aligned16(x) && mpn_aligned16(dy), MPN_ERR_BAD_ALIGN, "conv wgrad: pointers must be 16-byte aligned");
-    MPN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), MPN_ERR_BAD_ARG, "conv wgrad: scale/shift mismatch");
-    MPN_REQUIRE((long long)N * H * W * Cin < (1ll << 31) && (long long)N * H * W * Cout < (1ll << 31), MPN_ERR_BAD_SHAPE,
-                "conv wgrad: tensors must have fewer than 2^31 elements");
     const WgradGeom g = wgrad_geom(N, H, W, Cin, Cout, ksize, es);
     WgradParams p;
-    p.x = x; p.dy = dy; p.part = part;
-    p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.xs = x_stride > 0 ? x_stride : Cin; p.dys = dy_stride > 0 ? dy_stride : Cout;
-    MPN_REQUIRE(p.xs >= Cin && p.dys >= Cout && p.xs % ve == 0 && p.dys % ve == 0, MPN_ERR_BAD_SHAPE,
-                "conv wgrad: pixel strides (%d, %d) must be multiples of %d not below the channel counts", x_stride, dy_stride, ve);
-    MPN_REQUIRE((long long)N * H * W * p.xs < (1ll << 31) && (long long)N * H * W * p.dys < (1ll << 31), MPN_ERR_BAD_SHAPE,
-                "conv wgrad: strided tensors must span fewer than 2^31 elements");
-    // (the 16-bit 1x1 kernel addresses its tiles with 32-bit byte offsets and keeps 2^31 as the out-of-range offset)
-    MPN_REQUIRE(ksize != 1 || es != 2 || ((long long)N * H * W * p.xs < (1ll << 30) && (long long)N * H * W * p.dys < (1ll << 30)),
-                MPN_ERR_BAD_SHAPE, "conv wgrad: 16-bit 1x1 tensors must span fewer than 2^31 bytes");
-    p.tiles_x = (W + 15) / 16; p.tiles_y = (H + 7) / 8;
-    p.M = (long long)N * H * W;
-    p.ntiles = g.ntiles; p.nsplit = g.nsplit; p.n_cg = g.n_cg; p.n_cb = g.n_cb; p.xcd_remap = 1;
+    if (int rc = wgrad_fill_job(p, "conv wgrad", x, dy, part, N, H, W, Cin, Cout, x_stride, dy_stride, ksize, es, in_scale, in_shift, in_act,
+                                g, g.nsplit))
+        return rc;
 #ifdef MPN_DIAG
     p.dbg = (unsigned long long*)g_wgrad_dbg;
 #endif
     hipStream_t st = (hipStream_t)stream;
     if (dtype == MPN_F32) return ksize == 3 ? launch_wgrad<float, 9>(p, st) : launch_wgrad<float, 1>(p, st);
-    // the two wave groups run staggered by half a period on the 3x3 geometries, in step on 1x1 (measured best per geometry)
-    if (dtype == MPN_F16) {   // same kernel on v_mfma_f32_16x16x32_f16
-        if (wgrad_thin1x1(Cin, Cout, ksize)) return launch_wgrad_bf16<half_t, 1, 64, 128, 2, false>(p, st);
-        if (ksize == 1) return launch_wgrad_bf16<half_t, 1, 256, 256, 4, false>(p, st);
-        if (Cout <= 64) return launch_wgrad_bf16<half_t, 9, 256, 128, 4, true>(p, st);
-        return launch_wgrad_single_as_group<half_t>(p, st);
-    }
-    if (wgrad_thin1x1(Cin, Cout, ksize)) return launch_wgrad_bf16<bf16_t, 1, 64, 128, 2, false>(p, st);
-    if (ksize == 1) return launch_wgrad_bf16<bf16_t, 1, 256, 256, 4, false>(p, st);
-    if (Cout <= 64) return launch_wgrad_bf16<bf16_t, 9, 256, 128, 4, true>(p, st);
-    return launch_wgrad_single_as_group<bf16_t>(p, st);
+    if (dtype == MPN_F16)   // same kernel on v_mfma_f32_16x16x32_f16
+        return wgrad16_dispatch(Cin, Cout, ksize, [&](auto geo) { return launch_wgrad_bf16<half_t>(geo, p, st); });
+    return wgrad16_dispatch(Cin, Cout, ksize, [&](auto geo) { return launch_wgrad_bf16<bf16_t>(geo, p, st); });
 }
 
 namespace {
@@ -1107,17 +1152,6 @@ void wgrad_group_splits(int njobs, int N, const int* H, const int* W, int Cin, i
     while (used + quantum <= budget && nsplit[big] + quantum <= geoms[big].ntiles / 4) { nsplit[big] += quantum; used += quantum; }
 }
 
-template <typename T, int TAPS, int RBA, int RBD, int WM, bool STAGGER>
-int launch_wgrad_bf16_grouped(const WgradGroup& g, int blocks, hipStream_t st) {
-    constexpr int NPIXA = TAPS == 9 ? kHaloW * kHaloH : 128;
-    constexpr int smem = 2 * NPIXA * (RBA + 32) + 2 * 128 * (RBD + 32) + 2 * (RBA / 2) * (int)sizeof(float);
-    static mpn_attr_mask_t attr_mask{0};
-    MPN_HIP(mpn_ensure_dynamic_lds((const void*)conv_wgrad_bf16_grouped_kernel<T, TAPS, RBA, RBD, WM, STAGGER>, smem, &attr_mask));
-    conv_wgrad_bf16_grouped_kernel<T, TAPS, RBA, RBD, WM, STAGGER><<<dim3((unsigned)blocks), dim3(512), smem, st>>>(g);
-    MPN_LAUNCH_CHECK();
-    return MPN_OK;
-}
-
 bool wgrad_groupable(int njobs, int dtype) { return njobs >= 2 && njobs <= kMaxWgradGroup && (dtype == MPN_BF16 || dtype == MPN_F16); }
 
 }  // namespace
@@ -1142,7 +1176,8 @@ extern "C" int mpn_conv_bwd_weight_grouped(int njobs, const void* const* x, cons
                                            const int* H, const int* W, int Cin, int Cout, const int* x_stride, const int* dy_stride,
                                            int ksize, int dtype, const float* const* in_scale, const float* const* in_shift,
                                            int in_act, mpn_stream_t stream) {
-    MPN_REQUIRE(njobs > 0 && x && dy && part && H && W && in_scale && in_shift, MPN_ERR_BAD_ARG, "conv wgrad grouped: bad arguments");
+    const char* who = "conv wgrad grouped";
+    MPN_REQUIRE(njobs > 0 && x && dy && part && H && W && in_scale && in_shift, MPN_ERR_BAD_ARG, "%s: bad arguments", who);
     if (!wgrad_groupable(njobs, dtype)) {
         for (int j = 0; j < njobs; ++j)
             if (int rc = mpn_conv_bwd_weight(x[j], dy[j], part[j], N, H[j], W[j], Cin, Cout, x_stride ? x_stride[j] : 0,
@@ -1150,51 +1185,19 @@ extern "C" int mpn_conv_bwd_weight_grouped(int njobs, const void* const* x, cons
                 return rc;
         return MPN_OK;
     }
-    MPN_REQUIRE(ksize == 1 || ksize == 3, MPN_ERR_BAD_SHAPE, "conv wgrad grouped: ksize must be 1 or 3");
-    MPN_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, MPN_ERR_BAD_SHAPE, "conv wgrad grouped: bad shape");
+    if (int rc = wgrad_check_layer(who, N, Cin, Cout, ksize, dtype)) return rc;
     WgradGeom geoms[kMaxWgradGroup];
     int nsplit[kMaxWgradGroup];
     wgrad_group_splits(njobs, N, H, W, Cin, Cout, ksize, nsplit, geoms);
     WgradGroup grp = {};
-    int begin = 0;
-    for (int j = 0; j < njobs; ++j) {
-        MPN_REQUIRE(x[j] && dy[j] && part[j] && H[j] > 0 && W[j] > 0, MPN_ERR_BAD_ARG, "conv wgrad grouped: null pointer / bad size");
-        MPN_REQUIRE(mpn_aligned16(x[j]) && mpn_aligned16(dy[j]), MPN_ERR_BAD_ALIGN, "conv wgrad grouped: pointers must be 16-byte aligned");
-        MPN_REQUIRE((in_scale[j] == nullptr) == (in_shift[j] == nullptr), MPN_ERR_BAD_ARG, "conv wgrad grouped: scale/shift mismatch");
-        WgradParams& p = grp.p[j];
-        p.x = x[j]; p.dy = dy[j]; p.part = part[j];
-        p.in_scale = in_scale[j]; p.in_shift = in_shift[j]; p.in_act = in_act;
-        p.N = N; p.H = H[j]; p.W = W[j]; p.Cin = Cin; p.Cout = Cout;
-        p.xs = (x_stride && x_stride[j] > 0) ? x_stride[j] : Cin; p.dys = (dy_stride && dy_stride[j] > 0) ? dy_stride[j] : Cout;
-        MPN_REQUIRE(p.xs >= Cin && p.dys >= Cout && p.xs % 8 == 0 && p.dys % 8 == 0, MPN_ERR_BAD_SHAPE, "conv wgrad grouped: bad pixel strides");
-        MPN_REQUIRE((long long)N * H[j] * W[j] * p.xs < (1ll << 31) && (long long)N * H[j] * W[j] * p.dys < (1ll << 31), MPN_ERR_BAD_SHAPE,
-                    "conv wgrad grouped: tensors must span fewer than 2^31 elements");
-        MPN_REQUIRE(ksize != 1 || ((long long)N * H[j] * W[j] * p.xs < (1ll << 30) && (long long)N * H[j] * W[j] * p.dys < (1ll << 30)),
-                    MPN_ERR_BAD_SHAPE, "conv wgrad grouped: 1x1 tensors must span fewer than 2^31 bytes");
-        p.tiles_x = (W[j] + 15) / 16; p.tiles_y = (H[j] + 7) / 8;
-        p.M = (long long)N * H[j] * W[j];
-        p.ntiles = geoms[j].ntiles; p.nsplit = nsplit[j]; p.n_cg = geoms[j].n_cg; p.n_cb = geoms[j].n_cb;
-        const int blocks = p.n_cg * p.n_cb * p.nsplit;
-        p.xcd_remap = (begin % 8 == 0 && blocks % 8 == 0) ? 1 : 0;
-#ifdef MPN_DIAG
-        p.dbg = nullptr;
-#endif
-        grp.begin[j] = begin;
-        begin += blocks;
-    }
-    for (int j = njobs; j <= kMaxWgradGroup; ++j) grp.begin[j] = begin;
-    grp.njobs = njobs;
+    for (int j = 0; j < njobs; ++j)
+        if (int rc = wgrad_fill_job(grp.p[j], who, x[j], dy[j], part[j], N, H[j], W[j], Cin, Cout, x_stride ? x_stride[j] : 0,
+                                    dy_stride ? dy_stride[j] : 0, ksize, 2, in_scale[j], in_shift[j], in_act, geoms[j], nsplit[j]))
+            return rc;
+    const int blocks = wgrad_group_lay(grp, njobs);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPN_F16) {
-        if (wgrad_thin1x1(Cin, Cout, ksize)) return launch_wgrad_bf16_grouped<half_t, 1, 64, 128, 2, false>(grp, begin, st);
-        if (ksize == 1) return launch_wgrad_bf16_grouped<half_t, 1, 256, 256, 4, false>(grp, begin, st);
-        if (Cout <= 64) return launch_wgrad_bf16_grouped<half_t, 9, 256, 128, 4, true>(grp, begin, st);
-        return launch_wgrad_bf16_grouped<half_t, 9, 128, 256, 4, true>(grp, begin, st);
-    }
-    if (wgrad_thin1x1(Cin, Cout, ksize)) return launch_wgrad_bf16_grouped<bf16_t, 1, 64, 128, 2, false>(grp, begin, st);
-    if (ksize == 1) return launch_wgrad_bf16_grouped<bf16_t, 1, 256, 256, 4, false>(grp, begin, st);
-    if (Cout <= 64) return launch_wgrad_bf16_grouped<bf16_t, 9, 256, 128, 4, true>(grp, begin, st);
-    return launch_wgrad_bf16_grouped<bf16_t, 9, 128, 256, 4, true>(grp, begin, st);
+    if (dtype == MPN_F16) return wgrad16_dispatch(Cin, Cout, ksize, [&](auto geo) { return launch_wgrad_bf16_grouped<half_t>(geo, grp, blocks, st); });
+    return wgrad16_dispatch(Cin, Cout, ksize, [&](auto geo) { return launch_wgrad_bf16_grouped<bf16_t>(geo, grp, blocks, st); });
 }
 
 namespace {
@@ -1228,30 +1231,19 @@ struct Conv1x1Apply { const void* y_raw; int y_stride; const float *scale, *shif
 int conv1x1_bwd_fused_impl(const void* x, const void* dy, const float* w, void* dx, float* wpart, float* bn_part, int N, int H,
                            int W, int Cin, int Cout, int x_stride, int dy_stride, int dx_stride, int dtype,
                            const float* in_scale, const float* in_shift, int in_act, const Conv1x1Apply* ap, mpn_stream_t stream) {
-    MPN_REQUIRE(mpn_conv1x1_bwd_fused_supported(Cin, Cout, dtype), MPN_ERR_BAD_SHAPE, "conv1x1_bwd_fused: layer not covered (Cin %d, Cout %d)", Cin, Cout);
-    MPN_REQUIRE(x && dy && w && dx && wpart && in_scale && in_shift && N > 0 && H > 0 && W > 0, MPN_ERR_BAD_ARG, "conv1x1_bwd_fused: bad arguments");
-    MPN_REQUIRE(bn_part != nullptr || ap == nullptr, MPN_ERR_BAD_ARG, "conv1x1_bwd_fused_apply: needs the reduction's slab");
-    MPN_REQUIRE(mpn_aligned16(x) && mpn_aligned16(dy) && mpn_aligned16(dx), MPN_ERR_BAD_ALIGN, "conv1x1_bwd_fused: pointers must be 16-byte aligned");
-    MPN_REQUIRE(dx != x && dx != dy, MPN_ERR_BAD_ARG, "conv1x1_bwd_fused: dx must not alias an input");
-    WgradParams p = {};
-    p.x = x; p.dy = dy; p.part = wpart; p.in_scale = in_scale; p.in_shift = in_shift; p.in_act = in_act;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.xs = x_stride > 0 ? x_stride : Cin; p.dys = dy_stride > 0 ? dy_stride : Cout; p.dxs = dx_stride > 0 ? dx_stride : Cin;
-    MPN_REQUIRE(p.xs >= Cin && p.dys >= Cout && p.dxs >= Cin && p.xs % 8 == 0 && p.dys % 8 == 0 && p.dxs % 8 == 0, MPN_ERR_BAD_SHAPE,
-                "conv1x1_bwd_fused: pixel strides must be multiples of 8 not below the channel counts");
-    MPN_REQUIRE((long long)N * H * W * p.xs < (1ll << 31) && (long long)N * H * W * p.dys < (1ll << 31), MPN_ERR_BAD_SHAPE,
-                "conv1x1_bwd_fused: tensors must span fewer than 2^31 elements");
-    MPN_REQUIRE((long long)N * H * W * p.xs < (1ll << 30) && (long long)N * H * W * p.dys < (1ll << 30), MPN_ERR_BAD_SHAPE,
-                "conv1x1_bwd_fused: tensors must span fewer than 2^31 bytes");
+    const char* who = ap ? "conv1x1_bwd_fused_apply" : "conv1x1_bwd_fused";
+    MPN_REQUIRE(mpn_conv1x1_bwd_fused_supported(Cin, Cout, dtype), MPN_ERR_BAD_SHAPE, "%s: layer not covered (Cin %d, Cout %d)", who, Cin, Cout);
+    MPN_REQUIRE(w && dx && in_scale && in_shift, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+    MPN_REQUIRE(bn_part != nullptr || ap == nullptr, MPN_ERR_BAD_ARG, "%s: needs the reduction's slab", who);
+    MPN_REQUIRE(mpn_aligned16(dx), MPN_ERR_BAD_ALIGN, "%s: pointers must be 16-byte aligned", who);
+    MPN_REQUIRE(dx != x && dx != dy, MPN_ERR_BAD_ARG, "%s: dx must not alias an input", who);
     const WgradGeom g = wgrad_geom(N, H, W, Cin, Cout, 1, 2);
-    MPN_REQUIRE(g.n_cg == 1 && g.n_cb == 1, MPN_ERR_BAD_SHAPE, "conv1x1_bwd_fused: one block tile must hold the layer");
-    p.tiles_x = (W + 15) / 16; p.tiles_y = (H + 7) / 8;
-    p.M = (long long)N * H * W;
-    p.ntiles = g.ntiles; p.nsplit = g.nsplit; p.n_cg = 1; p.n_cb = 1; p.xcd_remap = 1;
-    p.wf = w; p.dx = dx; p.bn_part = bn_part;
-#ifdef MPN_DIAG
-    p.dbg = nullptr;
-#endif
+    MPN_REQUIRE(g.n_cg == 1 && g.n_cb == 1, MPN_ERR_BAD_SHAPE, "%s: one block tile must hold the layer", who);
+    WgradParams p;
+    if (int rc = wgrad_fill_job(p, who, x, dy, wpart, N, H, W, Cin, Cout, x_stride, dy_stride, 1, 2, in_scale, in_shift, in_act, g, g.nsplit))
+        return rc;
+    p.wf = w; p.dx = dx; p.bn_part = bn_part; p.dxs = dx_stride > 0 ? dx_stride : Cin;
+    MPN_REQUIRE(p.dxs >= Cin && p.dxs % 8 == 0, MPN_ERR_BAD_SHAPE, "%s: dx's pixel stride must be a multiple of 8 not below Cin", who);
     hipStream_t st = (hipStream_t)stream;
     const bool thin32 = Cin <= 32 && Cout <= 64, wide = Cin > 64;
     if (ap != nullptr) {

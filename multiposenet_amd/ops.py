@@ -42,6 +42,20 @@ def _aff(a):
     return ptr(a.scale), ptr(a.shift), int(a.act)
 
 
+def _arr(values, ctype=ctypes.c_void_p):
+    """The per-job arguments of a grouped entry point as a ctypes array: tensors' device pointers (None -> NULL), or ints with
+    ctype=ctypes.c_int."""
+    if ctype is ctypes.c_void_p:
+        values = [ptr(v) for v in values]
+    return (ctype * len(values))(*values)
+
+
+def _each_job_alone(fn, n, *args):
+    """LAUNCH_JOBS_ALONE: the grouped wrapper `fn` once per job - every per-job list among its arguments cut down to that job, the
+    other arguments as they are. Returns the n results."""
+    return [fn(*[[a[j]] if isinstance(a, (list, tuple)) else a for a in args]) for j in range(n)]
+
+
 # ----------------------------------------------------------------------------- dense conv (MFMA)
 class PackedConv:
     """Weights of one dense conv packed for the MFMA kernel (forward and, lazily, data-gradient)."""
@@ -123,23 +137,16 @@ def conv_fwd(x, packed, cout, ksize, affine=None, out=None, stats_part=None, up_
 def conv_fwd_grouped(xs, packeds, cout, ksize, affines, outs, stats_parts):
     """Several independent convolutions of one channel geometry in one grid (mpn_conv_fwd_grouped): lists per job;
     affines / stats_parts entries may be None. All inputs [N,H_j,W_j,Cin] of one dtype, same activation code."""
-    import ctypes
     n = len(xs)
     if LAUNCH_JOBS_ALONE and n > 1:
-        for j in range(n):
-            conv_fwd_grouped([xs[j]], [packeds[j]], cout, ksize, [affines[j]], [outs[j]], [stats_parts[j]])
+        _each_job_alone(conv_fwd_grouped, n, xs, packeds, cout, ksize, affines, outs, stats_parts)
         return outs
     N, _, _, cin = xs[0].shape
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    sc, sh, act = [], [], ACT_NONE
-    for a in affines:
-        s_, h_, a_ = _aff(a)
-        sc.append(s_); sh.append(h_)
-        if a is not None:
-            act = a_
-    call("mpn_conv_fwd_grouped", n, PA(*[ptr(x) for x in xs]), PA(*[ptr(p) for p in packeds]), PA(*[ptr(o) for o in outs]), N,
-         IA(*[x.shape[1] for x in xs]), IA(*[x.shape[2] for x in xs]), cin, cout, IA(*[_slice_stride(x, cin) for x in xs]),
-         IA(*[_slice_stride(o, cout) for o in outs]), ksize, _lib.dtype_code(xs[0].dtype), PA(*sc), PA(*sh), int(act), PA(*[ptr(t) for t in stats_parts]), stream_ptr())
+    act = next((int(a.act) for a in reversed(affines) if a is not None), ACT_NONE)
+    call("mpn_conv_fwd_grouped", n, _arr(xs), _arr(packeds), _arr(outs), N, _arr([x.shape[1] for x in xs], ctypes.c_int),
+         _arr([x.shape[2] for x in xs], ctypes.c_int), cin, cout, _arr([_slice_stride(x, cin) for x in xs], ctypes.c_int),
+         _arr([_slice_stride(o, cout) for o in outs], ctypes.c_int), ksize, _lib.dtype_code(xs[0].dtype),
+         _arr([a.scale if a else None for a in affines]), _arr([a.shift if a else None for a in affines]), act, _arr(stats_parts), stream_ptr())
     return outs
 
 
@@ -161,17 +168,15 @@ def conv_bwd_data_bn_grouped(dys, packeds_t, c, bns, xs_bn, outs, parts):
     """Data gradients of several independent 3x3 convolutions in one grid that also reduce for the batch-norm layers `bns`
     they feed (raw tensors xs_bn): outs[j] <- masked gradient, parts[j] <- partial sums of g and g * x (RAW x: finalize with a
     BnBwdFinalizeBatch job marked raw). Returns the rows each slab holds (conv_stats_rows)."""
-    import ctypes
     n = len(dys)
     if LAUNCH_JOBS_ALONE and n > 1:
-        return [conv_bwd_data_bn_grouped([dys[j]], [packeds_t[j]], c, [bns[j]], [xs_bn[j]], [outs[j]], [parts[j]])[0] for j in range(n)]
+        return [rows[0] for rows in _each_job_alone(conv_bwd_data_bn_grouped, n, dys, packeds_t, c, bns, xs_bn, outs, parts)]
     N, _, _, k = dys[0].shape
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    call("mpn_conv_bwd_data_bn_grouped", n, PA(*[ptr(t) for t in dys]), PA(*[ptr(p) for p in packeds_t]), PA(*[ptr(o) for o in outs]), N,
-         IA(*[t.shape[1] for t in dys]), IA(*[t.shape[2] for t in dys]), k, int(c), IA(*[_slice_stride(t, k) for t in dys]),
-         IA(*[_slice_stride(o, c) for o in outs]), _lib.dtype_code(dys[0].dtype), PA(*[ptr(x) for x in xs_bn]),
-         IA(*[_slice_stride(x, c) for x in xs_bn]), PA(*[ptr(b.scale) for b in bns]), PA(*[ptr(b.shift) for b in bns]), int(bns[0].act),
-         PA(*[ptr(t) for t in parts]), stream_ptr())
+    call("mpn_conv_bwd_data_bn_grouped", n, _arr(dys), _arr(packeds_t), _arr(outs), N, _arr([t.shape[1] for t in dys], ctypes.c_int),
+         _arr([t.shape[2] for t in dys], ctypes.c_int), k, int(c), _arr([_slice_stride(t, k) for t in dys], ctypes.c_int),
+         _arr([_slice_stride(o, c) for o in outs], ctypes.c_int), _lib.dtype_code(dys[0].dtype), _arr(xs_bn),
+         _arr([_slice_stride(x, c) for x in xs_bn], ctypes.c_int), _arr([b.scale for b in bns]), _arr([b.shift for b in bns]),
+         int(bns[0].act), _arr(parts), stream_ptr())
     return [conv_stats_rows(N, t.shape[1], t.shape[2], k, c, 3, t.dtype) for t in dys]
 
 
@@ -236,7 +241,6 @@ class SlabReducer:
     `jobs`: list of (part tensor, nparts, n, out tensor); the device table is built once."""
 
     def __init__(self, jobs, device):
-        import ctypes
         self._alone = [SlabReducer([j], device) for j in jobs] if LAUNCH_JOBS_ALONE and len(jobs) > 1 else None
         lib = _lib.lib()
         nb = lib.mpn_reduce_desc_bytes()
@@ -261,34 +265,30 @@ class SlabReducer:
 
 def conv_wgrad_grouped_num_parts(N, hws, cin, cout, ksize, dtype):
     """Slab counts of conv_bwd_weight_grouped for jobs of sizes hws = [(H, W), ...]."""
-    import ctypes
     n = len(hws)
     if LAUNCH_JOBS_ALONE and n > 1:
-        return [conv_wgrad_grouped_num_parts(N, [hw], cin, cout, ksize, dtype)[0] for hw in hws]
-    IA = ctypes.c_int * n
-    out = IA()
-    call("mpn_conv_wgrad_grouped_num_parts", n, N, IA(*[h for h, _ in hws]), IA(*[w for _, w in hws]), cin, cout, ksize,
-         _lib.dtype_code(dtype), out)
+        return [nps[0] for nps in _each_job_alone(conv_wgrad_grouped_num_parts, n, N, list(hws), cin, cout, ksize, dtype)]
+    out = (ctypes.c_int * n)()
+    call("mpn_conv_wgrad_grouped_num_parts", n, N, _arr([h for h, _ in hws], ctypes.c_int), _arr([w for _, w in hws], ctypes.c_int),
+         cin, cout, ksize, _lib.dtype_code(dtype), out)
     return list(out)
 
 
 def conv_bwd_weight_grouped(xs, dys, ksize, affines, parts):
     """conv_bwd_weight of several independent layers of one channel geometry in one grid (the pyramid levels of a subnet
     stage); the slabs stay in `parts` (sized by conv_wgrad_grouped_num_parts) for the batched reduction."""
-    import ctypes
     n = len(xs)
     if LAUNCH_JOBS_ALONE and n > 1:
-        for j in range(n):
-            conv_bwd_weight_grouped([xs[j]], [dys[j]], ksize, [affines[j]], [parts[j]])
+        _each_job_alone(conv_bwd_weight_grouped, n, xs, dys, ksize, affines, parts)
         return
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
     N, cin, cout = xs[0].shape[0], xs[0].shape[3], dys[0].shape[3]
-    sc, sh, act = zip(*[_aff(a) for a in affines])
-    if len(set(act)) != 1:
+    acts = {int(a.act) if a is not None else ACT_NONE for a in affines}
+    if len(acts) != 1:
         raise ValueError("grouped jobs must share the activation")
-    call("mpn_conv_bwd_weight_grouped", n, PA(*[ptr(t) for t in xs]), PA(*[ptr(t) for t in dys]), PA(*[ptr(t) for t in parts]), N,
-         IA(*[t.shape[1] for t in xs]), IA(*[t.shape[2] for t in xs]), cin, cout, IA(*[_slice_stride(t, cin) for t in xs]),
-         IA(*[_slice_stride(t, cout) for t in dys]), ksize, _lib.dtype_code(xs[0].dtype), PA(*sc), PA(*sh), int(act[0]), stream_ptr())
+    call("mpn_conv_bwd_weight_grouped", n, _arr(xs), _arr(dys), _arr(parts), N, _arr([t.shape[1] for t in xs], ctypes.c_int),
+         _arr([t.shape[2] for t in xs], ctypes.c_int), cin, cout, _arr([_slice_stride(t, cin) for t in xs], ctypes.c_int),
+         _arr([_slice_stride(t, cout) for t in dys], ctypes.c_int), ksize, _lib.dtype_code(xs[0].dtype),
+         _arr([a.scale if a else None for a in affines]), _arr([a.shift if a else None for a in affines]), acts.pop(), stream_ptr())
 
 
 # ----------------------------------------------------------------------------- batch norm
@@ -341,7 +341,6 @@ class BnFinalizeBatch:
     jobs: list of (bn, part tensor, nparts, count); the device table is built once (pointers are static)."""
 
     def __init__(self, jobs, device):
-        import ctypes
         self._alone = [BnFinalizeBatch([j], device) for j in jobs] if LAUNCH_JOBS_ALONE and len(jobs) > 1 else None
         lib = _lib.lib()
         nb = lib.mpn_bn_fin_desc_bytes()
@@ -369,7 +368,6 @@ class BnBwdFinalizeBatch:
     """Backward finalizes (dgamma, dbeta, k1, k2) of several independent layers in one launch."""
 
     def __init__(self, jobs, device):
-        import ctypes
         self._alone = [BnBwdFinalizeBatch([j], device) for j in jobs] if LAUNCH_JOBS_ALONE and len(jobs) > 1 else None
         lib = _lib.lib()
         nb = lib.mpn_bn_bwd_fin_desc_bytes()
@@ -415,41 +413,35 @@ def bn_bwd_apply(bn, dA, x, add_ch0=None):
 
 
 def _bn_group_args(bns, dAs, xs):
-    import ctypes
-    n = len(bns)
-    PA, LA, IA = ctypes.c_void_p * n, ctypes.c_longlong * n, ctypes.c_int * n
     C = xs[0].shape[-1]
     Ms = [x.numel() // x.shape[-1] for x in xs]
     sd, sx = [_row_stride(t, C) for t in dAs], [_row_stride(t, C) for t in xs]                # channel slices allowed
     # all dense: no stride tables - channel counts the shared grid does not cover (24: kThreads % (C / vector) != 0) then take the
     # library's per-layer launches instead of being refused for strides nobody asked for
-    strides = (None, None) if all(s == C for s in sd + sx) else (IA(*sd), IA(*sx))
-    return n, PA, PA(*[ptr(t) for t in dAs]), PA(*[ptr(t) for t in xs]), LA(*Ms), C, _lib.dtype_code(xs[0].dtype), strides
+    strides = (None, None) if all(s == C for s in sd + sx) else (_arr(sd, ctypes.c_int), _arr(sx, ctypes.c_int))
+    return len(bns), _arr(dAs), _arr(xs), _arr(Ms, ctypes.c_longlong), C, _lib.dtype_code(xs[0].dtype), strides
 
 
 def bn_bwd_reduce_grouped(bns, dAs, xs, parts):
     """bn_bwd_reduce of several independent layers (same channel count, dtype, activation) in one grid."""
     if LAUNCH_JOBS_ALONE and len(bns) > 1:
-        for j in range(len(bns)):
-            bn_bwd_reduce_grouped([bns[j]], [dAs[j]], [xs[j]], [parts[j]])
+        _each_job_alone(bn_bwd_reduce_grouped, len(bns), bns, dAs, xs, parts)
         return
-    n, PA, pd, px, Ms, C, dc, (sd, sx) = _bn_group_args(bns, dAs, xs)
-    call("mpn_bn_bwd_reduce_grouped", n, pd, px, Ms, C, dc, PA(*[ptr(b.scale) for b in bns]), PA(*[ptr(b.shift) for b in bns]),
-         PA(*[ptr(b.mean) for b in bns]), PA(*[ptr(b.invstd) for b in bns]), int(bns[0].act), PA(*[ptr(p) for p in parts]),
-         sd, sx, stream_ptr())
+    n, pd, px, Ms, C, dc, (sd, sx) = _bn_group_args(bns, dAs, xs)
+    call("mpn_bn_bwd_reduce_grouped", n, pd, px, Ms, C, dc, _arr([b.scale for b in bns]), _arr([b.shift for b in bns]),
+         _arr([b.mean for b in bns]), _arr([b.invstd for b in bns]), int(bns[0].act), _arr(parts), sd, sx, stream_ptr())
 
 
 def bn_bwd_apply_grouped(bns, dAs, xs, add_ch0s=None):
     """bn_bwd_apply of several independent layers in one grid (after their finalizes)."""
     if LAUNCH_JOBS_ALONE and len(bns) > 1:
-        for j in range(len(bns)):
-            bn_bwd_apply_grouped([bns[j]], [dAs[j]], [xs[j]], None if add_ch0s is None else [add_ch0s[j]])
+        _each_job_alone(bn_bwd_apply_grouped, len(bns), bns, dAs, xs, add_ch0s)
         return
-    n, PA, pd, px, Ms, C, dc, (sd, sx) = _bn_group_args(bns, dAs, xs)
+    n, pd, px, Ms, C, dc, (sd, sx) = _bn_group_args(bns, dAs, xs)
     add = add_ch0s if add_ch0s is not None else [None] * n
-    call("mpn_bn_bwd_apply_grouped", n, pd, px, Ms, C, dc, PA(*[ptr(b.scale) for b in bns]), PA(*[ptr(b.shift) for b in bns]),
-         PA(*[ptr(b.mean) for b in bns]), PA(*[ptr(b.invstd) for b in bns]), PA(*[ptr(b.k1) for b in bns]),
-         PA(*[ptr(b.k2) for b in bns]), int(bns[0].act), PA(*[ptr(t) for t in add]), sd, sx, stream_ptr())
+    call("mpn_bn_bwd_apply_grouped", n, pd, px, Ms, C, dc, _arr([b.scale for b in bns]), _arr([b.shift for b in bns]),
+         _arr([b.mean for b in bns]), _arr([b.invstd for b in bns]), _arr([b.k1 for b in bns]), _arr([b.k2 for b in bns]),
+         int(bns[0].act), _arr(add), sd, sx, stream_ptr())
 
 
 def bn_inference_affine(bn):

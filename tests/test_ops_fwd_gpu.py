@@ -379,6 +379,38 @@ def test_conv_fwd_grouped_statistics_rows_with_two_channel_tiles(cuda):
         np.testing.assert_allclose(s[1].numpy(), (yd * yd).sum(0).numpy(), rtol=1e-5, atol=1e-2)
 
 
+@pytest.mark.parametrize("Cin, Cout, bare", [(24, 64, None), (8, 64, None), (128, 128, 1)], ids=["24-64", "8-64", "128-128-one-job-without-affine"])
+def test_conv_fwd_grouped_on_the_tiled_kernel_equals_separate_launches(cuda, Cin, Cout, bare):
+    """The grouped forward launch of the TILED kernel (bf16 3x3 with thin input: 128-byte rows, no batch-norm reduction): three jobs
+    ragged against the 8 x 16 tile, one smaller than a tile, each with its own ReLU affine and statistics slab, job 1 reading and
+    writing channel slices of wider tensors - outputs bit for bit those of conv_fwd per job, the slab rows conv_stats_rows promises
+    with equal column sums, NaN left behind them. (128, 128) with one job WITHOUT affine: the documented fallback to separate
+    launches, still bit for bit."""
+    ops = _ops()
+    dtype = torch.bfloat16
+    rs = np.random.RandomState(41)
+    N, sizes = 2, [(20, 24), (9, 7), (5, 6)]
+    xs, pcs, affs, outs, parts, wides = [], [], [], [], [], []
+    for j, (h, w) in enumerate(sizes):
+        pad = 16 if j == 1 else 0                                        # job 1: slices [8, 8 + C) of tensors 16 channels wider
+        xw = dev(rnd(rs.randn(N, h, w, Cin + pad), dtype), dtype)
+        ow = torch.full((N, h, w, Cout + pad), float("nan"), device="cuda", dtype=dtype)
+        xs.append(xw[..., pad // 2:pad // 2 + Cin]); outs.append(ow[..., pad // 2:pad // 2 + Cout]); wides.append(ow)
+        pcs.append(ops.PackedConv(dev((rs.randn(3, 3, Cin, Cout) / np.sqrt(9 * Cin)).astype(np.float32)), dtype))
+        affs.append(None if j == bare else ops.Affine(dev(torch.tensor(0.5 + rs.rand(Cin), dtype=torch.float32)),
+                                                      dev(torch.tensor(rs.randn(Cin) * 0.5, dtype=torch.float32)), 1))
+        parts.append(torch.full((ops.conv_num_parts(N, h, w, 3), 2, Cout), float("nan"), device="cuda"))
+    ops.conv_fwd_grouped(xs, [pc.fwd for pc in pcs], Cout, 3, affs, outs, parts)
+    for x, pc, a, y, ow, part, (h, w) in zip(xs, pcs, affs, outs, wides, parts, sizes):
+        alone = torch.full_like(part, float("nan"))
+        assert torch.equal(y, ops.conv_fwd(x.contiguous(), pc.fwd, Cout, 3, a, stats_part=alone))
+        assert ow.shape[3] == Cout or (bool(torch.isnan(ow[..., :8]).all()) and bool(torch.isnan(ow[..., 8 + Cout:]).all()))
+        rows = ops.conv_stats_rows(N, h, w, Cin, Cout, 3, dtype)
+        assert 0 < rows <= part.shape[0] and bool(torch.isfinite(part[:rows]).all()) and bool(torch.isnan(part[rows:]).all())
+        assert bool(torch.isnan(alone[rows:]).all())
+        np.testing.assert_allclose(part[:rows].double().sum(0).cpu().numpy(), alone[:rows].double().sum(0).cpu().numpy(), rtol=1e-5, atol=1e-4)
+
+
 def test_conv_fwd_channel_slices_of_wider_tensors(cuda):
     """x / y pixel strides: a conv reads a channel slice of a wider NHWC tensor and writes into a slice of another one
     (phi_subnet_2/conv2 -> the first 128 channels of the 512-channel concat tensor), 3x3 tiled kernel and 1x1 GEMM kernel."""
