@@ -895,6 +895,67 @@ int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int ma
                    mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * One-Euro smoothing (Casiez, Roussel, Vogel, CHI 2012) of the tracked persons' keypoints, and the per-joint velocities its
+ * derivative estimate gives: one filter per (stream, track slot, joint), one block per stream.
+ *
+ *   mpn_pose_smooth   record: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place exactly as
+ *                     mpn_pose_track reads it (the header's total and counts, clamped the same way; only rows 0 .. total-1;
+ *                     of a row only keypoints[17][3] = (x, y, score)).
+ *                   track_rows: the `out` of mpn_pose_track for the same record, DEVICE; of a row int32 track_id and int32
+ *                     slot are read.
+ *                   Streams: B = streams * F, stream s owns images s*F .. s*F+F-1 in time order, as in mpn_pose_track.
+ *                   PURE, as mpn_pose_track and for the same reason: the launch reads prev and writes the COMPLETE new state
+ *                     to next and the rows to out; it never writes prev, and running it twice in a row gives the same bytes.
+ *                     The caller advances the state by copying next over prev. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   State, prev and next, mpn_pose_smooth_state_bytes(streams, max_tracks) bytes DEVICE, per stream in 32-bit
+ *                     words: int32 frames (the frames this stream has seen), three zero words; then max_tracks slots of 88
+ *                     words: int32 id (the track the filters belong to, 0 = none); 17 groups of {int32 last, f32 x_hat,
+ *                     y_hat, dx_hat, dy_hat}, last = the stream's frame number at which the joint's filter last took a sample,
+ *                     0 = no sample; two zero words. An all-zero state is the valid empty state. Frame numbers count from 1;
+ *                     the counter is an int32 and is NOT guarded against wrap (2^31 frames are about 2 years at 30 Hz).
+ *                   Every float operation below is one IEEE f32 operation in the order written, without contraction; the
+ *                     division is correctly rounded. For frame j of the launch (0 <= j < F) n = prev.frames + j + 1. For
+ *                     every record row r of that image:
+ *                     untracked (track_id <= 0, or slot outside 0 .. max_tracks-1): out = the raw (x, y, score), velocity
+ *                       (0, 0); no state is touched. A slot value of any kind never indexes anything.
+ *                     tracked: if state[slot].id != track_id the slot becomes {id = track_id, every last = 0} (the slot was
+ *                       given to another track; ids are never reused). Then per joint k with the raw (x, y, score):
+ *                       rejected, not (score >= min_keypoint_score): last = 0; out = raw, velocity 0. The next good sample
+ *                         starts the filter again.
+ *                       first, last == 0: x_hat = x, y_hat = y, dx_hat = dy_hat = 0, last = n; out = raw, velocity 0.
+ *                       filtered, otherwise, the same steps for y:
+ *                         gap = n - last      (>= 1: frames without the person, or without any detection, count)
+ *                         te = f32(gap) / rate
+ *                         alpha(fc): r = (TWO_PI * fc) * te; alpha = r / (r + 1)        TWO_PI = 6.2831855f
+ *                         dx = (x - x_hat) / te
+ *                         dx_hat = dx_hat + alpha(d_cutoff) * (dx - dx_hat)
+ *                         fc = min_cutoff + beta * fabs(dx_hat)
+ *                         x_hat = x_hat + alpha(fc) * (x - x_hat)
+ *                       then last = n; out = (x_hat, y_hat, score), velocity (dx_hat, dy_hat) in pixels per second. The
+ *                       incremental form keeps a constant input exactly constant.
+ *                     Slots that no row of the launch names are copied from prev to next unchanged; next.frames =
+ *                     prev.frames + F. A frame without detections still counts. Two rows of one frame that name the same slot
+ *                     cannot come out of mpn_pose_track; the result for that slot is then unspecified, memory safety is not.
+ *                     The units are pixels: beta, which multiplies a speed, depends on the resolution.
+ *                   out: mpn_pose_smooth_out_bytes(B, max_boxes) bytes DEVICE, one row of 340 bytes per record row, aligned
+ *                     with the record's rows 0 .. total-1, every other row zero: f32 keypoints[17][3] (x, y, score), then f32
+ *                     velocities[17][2].
+ *                   Checked before any HIP call: null pointers, prev == next, rate / min_cutoff / d_cutoff not finite or not
+ *                     > 0, beta not finite or < 0, min_keypoint_score not finite (MPN_ERR_BAD_ARG); streams >= 1,
+ *                     B % streams == 0, 1 <= max_tracks <= 64, 1 <= max_boxes <= 64, B * max_boxes <= 4096
+ *                     (MPN_ERR_BAD_SHAPE); record 16-byte and track_rows / prev / next / out 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN). The grid depends on streams alone: a captured launch serves any later record and
+ *                     state.
+ *   mpn_pose_smooth_state_bytes   streams * (16 + max_tracks * 352); 0 for arguments out of range.
+ *   mpn_pose_smooth_out_bytes     B * max_boxes * 340; 0 for arguments out of range.
+ */
+size_t mpn_pose_smooth_state_bytes(int streams, int max_tracks);
+size_t mpn_pose_smooth_out_bytes(int B, int max_boxes);
+int mpn_pose_smooth(const void* record, const void* track_rows, int B, int max_boxes, int streams, int max_tracks,
+                    float rate, float min_cutoff, float beta, float d_cutoff, float min_keypoint_score, const void* prev,
+                    void* next, void* out, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

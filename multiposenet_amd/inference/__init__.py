@@ -2,4 +2,4 @@ from .utils import get_keypoints, get_keypoints_batch, KeypointDecoder, draw_eve
 from .detector import Detector  # noqa: F401
 from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401
 from .maps import MapPlotter, plot_maps  # noqa: F401
-from ..tracking import PoseTracker  # noqa: F401
+from ..tracking import PoseTracker, OneEuro  # noqa: F401

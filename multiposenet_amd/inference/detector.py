@@ -368,7 +368,11 @@ class Detector:
                 stream, 0 = untracked), 'track_hits' int32 [n], 'track_new' bool [n] and 'track_similarity' f64 [n] to
                 every dict: one mpn_pose_track launch behind the gather inside the captured graph - a graph of its own per
                 (tracker, b) - whose rows arrive with the record. The launch only reads the tracker's state; the call
-                advances it once, by a small device copy behind the graph. Every other key is unchanged.
+                advances it once, by a small device copy behind the graph. Every other key is unchanged. A tracker made
+                with smooth=OneEuro(...) (needs the PRN) also adds 'keypoints_smoothed' f32 [n, 17, 3] - the One-Euro filtered
+                (x, y) of every tracked person's joints with the frame's score, in the coordinates of this call's 'keypoints' -
+                and 'keypoint_velocities' f32 [n, 17, 2] in pixels per second: one mpn_pose_smooth launch behind the track
+                launch in the same graph, its rows in the same copy. `annotate` still draws the frame's own detections.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
@@ -426,6 +430,8 @@ class Detector:
             raise ValueError("track= needs the person detector (detector_path): without it no persons are detected")
         if track.similarity == 'oks' and self.assigner is None:
             raise ValueError("track=: similarity='oks' compares keypoints, which need the PRN (prn_path); use similarity='iou'")
+        if track.smooth is not None and self.assigner is None:
+            raise ValueError("track=: the tracker's smooth= filters keypoints, which need the PRN (prn_path)")
         track.check_batch(b)
         if track.max_boxes != self.params['max_boxes']:
             raise ValueError(f"track=: the tracker was made for max_boxes = {track.max_boxes}, this Detector's is "
@@ -548,7 +554,8 @@ class Detector:
         oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
         the record in the same buffer, so that they reach the host in the record's copy.
         track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
-        tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits).
+        tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits). A tracker
+        with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
         aug (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -601,8 +608,8 @@ class Detector:
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
         if oks is not None:
             oks.launch(record, whole[nbytes:nbytes + oks_bytes])
-        if track is not None:
-            track.launch(record, whole[nbytes + oks_bytes:], b)
+        if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
+            track.launch_all(record, whole[nbytes + oks_bytes:], b)
         dev['record'] = whole
         if annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)

@@ -3,7 +3,8 @@
     python -m multiposenet_amd.track_frames --images DIR --out tracks.jsonl
         [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32] [--size W H] [--batch 16]
         [--similarity oks|iou] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
-        [--score-threshold 0.05]
+        [--score-threshold 0.05] [--smooth [--fps 30] [--min-cutoff 1.0] [--beta 0.007] [--d-cutoff 1.0]
+        [--min-keypoint-score 0.0]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -12,7 +13,9 @@ route `jpeg.jpeg_support` names); a batch holding any other file is decoded by P
 The last, shorter batch runs at its own size (a second graph of that size): padding it with copies of the last frame would
 advance the tracks by frames the video does not have. --out gets one JSON line per frame: its name, and per person the
 track id (0 = untracked), the box (ymin, xmin, ymax, xmax, normalised to the frame) and the keypoints (x, y, score) in the
-frame's pixels. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+frame's pixels. --smooth runs a One-Euro filter over every tracked joint on the device as well (`tracking.OneEuro`; --fps is
+the video's frame rate) and adds "keypoints_smoothed" (x, y, score) and "keypoint_velocities" (pixels per second) to every
+line; beta multiplies a speed in frame pixels and so depends on the resolution. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -54,6 +57,12 @@ def main(argv=None):
     ap.add_argument("--new-track-score", type=float, default=0.3)
     ap.add_argument("--max-tracks", type=int, default=32)
     ap.add_argument("--score-threshold", type=float, default=0.05)
+    ap.add_argument("--smooth", action="store_true", help="One-Euro smoothing of the tracked keypoints, and their velocities")
+    ap.add_argument("--fps", type=float, default=30.0, help="frame rate of the video (--smooth)")
+    ap.add_argument("--min-cutoff", type=float, default=1.0)
+    ap.add_argument("--beta", type=float, default=0.007)
+    ap.add_argument("--d-cutoff", type=float, default=1.0)
+    ap.add_argument("--min-keypoint-score", type=float, default=0.0)
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
@@ -63,15 +72,23 @@ def main(argv=None):
 
     import torch
     from .evaluate_pose import _random_head
-    from .inference import Detector, PoseTracker
+    from .inference import Detector, OneEuro, PoseTracker
     from .prn import initial_values
+    smooth = None
+    if args.smooth:
+        try:
+            smooth = OneEuro(rate=args.fps, min_cutoff=args.min_cutoff, beta=args.beta, d_cutoff=args.d_cutoff,
+                             min_keypoint_score=args.min_keypoint_score)
+        except ValueError as e:
+            ap.error(str(e))
     if args.detector is None or args.prn is None:
         print("[track_frames] no --detector / --prn file: seeded random weights, the tracks mean nothing")
     det = Detector(args.model, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
                    detector_path=args.detector if args.detector is not None else _random_head(),
                    prn_path=args.prn if args.prn is not None else initial_values(seed=0))
     tracker = PoseTracker(streams=1, max_tracks=args.max_tracks, similarity=args.similarity, match_threshold=args.match_threshold,
-                          max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'])
+                          max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'],
+                          smooth=smooth)
     size = (args.size[1], args.size[0])
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -87,13 +104,21 @@ def main(argv=None):
                 outs = det.predict_images([_pixels(data) for data in files], size=size, score_threshold=args.score_threshold,
                                           track=tracker)
             for name, o in zip(batch, outs):
-                out.write(json.dumps({"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
-                                      "keypoints": o["keypoints"].tolist()}) + "\n")
+                line = {"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
+                        "keypoints": o["keypoints"].tolist()}
+                if smooth is not None:
+                    line["keypoints_smoothed"] = o["keypoints_smoothed"].tolist()
+                    line["keypoint_velocities"] = o["keypoint_velocities"].tolist()
+                out.write(json.dumps(line) + "\n")
                 persons += len(o["track_ids"])
             frames += len(batch)
     state = tracker.tracks(0)
-    print(json.dumps({"frames": frames, "persons": persons, "ids_given": state["next_id"] - 1, "live_tracks": len(state["ids"]),
-                      "dropped": state["dropped"], "similarity": args.similarity, "out": args.out}))
+    summary = {"frames": frames, "persons": persons, "ids_given": state["next_id"] - 1, "live_tracks": len(state["ids"]),
+               "dropped": state["dropped"], "similarity": args.similarity, "out": args.out}
+    if smooth is not None:
+        summary["smooth"] = {"fps": smooth.rate, "min_cutoff": smooth.min_cutoff, "beta": smooth.beta, "d_cutoff": smooth.d_cutoff,
+                             "min_keypoint_score": smooth.min_keypoint_score}
+    print(json.dumps(summary))
     return state
 
 

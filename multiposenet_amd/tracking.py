@@ -11,8 +11,16 @@ launch is a PURE function of (record, prev): it writes the new state to `next` a
 runs its device side eagerly and then replays the graph on an entry's first call (and again when the variables change) - an
 in-place update would step the state twice there. The state advances when `commit()` queues `prev.copy_(next)` behind the
 launch, outside the graph; the Detector does that once per call. `update()` is the same launch for host dicts.
+
+    tracker = PoseTracker(streams=1, smooth=OneEuro(rate=30.0))  # + 'keypoints_smoothed' f32 [n,17,3], 'keypoint_velocities' [n,17,2]
+
+`smooth=` adds `mpn_pose_smooth` behind the track launch: one One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) per track slot
+and joint, keyed by the slot and the id the track launch gave the row, with a prev / next state of its own that `commit()`
+advances in the same way. The units are pixels of the call's 'keypoints': `beta` multiplies a speed in pixels per second and
+so depends on the resolution.
 """
 import itertools
+import math
 
 import numpy as np
 
@@ -32,7 +40,59 @@ _HEAD = np.dtype([('next_id', np.int32), ('dropped', np.int32), ('pad', np.int32
 _SLOT = np.dtype([('id', np.int32), ('hits', np.int32), ('age', np.int32), ('misses', np.int32), ('box', np.float32, (4,)),
                   ('score', np.float32), ('keypoints', np.float32, (NUM_KEYPOINTS, 3))])
 
+# a row of mpn_pose_smooth's output and its state of one stream
+_SMOOTH_OUT = np.dtype([('keypoints', np.float32, (NUM_KEYPOINTS, 3)), ('velocities', np.float32, (NUM_KEYPOINTS, 2))])
+_SMOOTH_HEAD = np.dtype([('frames', np.int32), ('pad', np.int32, (3,))])
+_SMOOTH_SLOT = np.dtype([('id', np.int32),
+                         ('joints', [('last', np.int32), ('hat', np.float32, (4,))], (NUM_KEYPOINTS,)),     # x, y, dx, dy
+                         ('pad', np.int32, (2,))])
+
 _serials = itertools.count(1)
+
+
+class OneEuro:
+    """The parameters of the One-Euro filter `PoseTracker(smooth=...)` runs on every tracked joint. Immutable.
+
+    rate: frames per second of a stream (a frame a person is missing from still counts as 1 / rate seconds).
+    min_cutoff: the low-pass cutoff in Hz at rest - lower is smoother and lags more. beta: how fast the cutoff rises with the
+    estimated speed, Hz per (pixel / second) - higher follows fast motion more closely. d_cutoff: the cutoff of the speed
+    estimate itself. min_keypoint_score: a sample whose score is below it (not >=) is returned raw and restarts the joint's
+    filter."""
+    __slots__ = ('rate', 'min_cutoff', 'beta', 'd_cutoff', 'min_keypoint_score')
+
+    def __init__(self, rate=30.0, min_cutoff=1.0, beta=0.007, d_cutoff=1.0, min_keypoint_score=0.0):
+        values = dict(rate=rate, min_cutoff=min_cutoff, beta=beta, d_cutoff=d_cutoff, min_keypoint_score=min_keypoint_score)
+        for name, v in values.items():
+            try:
+                with np.errstate(over='ignore'):
+                    v = float(np.float32(v))                        # what the launch receives (too large: inf, refused below)
+            except (TypeError, ValueError):
+                raise ValueError(f"OneEuro: {name} must be a number (got {v!r})") from None
+            if not math.isfinite(v):
+                raise ValueError(f"OneEuro: {name} must be finite (got {values[name]!r})")
+            if name in ('rate', 'min_cutoff', 'd_cutoff') and not v > 0:
+                raise ValueError(f"OneEuro: {name} must be > 0 (got {values[name]!r})")
+            if name == 'beta' and not v >= 0:
+                raise ValueError(f"OneEuro: beta must be >= 0 (got {values[name]!r})")
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("OneEuro is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("OneEuro is immutable")
+
+    def astuple(self):
+        return (self.rate, self.min_cutoff, self.beta, self.d_cutoff, self.min_keypoint_score)
+
+    def __eq__(self, other):
+        return isinstance(other, OneEuro) and self.astuple() == other.astuple()
+
+    def __hash__(self):
+        return hash(self.astuple())
+
+    def __repr__(self):
+        return "OneEuro(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
 
 
 class PoseTracker:
@@ -43,12 +103,17 @@ class PoseTracker:
     IoU of the boxes). A pair matches at similarity >= match_threshold, the largest first; a track unmatched for more than
     max_misses frames in a row is dropped; an unmatched detection with score >= new_track_score starts a track in the lowest
     free slot, or is counted in `dropped` when there is none. Ids count from 1 per stream and are never reused.
-    max_boxes: the detection slots per image of the records this tracker reads (the Detector's params['max_boxes'])."""
+    max_boxes: the detection slots per image of the records this tracker reads (the Detector's params['max_boxes']).
+    smooth: None, or a OneEuro: every tracked person's keypoints are filtered on the device as well (`mpn_pose_smooth`), which
+    adds 'keypoints_smoothed' and 'keypoint_velocities' to what `unpack` / `update` / the Detector return."""
 
     def __init__(self, streams=1, max_tracks=32, similarity='oks', match_threshold=0.3, max_misses=10, new_track_score=0.3,
-                 max_boxes=25, device=None):
+                 max_boxes=25, device=None, smooth=None):
         if similarity not in SIMILARITIES:
             raise ValueError(f"similarity must be one of {sorted(SIMILARITIES)} (got {similarity!r})")
+        if smooth is not None and not isinstance(smooth, OneEuro):
+            raise ValueError(f"smooth must be None or a tracking.OneEuro (got {smooth!r})")
+        self.smooth = smooth
         self.streams, self.max_tracks, self.max_boxes = int(streams), int(max_tracks), int(max_boxes)
         self.similarity, self.max_misses = similarity, int(max_misses)
         self.match_threshold, self.new_track_score = float(match_threshold), float(new_track_score)
@@ -70,6 +135,13 @@ class PoseTracker:
         self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
         self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
         self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
+        if smooth is not None:
+            self.smooth_state_bytes = lib.mpn_pose_smooth_state_bytes(self.streams, self.max_tracks)
+            self.smooth_stream_bytes = _SMOOTH_HEAD.itemsize + self.max_tracks * _SMOOTH_SLOT.itemsize
+            if self.smooth_state_bytes == 0 or self.smooth_state_bytes != self.streams * self.smooth_stream_bytes:
+                raise _lib.MpnError("mpn_pose_smooth: the state's layout is not the one this binding was written against")
+            self.smooth_prev = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
+            self.smooth_next = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
         self._update = {}                                           # update(): device record and rows per batch size
 
     def check_batch(self, b):
@@ -78,54 +150,106 @@ class PoseTracker:
             raise ValueError(f"track=: {b} images are not a whole number of frames for each of {self.streams} streams")
         return b // self.streams
 
-    def out_bytes(self, b):
+    def track_bytes(self, b):
+        """The bytes of mpn_pose_track's rows for b images."""
         self.check_batch(b)
         n = _lib.lib().mpn_pose_track_out_bytes(b, self.max_boxes)
         if n == 0 or n != b * self.max_boxes * _OUT.itemsize:
             raise ValueError(f"mpn_pose_track: {b} x {self.max_boxes} slots are more than one launch takes")
         return n
 
+    def out_bytes(self, b):
+        """The bytes of a call's rows for b images: the track rows and, with smooth=, the smoothed rows behind them."""
+        n = self.track_bytes(b)
+        if self.smooth is not None:
+            m = _lib.lib().mpn_pose_smooth_out_bytes(b, self.max_boxes)
+            if m == 0 or m != b * self.max_boxes * _SMOOTH_OUT.itemsize:
+                raise ValueError(f"mpn_pose_smooth: {b} x {self.max_boxes} slots are more than one launch takes")
+            n += m
+        return n
+
     def launch(self, record, out, b):
         """record: the uint8 device tensor mpn_pose_gather wrote for (b, max_boxes); out: uint8 device tensor of
-        `out_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`."""
+        `track_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`."""
         self.check_batch(b)
         _lib.call("mpn_pose_track", _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
                   SIMILARITIES[self.similarity], self.match_threshold, self.new_track_score, self.max_misses,
                   _lib.ptr(self.prev), _lib.ptr(self.next), _lib.ptr(out), _lib.stream_ptr())
         return out
 
+    def launch_smooth(self, record, track_out, out, b):
+        """record and track_out: what `launch` read and wrote (uint8 device tensors); out: uint8 device tensor of
+        `out_bytes(b) - track_bytes(b)`. Reads `smooth_prev`, writes `smooth_next` and out; `commit()` advances the state."""
+        if self.smooth is None:
+            raise ValueError("launch_smooth: this tracker was made without smooth=")
+        self.check_batch(b)
+        _lib.call("mpn_pose_smooth", _lib.ptr(record), _lib.ptr(track_out), b, self.max_boxes, self.streams, self.max_tracks,
+                  *self.smooth.astuple(), _lib.ptr(self.smooth_prev), _lib.ptr(self.smooth_next), _lib.ptr(out),
+                  _lib.stream_ptr())
+        return out
+
+    def launch_all(self, record, out, b):
+        """`launch` and, with smooth=, `launch_smooth` behind it: out is a uint8 device tensor of `out_bytes(b)`, the track rows
+        first."""
+        n = self.track_bytes(b)
+        self.launch(record, out[:n], b)
+        if self.smooth is not None:
+            self.launch_smooth(record, out[:n], out[n:], b)
+        return out
+
     def commit(self):
-        """The last launch's state becomes the current one: one small device copy on the current stream."""
+        """The last launch's state becomes the current one: one small device copy on the current stream (two with smooth=)."""
         self.prev.copy_(self.next, non_blocking=True)
+        if self.smooth is not None:
+            self.smooth_prev.copy_(self.smooth_next, non_blocking=True)
 
     def reset(self, stream=None):
         """Forget every track and start the ids at 1 again: of all streams, or of one."""
         if stream is None:
             self.prev.zero_()
             self.next.zero_()
+            if self.smooth is not None:
+                self.smooth_prev.zero_()
+                self.smooth_next.zero_()
             return
         if not 0 <= int(stream) < self.streams:
             raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
         at = int(stream) * self.stream_bytes
         self.prev[at:at + self.stream_bytes].zero_()
         self.next[at:at + self.stream_bytes].zero_()
+        if self.smooth is not None:
+            at = int(stream) * self.smooth_stream_bytes
+            self.smooth_prev[at:at + self.smooth_stream_bytes].zero_()
+            self.smooth_next[at:at + self.smooth_stream_bytes].zero_()
 
     def unpack(self, out, counts):
         """A host copy of the output rows (uint8 array) and the record's per-image counts -> a list of dicts, one per image:
         'track_ids' int32 [n] (0 = untracked), 'track_hits' int32 [n], 'track_new' bool [n], 'track_similarity' f64 [n],
-        in the image's record order."""
-        rows = np.frombuffer(out, np.uint8, len(counts) * self.max_boxes * _OUT.itemsize).view(_OUT)
+        in the image's record order. With smooth= the smoothed rows lie behind the track rows and add 'keypoints_smoothed' f32
+        [n,17,3] (x, y, score; raw for an untracked person, a joint's first sample and a sample below min_keypoint_score) and
+        'keypoint_velocities' f32 [n,17,2] (pixels per second; 0 there)."""
+        slots = len(counts) * self.max_boxes
+        rows = np.frombuffer(out, np.uint8, slots * _OUT.itemsize).view(_OUT)
+        smooth = None
+        if self.smooth is not None:
+            smooth = np.frombuffer(out, np.uint8, slots * _SMOOTH_OUT.itemsize, slots * _OUT.itemsize).view(_SMOOTH_OUT)
         res, s = [], 0
         for n in counts:
             r = rows[s:s + int(n)]
             res.append({'track_ids': r['track_id'].copy(), 'track_hits': r['hits'].copy(),
                         'track_new': (r['flags'] & FLAG_NEW) != 0, 'track_similarity': r['similarity'].copy()})
+            if smooth is not None:
+                res[-1]['keypoints_smoothed'] = smooth['keypoints'][s:s + int(n)].copy()
+                res[-1]['keypoint_velocities'] = smooth['velocities'][s:s + int(n)].copy()
             s += int(n)
         return res
 
     def tracks(self, stream=0):
         """A host copy of one stream's current state: {'next_id', 'dropped', 'slots' int [m] (the live slots), 'ids', 'hits',
-        'age', 'misses' int32 [m], 'boxes' f32 [m,4], 'scores' f32 [m], 'keypoints' f32 [m,17,3]}."""
+        'age', 'misses' int32 [m], 'boxes' f32 [m,4], 'scores' f32 [m], 'keypoints' f32 [m,17,3]}. With smooth= also 'frames'
+        (the frames the stream's filters have seen), 'keypoints_smoothed' f32 [m,17,2] (x_hat, y_hat of the live slots; of a
+        slot whose track was not detected since the slot changed hands, the earlier track's) and 'keypoint_last' int32 [m,17]
+        (the frame number of each joint's last sample, 0 = none)."""
         if not 0 <= int(stream) < self.streams:
             raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
         at = int(stream) * self.stream_bytes
@@ -134,9 +258,17 @@ class PoseTracker:
         slots = raw[_HEAD.itemsize:].view(_SLOT)
         live = np.nonzero(slots['id'] != 0)[0]
         s = slots[live]
-        return {'next_id': max(int(head['next_id']), 1), 'dropped': int(head['dropped']), 'slots': live,
-                'ids': s['id'].copy(), 'hits': s['hits'].copy(), 'age': s['age'].copy(), 'misses': s['misses'].copy(),
-                'boxes': s['box'].copy(), 'scores': s['score'].copy(), 'keypoints': s['keypoints'].copy()}
+        res = {'next_id': max(int(head['next_id']), 1), 'dropped': int(head['dropped']), 'slots': live,
+               'ids': s['id'].copy(), 'hits': s['hits'].copy(), 'age': s['age'].copy(), 'misses': s['misses'].copy(),
+               'boxes': s['box'].copy(), 'scores': s['score'].copy(), 'keypoints': s['keypoints'].copy()}
+        if self.smooth is not None:
+            at = int(stream) * self.smooth_stream_bytes
+            raw = self.smooth_prev[at:at + self.smooth_stream_bytes].cpu().numpy()
+            joints = raw[_SMOOTH_HEAD.itemsize:].view(_SMOOTH_SLOT)['joints'][live]
+            res['frames'] = int(raw[:_SMOOTH_HEAD.itemsize].view(_SMOOTH_HEAD)[0]['frames'])
+            res['keypoints_smoothed'] = joints['hat'][..., :2].copy()
+            res['keypoint_last'] = joints['last'].copy()
+        return res
 
     def update(self, outputs):
         """The same launch for host arrays: b result dicts ('boxes', 'scores', 'keypoints' as `Detector.predict_*` returns
@@ -153,7 +285,7 @@ class PoseTracker:
                                    torch.zeros(nbytes, dtype=torch.uint8, device=self.device))
             dev_record, dev_out = self._update[b]
             dev_record.copy_(torch.from_numpy(record))
-            self.launch(dev_record, dev_out, b)
+            self.launch_all(dev_record, dev_out, b)
             self.commit()
             out = dev_out.cpu().numpy()
         return self.unpack(out, counts)

@@ -18,7 +18,14 @@ the commit copy alone on B's buffers - with --streams 1 the block walks the batc
 launch a batch can ask for; the same launch with one stream per image is reported next to it. The frames are unrelated random
 images (as in bench_predict_images.py): few persons of a frame are found again in the next, the 32 slots fill within the first
 frames and most later persons find none - the similarity matrix and the births run at full load, the greedy rounds do not.
-A run without a GPU fails."""
+A run without a GPU fails.
+
+    timeout -k 10 300 python tools/bench_pose_track.py --smooth [the same options]
+
+measures what `PoseTracker(smooth=OneEuro())` adds and writes it under the "smooth" key of --out, whose other keys stay (the
+file is read first): device time, ALTERNATING in one run, of the captured graph with a smoothing tracker against the same graph
+with a plain tracker, and of the mpn_pose_smooth launch plus its state's commit copy alone against the mpn_pose_track launch plus
+its commit copy alone. The comparison is the plain-tracker graph of the same run; no ratio is fixed in advance."""
 import argparse
 import json
 import os
@@ -38,6 +45,94 @@ from tools.bench_inference_batch import build_detector  # noqa: E402  (the livel
 from tools.bench_predict_images import events_ms  # noqa: E402
 
 
+def spread(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def smooth_leg(args, det, frames):
+    from multiposenet_amd.inference import OneEuro, PoseTracker
+    b, s, thr = args.batch, args.size, args.threshold
+    kw = dict(streams=args.streams, similarity=args.similarity, max_boxes=det.params['max_boxes'])
+    # one camera's frames that follow each other (the first frame panned by 4 pixels a frame): the tracks go on from frame to
+    # frame and their filters run, which the unrelated frames of the other legs would not make them do
+    frames = [np.roll(frames[0], 4 * f, axis=1) for f in range(b)]
+    trackers = {"plain": PoseTracker(**kw), "smooth": PoseTracker(smooth=OneEuro(), **kw)}
+    tracked = {}
+    for name, t in trackers.items():                                   # warm-up: graphs captured, states filled
+        for _ in range(3):
+            outs = det.predict_images(frames, size=(s, s), score_threshold=thr, track=t)
+        tracked[name] = sum(int((o['track_ids'] > 0).sum()) for o in outs) / b
+    filtered = sum(int(np.count_nonzero(o['keypoint_velocities'].any(axis=2))) for o in outs) / b
+    ents = {name: next(e for e in det._graphs.values() if getattr(e, 'track', None) is t) for name, t in trackers.items()}
+    t = trackers["smooth"]
+    whole = ents["smooth"].outs['record']
+    nbytes = whole.numel() - t.out_bytes(b)
+    record, rows, out = whole[:nbytes], whole[nbytes:nbytes + t.track_bytes(b)], whole[nbytes + t.track_bytes(b):]
+
+    def track_and_commit():
+        t.launch(record, rows, b)
+        t.prev.copy_(t.next, non_blocking=True)
+
+    def smooth_and_commit():
+        t.launch_smooth(record, rows, out, b)
+        t.smooth_prev.copy_(t.smooth_next, non_blocking=True)
+    # the same launch with EVERY person of the record tracked (handwritten track rows: person r of a frame in slot r, id r + 1):
+    # all filters of a frame step in every frame, which the tracker's own rows do not make them do when few persons of a
+    # frame are found again in the next
+    from multiposenet_amd import tracking
+    counts = whole[4:4 + 4 * b].cpu().numpy().view(np.int32)
+    full_rows = np.zeros(b * t.max_boxes, tracking._OUT)
+    full_rows['slot'] = -1
+    at = 0
+    for n in counts:
+        m = min(int(n), t.max_tracks)
+        full_rows['slot'][at:at + m] = np.arange(m)
+        full_rows['track_id'][at:at + m] = np.arange(m) + 1
+        at += int(n)
+    full_rows_dev = torch.from_numpy(full_rows.view(np.uint8)).to(whole.device)
+    full_out = torch.zeros_like(out)
+
+    def smooth_full_and_commit():
+        t.launch_smooth(record, full_rows_dev, full_out, b)
+        t.smooth_prev.copy_(t.smooth_next, non_blocking=True)
+    timed = {"graph_with_smoothing_tracker": ents["smooth"].graph.replay, "graph_with_plain_tracker": ents["plain"].graph.replay,
+             "smooth_launch_and_commit": smooth_and_commit, "smooth_launch_and_commit_every_person_tracked": smooth_full_and_commit,
+             "track_launch_and_commit": track_and_commit}
+    for fn in timed.values():
+        fn()
+    ms = {name: [] for name in timed}
+    for _ in range(args.rounds):
+        for name, fn in timed.items():
+            ms[name].append(events_ms(fn, 20))
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    velocities = full_out.cpu().numpy().view(tracking._SMOOTH_OUT)['velocities']
+    t.reset()                                                          # (the handwritten rows left filters no track owns)
+    result = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "batch": b, "streams": args.streams,
+              "source": list(args.source), "size": [s, s], "score_threshold": thr, "similarity": args.similarity,
+              "max_tracks": t.max_tracks, "rounds": args.rounds, "one_euro": repr(t.smooth),
+              "tracked_per_image": tracked, "filtered_joints_per_image": filtered,
+              "filtered_joints_per_image_every_person_tracked": int(np.count_nonzero(velocities.any(axis=2))) / b,
+              "smooth_rows_d2h_bytes_per_batch": int(t.out_bytes(b) - t.track_bytes(b)), "smooth_state_bytes": int(t.smooth_state_bytes),
+              "device_ms_per_batch": {name: spread(v) for name, v in ms.items()},
+              "graph_added_ms": med["graph_with_smoothing_tracker"] - med["graph_with_plain_tracker"],
+              "graph_with_smoothing_over_plain": med["graph_with_smoothing_tracker"] / med["graph_with_plain_tracker"],
+              "smooth_over_track_launch": med["smooth_launch_and_commit"] / med["track_launch_and_commit"],
+              "smooth_every_person_tracked_over_track_launch":
+                  med["smooth_launch_and_commit_every_person_tracked"] / med["track_launch_and_commit"]}
+    merged = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            merged = json.load(f)
+    merged["smooth"] = result
+    out_dir = os.path.dirname(args.out)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"smooth": result}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -50,6 +145,7 @@ def main():
     ap.add_argument("--similarity", default="oks", choices=["oks", "iou"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--out", default=os.path.join("profiles", "pose_track.json"))
+    ap.add_argument("--smooth", action="store_true", help="only the smoothing leg; merged into --out under 'smooth'")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_pose_track: no GPU (a measurement path does not fall back)")
@@ -61,6 +157,8 @@ def main():
     yy, xx = np.arange(sh) * s // sh, np.arange(sw) * s // sw          # structure at the network's scale (bench_predict_images.py)
     frames = [np.ascontiguousarray(rng.randint(0, 256, (s, s, 3)).astype(np.uint8)[yy][:, xx]) for _ in range(b)]
     max_boxes = det.params['max_boxes']
+    if args.smooth:
+        return smooth_leg(args, det, frames)
     tracker = PoseTracker(streams=args.streams, similarity=args.similarity, max_boxes=max_boxes)
     p = ref.Params(tracker.max_tracks, args.similarity, tracker.match_threshold, tracker.max_misses, tracker.new_track_score)
     host_state = ref.new_state(args.streams, tracker.max_tracks)
@@ -111,9 +209,6 @@ def main():
     plain_ms = [events_ms(plain.graph.replay, 20) for _ in range(args.rounds)]
     track_ms = [events_ms(lambda: track_and_commit(tracker), 20) for _ in range(args.rounds)]
     track_per_image_ms = [events_ms(lambda: track_and_commit(per_image), 20) for _ in range(args.rounds)]
-
-    def spread(v):
-        return {"median": statistics.median(v), "min": min(v), "max": max(v)}
     result = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "batch": b, "streams": args.streams,
               "source": [sh, sw], "size": [s, s], "score_threshold": thr, "similarity": args.similarity,
               "max_tracks": tracker.max_tracks, "batches_per_leg_round": args.batches, "rounds": args.rounds,
@@ -134,6 +229,9 @@ def main():
     result["track_rate_over_plain"] = rate["predict_images_track"] / rate["predict_images"]
     result["track_rate_over_host_tracker"] = rate["predict_images_track"] / rate["predict_images_host_tracker"]
     result["track_share_of_graph_device_time"] = statistics.median(track_ms) / statistics.median(graph_ms)
+    if os.path.exists(args.out):                                       # the --smooth run's record stays
+        with open(args.out) as f:
+            result.update({k: v for k, v in json.load(f).items() if k == "smooth"})
     out_dir = os.path.dirname(args.out)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
