@@ -1116,6 +1116,63 @@ int mpn_draw_detections(const uint8_t* sources, size_t sources_bytes, const void
                         void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Annotated frames of TRACKED persons: the picture of mpn_draw_detections with a colour per identity and the id as a label,
+ * equal byte for byte to what Pillow draws for it (tests/draw_tracks_ref.py restates it; tests/test_draw_tracks_host.py holds
+ * the restatement against Pillow). sources, descs, record, with_keypoints, out_rgba, the geometry of box, lines and dots, the
+ * clamping and the draw order (per KEPT person in record order: box, 16 lines, 17 dots, then the label; a pixel takes the
+ * LAST primitive that covers it) are those of mpn_draw_detections. What differs, per person (record row r):
+ *   colours      track_id = int32 at byte 0 of row r of track_rows (24-byte rows, mpn_pose_track's out for the same record).
+ *                track_id <= 0, untracked: red box, white lines, red dots as mpn_draw_detections draws them - or, with the
+ *                hide flag, nothing at all. track_id > 0: box and dots in palette[(track_id - 1) % P], lines in line_colour.
+ *   keypoints    smooth_rows NULL: the notebook's f64 / f32 arithmetic from box and keypoint_positions, unchanged.
+ *                Otherwise (x, y) = the f32 pair at floats 3k, 3k+1 of row r of smooth_rows (340-byte rows, mpn_pose_smooth's
+ *                out): lines from (trunc x_a, trunc y_a) to (trunc x_b, trunc y_b), dot corners trunc(x - 2.0f) ..
+ *                trunc(x + 2.0f) in f32. (For an untracked person those rows hold the record's own float32 keypoints.)
+ *   label        only with the labels flag, for track_id > 0 and a box that is drawn (x1 >= x0 and y1 >= y0); also with
+ *                with_keypoints = 0. The text is the decimal digits of track_id, n = 1..10 of them, one per cell. With
+ *                pad = 1, lw = 2*pad + n*cell, lh = 2*pad + (bot - top) and the box's integer corner (x0, y0):
+ *                    lx0 = x0;  ly0 = y0 - lh if that is >= 0, else y0     (above the box, or inside it at the frame's top)
+ *                the FILLED rectangle [lx0, ly0, lx0+lw-1, ly0+lh-1] in the identity colour; digit k (from the left, value d)
+ *                has its stamp's top left at (lx0 + pad + k*cell + ox_d, ly0 + pad - top + oy_d), and a pixel under stamp
+ *                byte m is, per colour channel, BLEND8(m, identity, text): t = m*text + (255-m)*identity + 128;
+ *                ((t >> 8) + t) >> 8; alpha 255. In Pillow's terms: draw.rectangle(fill=identity), then draw.text per digit
+ *                at (lx0 + pad + k*cell, ly0 + pad - top) with a font whose getmask2(d, 'L') is (stamp_d, (ox_d, oy_d)),
+ *                cell = max ceil(getlength(d)), top = min oy_d, bot = max (oy_d + h_d). Every stamp lies at most the padding
+ *                outside its cell (-pad <= ox_d, ox_d + w_d <= cell + pad, top <= oy_d, oy_d + h_d <= bot), hence inside the
+ *                rectangle. A glyph wider than its advance reaches into the neighbouring cell: a pixel under the stamps of two
+ *                digits is blended twice, the left digit first, as Pillow draws them - BLEND8(m_right, BLEND8(m_left,
+ *                identity, text), text). Either way a label pixel is a function of the style and the id alone.
+ *   tables       DEVICE, 4-byte aligned, tables_bytes >= MPN_DRAW_TRACKS_TABLE_HEADER_BYTES; int32 words:
+ *                    0 flags (bit 0 labels, bit 1 hide untracked)   1 line_colour   2 text_colour   (R | G<<8 | B<<16)
+ *                    3 P, the palette's size, 1..MPN_DRAW_TRACKS_MAX_PALETTE   4 cell, 1..MPN_DRAW_TRACKS_MAX_CELL
+ *                    5 top   6 bot (0 <= bot - top <= MPN_DRAW_TRACKS_MAX_STAMP_H, |top| <= that too)   7 zero
+ *                    8 + 5*d .. 12 + 5*d, d = 0..9: the stamp of digit d: w, h, ox, oy, byte offset of its w*h L8 bytes
+ *                                (rows of w) from the start of tables
+ *                    58 .. 57 + P: the palette, one colour per word as above
+ *                then the stamps' bytes. mpn_draw_tracks_tables_bytes(P, cell, bot - top): the bytes that hold any such
+ *                table (header + 4*P + 10*(cell + 2*pad)*(bot-top), rounded up to 16); 0 for arguments out of range.
+ *                The style is DATA: a captured graph serves any later table of at most tables_bytes. The kernels check every
+ *                index they derive from the table against tables_bytes and the limits above; a palette that does not fit
+ *                leaves a tracked person undrawn, a label whose cell, top / bot or digit stamps fail a check is not drawn.
+ *   workspace    mpn_draw_tracks_workspace_bytes(B, max_boxes) bytes (0 out of range; more than mpn_draw_detections needs),
+ *                16-byte aligned.
+ * Two launches with the grids of mpn_draw_detections, no scatter, no atomics on global memory: the output is a function of
+ * the inputs. Checked before any HIP call: null track_rows / tables (MPN_ERR_BAD_ARG; smooth_rows may be NULL); everything
+ * mpn_draw_detections checks, with the same codes; track_rows / smooth_rows / tables not 4-byte aligned (MPN_ERR_BAD_ALIGN);
+ * tables_bytes < MPN_DRAW_TRACKS_TABLE_HEADER_BYTES (MPN_ERR_WORKSPACE).
+ */
+#define MPN_DRAW_TRACKS_MAX_PALETTE 256
+#define MPN_DRAW_TRACKS_MAX_CELL 32
+#define MPN_DRAW_TRACKS_MAX_STAMP_H 48
+#define MPN_DRAW_TRACKS_TABLE_HEADER_BYTES 232
+size_t mpn_draw_tracks_tables_bytes(int palette_size, int cell_w, int stamp_h);
+size_t mpn_draw_tracks_workspace_bytes(int B, int max_boxes);
+int mpn_draw_tracks(const uint8_t* sources, size_t sources_bytes, const void* descs, const void* record, size_t record_bytes,
+                    const void* track_rows, const void* smooth_rows, const void* tables, size_t tables_bytes, int B,
+                    int max_boxes, int with_keypoints, uint8_t* out_rgba, size_t out_bytes, void* workspace,
+                    size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Heatmap and mask overlays: `plot_maps` of the reference's inference/predict.ipynb (the cells under "Show heatmaps") for
  * a batch of B frames of one size, equal byte for byte to what Pillow and matplotlib make there. With h = H / 2, w = W / 2
  * (integer division), panel j of frame b is rows j*h .. j*h + h - 1 of out_rgba[b]: the frame resized to (w, h) with

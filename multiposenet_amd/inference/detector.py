@@ -72,6 +72,22 @@ def check_annotate(annotate, jpeg_quality, jpeg_subsampling):
     return int(jpeg_quality), jpeg_subsampling
 
 
+def check_track_style(track_style, annotate, track):
+    """The `track_style` argument of the predict_* methods -> () or the tail of the entry's key. Before any device work."""
+    if track_style is None:
+        return ()
+    if not isinstance(track_style, draw.TrackStyle):
+        raise ValueError(f"track_style must be None or an inference.TrackStyle (got {track_style!r})")
+    if not annotate:
+        raise ValueError("track_style= says how annotate draws tracked persons: it needs annotate=True or 'jpeg'")
+    if track is None:
+        raise ValueError("track_style= colours persons by their track ids: it needs track=, a tracking.PoseTracker")
+    if track_style.keypoints == 'smoothed' and getattr(track, 'smooth', None) is None:
+        raise ValueError("track_style: keypoints='smoothed' draws the tracker's smoothed keypoints; this tracker was made "
+                         "without smooth=")
+    return ('style', track_style)
+
+
 def check_plot_maps(plot_maps, heatmap_outputs):
     """The `plot_maps` argument of the predict_* methods -> bool. True needs a graph with heatmap outputs (a bool, or a
     callable asked only then): without them there is nothing to plot, and that is an error up front, not an empty picture."""
@@ -127,10 +143,10 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -326,7 +342,7 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None):
+                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -372,17 +388,24 @@ class Detector:
                 with smooth=OneEuro(...) (needs the PRN) also adds 'keypoints_smoothed' f32 [n, 17, 3] - the One-Euro filtered
                 (x, y) of every tracked person's joints with the frame's score, in the coordinates of this call's 'keypoints' -
                 and 'keypoint_velocities' f32 [n, 17, 2] in pixels per second: one mpn_pose_smooth launch behind the track
-                launch in the same graph, its rows in the same copy. `annotate` still draws the frame's own detections.
+                launch in the same graph, its rows in the same copy. Without `track_style`, `annotate` still draws the frame's own
+                detections in red and white.
+            track_style: None, or an inference.TrackStyle (needs annotate and track): 'annotated' / 'annotated_jpeg' then carry
+                the identities - mpn_draw_tracks in place of mpn_draw_detections, on the record, the track rows and (for
+                keypoints='smoothed') the smoothed rows the graph has just produced: every tracked person's box, dots and an
+                id label in the colour of its track, untracked persons as before or hidden. The style is part of the
+                graph's key; its table goes to the device once, when the entry is made. None changes nothing.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        style = check_track_style(track_style, annotate, track)
         plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         b, h, w = check_batch(images)
         thr = float(score_threshold)
         oks = self._check_groundtruth(groundtruth, b)
         trk = self._check_track(track, b)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w), trk, track)
+        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w), trk, track, style)
         if oks:
             ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
         if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
@@ -395,7 +418,7 @@ class Detector:
                 stage[i] = im
         ent.x[:b].copy_(ent.stage, non_blocking=True)               # ONE host-to-device copy
         outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps,
-                                                              oks=ent.oks, aug=ent.tta, track=ent.track))
+                                                              oks=ent.oks, aug=ent.tta, track=ent.track, style=ent.style))
         if trk:
             ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
         return self._finish(ent, outs, b, return_heatmaps)
@@ -440,6 +463,12 @@ class Detector:
             raise ValueError(f"track=: the tracker lives on {track.device}, this Detector on {self.net.device}")
         track.out_bytes(b)
         return ('track', track.serial, b)
+
+    def _place_style(self, style):
+        """A check_track_style key -> None or (TrackStyle, its table on the device): uploaded once, when the entry is made."""
+        if not style:
+            return None
+        return style[1], torch.from_numpy(style[1].tables().copy()).to(self.net.device)
 
     def _oks_buffers(self, b, oks):
         return pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, self.net.device, oks[1], oks[2])
@@ -501,7 +530,8 @@ class Detector:
                 p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=(), trk=(), track=None):
+    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=(), trk=(), track=None,
+                     style=()):
         """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks][, tta][, track]): pinned staging, the device input (with the
         mirrors behind the batch and the inputs of the extra scales for a check_tta key), fixed drawing and
         encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
@@ -510,7 +540,7 @@ class Detector:
             key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
         if plot_maps:
             key += ('maps',)
-        key += oks + tta_key + trk
+        key += oks + tta_key + trk + style
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
@@ -531,6 +561,7 @@ class Detector:
         if oks:
             ent.oks = self._oks_buffers(b, oks)
         ent.track = track if trk else None
+        ent.style = self._place_style(style)
         store[key] = ent
         return ent
 
@@ -543,7 +574,7 @@ class Detector:
             ent.x = torch.empty((b, h, w, 3), dtype=torch.uint8, device=self.net.device)
 
     def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None,
-                           oks=None, aug=None, track=None):
+                           oks=None, aug=None, track=None, style=None):
         """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
         b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
         the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
@@ -556,6 +587,8 @@ class Detector:
         track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
         tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits). A tracker
         with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
+        style ((TrackStyle, its table on the device), with annotate and track): the drawing is mpn_draw_tracks, which reads
+        those rows in place.
         aug (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -611,7 +644,12 @@ class Detector:
         if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
             track.launch_all(record, whole[nbytes + oks_bytes:], b)
         dev['record'] = whole
-        if annotate is not None:
+        if annotate is not None and style is not None:              # identities: mpn_draw_tracks on the rows just written
+            rows = whole[nbytes + oks_bytes:]
+            n = track.track_bytes(b)
+            smoothed = rows[n:] if style[0].keypoints == 'smoothed' else None
+            dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, style[1], self.assigner is not None)
+        elif annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
         return self._encode_frames(dev, encode)
 
@@ -640,7 +678,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None):
+                       flip=False, scales=None, track=None, track_style=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -666,12 +704,14 @@ class Detector:
                 ratio of `size` - not the source frames resized again.
             track: as for `predict_batch`; the tracker sees the boxes normalised to the source images and the keypoints in
                 source pixels, as they are returned.
+            track_style: as for `predict_batch`; the identities are drawn on the SOURCE frames.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
         raises ValueError.
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        style = check_track_style(track_style, annotate, track)
         plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         items = resample.check_images(images)
         height, width = resample.check_size(size)
@@ -685,12 +725,12 @@ class Detector:
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
         return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key, track)
+                                     tta_key, track, style)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None, flip=False, scales=None, track=None):
+                      groundtruth=None, flip=False, scales=None, track=None, track_style=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -707,11 +747,12 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales, track: as for `predict_images`.
+            flip, scales, track, track_style: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
         jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
+        style = check_track_style(track_style, annotate, track)
         plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
         if isinstance(jpegs, (bytes, bytearray, memoryview)):
             raise ValueError("jpegs must be a list of bytes (got one bytes object)")
@@ -735,10 +776,10 @@ class Detector:
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
             self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
         return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key, track)
+                                     tta_key, track, style)
 
     def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False,
-                         groundtruth=None, tta_key=(), track=None):
+                         groundtruth=None, tta_key=(), track=None, style=()):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
         one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
@@ -746,7 +787,7 @@ class Detector:
         eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
         oks = self._check_groundtruth(groundtruth, b)
         trk = self._check_track(track, b)
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key, trk, track)
+        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key, trk, track, style)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
@@ -767,7 +808,7 @@ class Detector:
         return persons
 
     def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=(), tta_key=(), trk=(),
-                      track=None):
+                      track=None, style=()):
         """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
         of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
         graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
@@ -783,7 +824,7 @@ class Detector:
         tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
         if plot_maps:
             tail += ('maps',)
-        tail += oks + tta_key + trk
+        tail += oks + tta_key + trk + style
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -815,6 +856,7 @@ class Detector:
         if oks:
             ent.oks = self._oks_buffers(b, oks)
         ent.track = track if trk else None
+        ent.style = self._place_style(style)
         store[key] = ent
         return ent
 
@@ -828,7 +870,7 @@ class Detector:
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
         return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps,
-                                       oks=ent.oks, aug=ent.tta, track=ent.track)
+                                       oks=ent.oks, aug=ent.tta, track=ent.track, style=ent.style)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

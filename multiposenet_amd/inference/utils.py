@@ -170,3 +170,70 @@ def draw_everything(image, outputs):
         buffers.place([(h, w)], [0])
         out = buffers.launch(torch.from_numpy(image.reshape(-1)).to(device), torch.from_numpy(record).to(device), len(pos) > 0)
         return buffers.unpack(out[:buffers.out_bytes].cpu().numpy())[0]
+
+
+def draw_tracks(image, outputs, style=None):
+    """
+    `draw_everything` for persons with identities, drawn on the device by `mpn_draw_tracks`: every tracked person's box, dots
+    and id label in the colour of its track, as `Detector.predict_*(annotate=True, track=..., track_style=style)` draws them.
+
+    Arguments:
+        image: a uint8 array with shape [height, width, 3], or anything `np.asarray` turns into one (a PIL image).
+        outputs: a dict with 'boxes' [n, 4], 'keypoint_positions' [n, 17, 2] (no rows at all: boxes and labels only) and
+            'track_ids' [n] (0 = untracked) as `Detector.predict_*(track=...)` returns them; for a style with
+            keypoints='smoothed' also 'keypoints_smoothed' [n, 17, 3].
+        style: an inference.TrackStyle; None is TrackStyle().
+    Returns:
+        a numpy uint8 array with shape [height, width, 4]: RGBA, alpha 255.
+    """
+    import torch
+    from . import draw
+    from .detector import _ROW
+    style = draw.TrackStyle() if style is None else style
+    if not isinstance(style, draw.TrackStyle):
+        raise ValueError(f"style must be None or an inference.TrackStyle (got {style!r})")
+    image = np.ascontiguousarray(np.asarray(image))
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"image must be uint8 [height, width, 3] (got {image.dtype} {tuple(image.shape)})")
+    boxes = np.asarray(outputs['boxes'], np.float32).reshape(-1, 4)
+    pos = np.asarray(outputs['keypoint_positions'], np.float32).reshape(-1, NUM_KEYPOINTS, 2)
+    ids = np.asarray(outputs['track_ids']).reshape(-1)
+    n = len(boxes)
+    if len(ids) != n:
+        raise ValueError(f"{n} boxes but {len(ids)} track_ids")
+    smoothed = None
+    if style.keypoints == 'smoothed':
+        if 'keypoints_smoothed' not in outputs:
+            raise ValueError("a style with keypoints='smoothed' needs outputs['keypoints_smoothed']")
+        smoothed = np.asarray(outputs['keypoints_smoothed'], np.float32).reshape(-1, NUM_KEYPOINTS, 3)
+    with_keypoints = len(smoothed if smoothed is not None else pos) > 0
+    if len(smoothed if smoothed is not None else pos) not in (0, n):
+        raise ValueError(f"{n} boxes but {len(smoothed if smoothed is not None else pos)} rows of keypoints")
+    if n > draw.MAX_BOXES:
+        raise ValueError(f"draw_tracks draws at most {draw.MAX_BOXES} persons (got {n})")
+    lib = _lib.lib()
+    slots = max(n, 1)
+    first, size = lib.mpn_pose_gather_row_offset(1, slots, 0), lib.mpn_pose_gather_record_bytes(1, slots)
+    if size != first + slots * _ROW.itemsize:
+        raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
+    record = np.zeros(size, np.uint8)
+    record[:8].view(np.int32)[:] = (n, n)                                   # total, counts[0]
+    rows = record[first:].view(_ROW)
+    rows['box'][:n] = boxes
+    if len(pos) == n:
+        rows['keypoint_positions'][:n] = pos
+    track_rows = np.zeros((slots, 6), np.int32)                             # mpn_pose_track's rows: track_id first
+    track_rows[:n, 0] = ids
+    smooth_rows = None
+    if smoothed is not None:
+        smooth_rows = np.zeros((slots, 85), np.float32)                     # mpn_pose_smooth's rows: keypoints first
+        if len(smoothed) == n:
+            smooth_rows[:n, :NUM_KEYPOINTS * 3] = smoothed.reshape(n, -1)
+    device = _lib.current_device()
+    with torch.cuda.device(device):
+        h, w = image.shape[:2]
+        buffers = draw.Buffers(1, slots, h * w * 3, device)
+        buffers.place([(h, w)], [0])
+        up = lambda a: None if a is None else torch.from_numpy(a.reshape(-1).view(np.uint8).copy()).to(device)   # noqa: E731
+        out = buffers.launch_tracks(up(image), up(record), up(track_rows), up(smooth_rows), up(style.tables()), with_keypoints)
+        return buffers.unpack(out[:buffers.out_bytes].cpu().numpy())[0]

@@ -5,6 +5,7 @@
         [--similarity oks|iou] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
         [--score-threshold 0.05] [--smooth [--fps 30] [--min-cutoff 1.0] [--beta 0.007] [--d-cutoff 1.0]
         [--min-keypoint-score 0.0]]
+        [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -15,7 +16,10 @@ advance the tracks by frames the video does not have. --out gets one JSON line p
 track id (0 = untracked), the box (ymin, xmin, ymax, xmax, normalised to the frame) and the keypoints (x, y, score) in the
 frame's pixels. --smooth runs a One-Euro filter over every tracked joint on the device as well (`tracking.OneEuro`; --fps is
 the video's frame rate) and adds "keypoints_smoothed" (x, y, score) and "keypoint_velocities" (pixels per second) to every
-line; beta multiplies a speed in frame pixels and so depends on the resolution. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+line; beta multiplies a speed in frame pixels and so depends on the resolution. --frames-out DIR also writes every frame as
+DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in a colour per track (`inference.TrackStyle`;
+--draw-smoothed draws the smoothed keypoints, --hide-untracked leaves persons without an id out) - drawn and JPEG-encoded on
+the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -63,6 +67,11 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=0.007)
     ap.add_argument("--d-cutoff", type=float, default=1.0)
     ap.add_argument("--min-keypoint-score", type=float, default=0.0)
+    ap.add_argument("--frames-out", metavar="DIR", help="write every frame as DIR/<name>.jpg with its tracked persons drawn on it")
+    ap.add_argument("--jpeg-quality", type=int, default=75, help="of the written frames (--frames-out)")
+    ap.add_argument("--label-size", type=int, default=10, help="font size of the id labels (--frames-out)")
+    ap.add_argument("--draw-smoothed", action="store_true", help="draw the smoothed keypoints (--frames-out, needs --smooth)")
+    ap.add_argument("--hide-untracked", action="store_true", help="leave persons without an id out of the frames (--frames-out)")
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
@@ -72,7 +81,7 @@ def main(argv=None):
 
     import torch
     from .evaluate_pose import _random_head
-    from .inference import Detector, OneEuro, PoseTracker
+    from .inference import Detector, OneEuro, PoseTracker, TrackStyle
     from .prn import initial_values
     smooth = None
     if args.smooth:
@@ -81,6 +90,18 @@ def main(argv=None):
                              min_keypoint_score=args.min_keypoint_score)
         except ValueError as e:
             ap.error(str(e))
+    draw = {}
+    if args.frames_out is not None:
+        if args.draw_smoothed and smooth is None:
+            ap.error("--draw-smoothed needs --smooth")
+        try:
+            style = TrackStyle(label_size=args.label_size, keypoints="smoothed" if args.draw_smoothed else "frame",
+                               untracked="hide" if args.hide_untracked else "plain")
+            style.tables()
+        except ValueError as e:
+            ap.error(str(e))
+        draw = dict(annotate="jpeg", jpeg_quality=args.jpeg_quality, track_style=style)
+        os.makedirs(args.frames_out, exist_ok=True)
     if args.detector is None or args.prn is None:
         print("[track_frames] no --detector / --prn file: seeded random weights, the tracks mean nothing")
     det = Detector(args.model, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
@@ -99,10 +120,10 @@ def main(argv=None):
                 with open(os.path.join(args.images, name), "rb") as f:
                     files.append(f.read())
             if all(_is_jpeg(data) for data in files):
-                outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker)
+                outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, **draw)
             else:
                 outs = det.predict_images([_pixels(data) for data in files], size=size, score_threshold=args.score_threshold,
-                                          track=tracker)
+                                          track=tracker, **draw)
             for name, o in zip(batch, outs):
                 line = {"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
                         "keypoints": o["keypoints"].tolist()}
@@ -110,6 +131,9 @@ def main(argv=None):
                     line["keypoints_smoothed"] = o["keypoints_smoothed"].tolist()
                     line["keypoint_velocities"] = o["keypoint_velocities"].tolist()
                 out.write(json.dumps(line) + "\n")
+                if draw:
+                    with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
+                        f.write(o["annotated_jpeg"])
                 persons += len(o["track_ids"])
             frames += len(batch)
     state = tracker.tracks(0)
