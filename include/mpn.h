@@ -838,8 +838,8 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
                   mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
- * Person identities across the frames of a video: the record's persons of every frame are matched greedily against the
- * tracks the earlier frames left, one block per stream.
+ * Person identities across the frames of a video: the record's persons of every frame are matched against the tracks the
+ * earlier frames left, one block per stream: greedily (mpn_pose_track) or by the optimal assignment (mpn_pose_track_optimal).
  *
  *   mpn_pose_track   record: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place exactly as
  *                     mpn_oks_match reads it (the header's total and counts, clamped the same way; only rows 0 .. total-1;
@@ -887,12 +887,51 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
  *                     (MPN_ERR_BAD_ALIGN); prev == next (MPN_ERR_BAD_ARG). The grid depends on streams alone: a captured
  *                     launch serves any later record and state.
  *   mpn_pose_track_state_bytes, mpn_pose_track_out_bytes   0 for arguments out of range.
+ *
+ *   mpn_pose_track_optimal   mpn_pose_track with the frame's matching optimal (Hungarian) instead of greedy: the same
+ *                     arguments, state layout, output rows, purity, grid and checks (in the same order; the messages begin
+ *                     "pose_track_optimal:"). Of "Per frame" only step 1 differs; steps 2 - 4 are mpn_pose_track's word for
+ *                     word. Step 1, for a frame with n detections and T = max_tracks slots:
+ *                   Similarity: s(d, t) is the f64 value mpn_pose_track computes (IoU in f32, widened; OKS in f64).
+ *                   Eligibility: the pair (d, t) is eligible when slot t is live and s >= (double)match_threshold; a NaN is
+ *                     never eligible.
+ *                   Weight: q = floor(s * 2^20) in f64, clamped to 0 .. 2^20 before the conversion to an integer; w = q + 1.
+ *                     Integers make the optimum independent of the order of summation (a last-bit difference in exp changes
+ *                     it only where s * 2^20 sits on an integer); the + 1 makes every eligible match worth taking.
+ *                   Problem: rows i = 1..n are the detections. Columns j = 1..T are the slots, cost(i, j) = -w(i-1, j-1) where
+ *                     eligible, absent otherwise. Columns j = T+1..T+n are dummies: cost(i, T+i) = 0, absent for every other
+ *                     row. Every row is assigned to a distinct column at minimal total cost: the maximum-weight matching of the
+ *                     eligible pairs, always feasible. A row on its dummy is an unmatched detection.
+ *                   Algorithm (it fixes the result where several optima exist): shortest augmenting paths in exact integers,
+ *                     potentials u[0..n] and v[0..m], p[0..m] (the row on column j, 0 = none), way[0..m], m = T + n, all 0
+ *                     at the start of the frame; rows are inserted in row order:
+ *                       for i in 1..n:
+ *                         p[0] = i; j0 = 0; minv[1..m] = absent; used[0..m] = false
+ *                         repeat:
+ *                           used[j0] = true; i0 = p[j0]; delta = absent
+ *                           for j in 1..m in increasing order, used[j] false:
+ *                             if cost(i0, j) present: cur = cost(i0, j) - u[i0] - v[j];
+ *                               if minv[j] absent or cur < minv[j]: minv[j] = cur; way[j] = j0
+ *                             if minv[j] present and (delta absent or minv[j] < delta): delta = minv[j]; j1 = j
+ *                               (ties: the smaller j)
+ *                           for j in 0..m: used[j] ? (u[p[j]] += delta, v[j] -= delta)
+ *                                                  : (minv[j] present ? minv[j] -= delta)
+ *                           j0 = j1
+ *                         until p[j0] == 0
+ *                         repeat: j1 = way[j0]; p[j0] = p[j1]; j0 = j1 until j0 == 0
+ *                     Detection p[j] - 1 is matched to slot j - 1 for every j <= T with p[j] != 0; the row's similarity is
+ *                     the unquantised f64 s of its pair. The arithmetic is in 64-bit integers. The loops over rows, over
+ *                     the repeat of a row and over its path are bounded (64, 129, 129 trips): should a bound be hit, the
+ *                     frame's remaining detections stay unmatched.
  */
 size_t mpn_pose_track_state_bytes(int streams, int max_tracks);
 size_t mpn_pose_track_out_bytes(int B, int max_boxes);
 int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
                    float match_threshold, float new_track_score, int max_misses, const void* prev, void* next, void* out,
                    mpn_stream_t stream);
+int mpn_pose_track_optimal(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                           float match_threshold, float new_track_score, int max_misses, const void* prev, void* next,
+                           void* out, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * One-Euro smoothing (Casiez, Roussel, Vogel, CHI 2012) of the tracked persons' keypoints, and the per-joint velocities its

@@ -3,6 +3,8 @@
 //   mpn_pose_track   record (read in place) + prev state -> next state + one 24-byte row per record row
 //                    {track_id, slot, hits, flags, similarity}. PURE: prev is never written; the caller advances the state by
 //                    copying next over prev (include/mpn.h says why: a captured launch runs twice on an entry's first call).
+//   mpn_pose_track_optimal   the same entry with phase C the optimal (Hungarian) assignment under integer weights; every
+//                    other phase is the same code (pose_track_kernel<kOptimal>).
 // ONE block per stream (B = streams * F images, stream s owns images s*F .. s*F+F-1 in time order); the block walks its F frames
 // in order with the working state in LDS. Per frame:
 //   phase A  the extent area of every live track's keypoints (OKS), the per-detection tables cleared
@@ -10,6 +12,7 @@
 //   phase C  greedy matching by wave 0, lane = track slot: every lane keeps the best open detection of its row (ties: the
 //            smaller detection), a 6-step xor butterfly takes the largest (ties: the smaller slot); a lane rescans its row
 //            only when the detection it held was taken. No barrier inside the rounds, at most min(tracks, detections) of them.
+//            (optimal: assign_optimal below, also wave 0 alone and without a barrier)
 //   phase D  hits / age / misses of the live tracks, tracks past max_misses freed
 //   phase E  births in row order into the lowest free slots: two ballots and popcounts, no serial walk
 //   phase F  the detections' box, score and keypoints copied into their slots, free slots zeroed, the output rows
@@ -75,6 +78,122 @@ __device__ __forceinline__ double oks_track(const float* track_kp, double area, 
     return sum / (double)kOksKeypoints;
 }
 
+// Phase C of mpn_pose_track: the greedy rounds. Wave 0, lane = track slot t; `mine` is the detection the slot takes, -1 = none.
+__device__ __forceinline__ void assign_greedy(const double (*sim)[kMaxTracks], int n, int t, bool live, double thr, int& mine,
+                                              double& mine_sim) {
+    unsigned long long taken = 0ull;
+    bool open = live, rescan = true;
+    double best = 0.0;
+    int best_d = -1;
+    for (int round = 0; round < n; ++round) {
+        if (open && rescan) {
+            best_d = -1;
+            for (int d = 0; d < n; ++d) {
+                if ((taken >> d) & 1ull) continue;
+                const double v = sim[d][t];
+                if (v >= thr && (best_d < 0 || v > best)) { best = v; best_d = d; }   // a NaN never passes v >= thr
+            }
+            rescan = false;
+        }
+        double v = best;
+        int ct = (open && best_d >= 0) ? t : -1, cd = best_d;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double v2 = __shfl_xor(v, o, 64);
+            const int t2 = __shfl_xor(ct, o, 64), d2 = __shfl_xor(cd, o, 64);
+            if (t2 >= 0 && (ct < 0 || v2 > v || (v2 == v && t2 < ct))) { v = v2; ct = t2; cd = d2; }
+        }
+        if (ct < 0) break;                        // (every lane holds the same winner: a uniform exit)
+        taken |= 1ull << cd;
+        if (ct == t) { open = false; mine = cd; mine_sim = v; }
+        else if (best_d == cd) rescan = true;
+    }
+}
+
+// the weight of an eligible pair is quantum + 1: floor(s * 2^20) in f64 (the product is exact), clamped before the conversion
+constexpr double kQuanta = 1048576.0;
+__device__ __forceinline__ long long quantum_of(double s) {
+    double q = floor(s * kQuanta);
+    q = q < 0.0 ? 0.0 : (q > kQuanta ? kQuanta : q);
+    return (long long)q;
+}
+
+// Phase C of mpn_pose_track_optimal: the shortest-augmenting-path Hungarian method of include/mpn.h in 64-bit integers (a cost
+// is at most 2^20 + 1 in size; a delta is at most the reduced cost of the way to row i's own dummy, -u[i] - v[T + i], so the
+// potentials grow by a few costs per row: about 64 * 2^20 = 2^26 at 64 x 64, 36 bits short of the type). Wave 0; rows are the
+// detections 1..n, columns 1..T the slots, T+1..T+n the rows' dummies. Lane L owns column L + 1 (slot L; "A") and column
+// T + L + 1 (the dummy of row L + 1; "B") - their v, minv, way, used and p - and the potential u of row L + 1. What the
+// current column and row decide (j0, i0, delta, the tree's rows) is the same value in every lane: a value fetched from its
+// owner by a shuffle, or the outcome of the butterfly. No LDS is written, no barrier, no atomics. Every loop has a
+// compile-time bound: a row whose search or flip does not end within it ends the frame's matching with the rows before it
+// (which cannot happen: a search takes a new column into its tree in every trip and there are at most 128).
+constexpr int kMaxCols = kMaxTracks + kMaxBoxes;
+constexpr long long kAbsent = 1ll << 62;
+
+__device__ __forceinline__ void assign_optimal(const double (*sim)[kMaxTracks], int n, int T, int lane, bool live, double thr,
+                                               int& mine, double& mine_sim) {
+    const int jA = lane < T ? lane + 1 : -1, jB = T + lane + 1;
+    long long u = 0, vA = 0, vB = 0;
+    int pA = 0, pB = 0;
+    for (int i = 1; i <= kMaxBoxes; ++i) {
+        if (i > n) break;
+        long long minvA = kAbsent, minvB = kAbsent;
+        int wayA = 0, wayB = 0;
+        bool usedA = false, usedB = false, reached = false;
+        unsigned long long tree = 0ull;                   // the rows whose column is used (and row i, on column 0)
+        int j0 = 0, i0 = i;
+        for (int trip = 0; trip <= kMaxCols; ++trip) {
+            usedA = usedA || j0 == jA;
+            usedB = usedB || j0 == jB;
+            tree |= 1ull << (i0 - 1);
+            const long long u0 = __shfl(u, i0 - 1, 64);
+            if (live && !usedA) {
+                const double s = sim[i0 - 1][lane];
+                if (s >= thr) {                           // (a NaN is never eligible)
+                    const long long cur = -(quantum_of(s) + 1) - u0 - vA;
+                    if (cur < minvA) { minvA = cur; wayA = j0; }
+                }
+            }
+            if (lane == i0 - 1 && !usedB) {
+                const long long cur = -u0 - vB;
+                if (cur < minvB) { minvB = cur; wayB = j0; }
+            }
+            // delta = the smallest minv of the unused columns, ties to the smaller column (jA < jB within a lane)
+            long long delta = kAbsent;
+            int j1 = -1;
+            if (!usedA && minvA != kAbsent) { delta = minvA; j1 = jA; }
+            if (!usedB && minvB != kAbsent && (j1 < 0 || minvB < delta)) { delta = minvB; j1 = jB; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const long long v2 = __shfl_xor(delta, o, 64);
+                const int j2 = __shfl_xor(j1, o, 64);
+                if (j2 >= 0 && (j1 < 0 || v2 < delta || (v2 == delta && j2 < j1))) { delta = v2; j1 = j2; }
+            }
+            if (j1 < 0) break;                            // (row i's own dummy is always there; uniform)
+            if ((tree >> lane) & 1ull) u += delta;
+            if (usedA) vA -= delta; else if (minvA != kAbsent) minvA -= delta;
+            if (usedB) vB -= delta; else if (minvB != kAbsent) minvB -= delta;
+            j0 = j1;
+            const int rowA = __shfl(pA, (j0 - 1) & 63, 64), rowB = __shfl(pB, (j0 - T - 1) & 63, 64);
+            i0 = j0 <= T ? rowA : rowB;
+            if (i0 < 1 || i0 > n) { reached = i0 == 0; break; }
+        }
+        if (!reached) break;
+        for (int trip = 0; trip <= kMaxCols; ++trip) {    // the path back to column 0: every column takes the row before it
+            const int wA = __shfl(wayA, (j0 - 1) & 63, 64), wB = __shfl(wayB, (j0 - T - 1) & 63, 64);
+            const int j1 = j0 <= T ? wA : wB;
+            const int rowA = __shfl(pA, (j1 - 1) & 63, 64), rowB = __shfl(pB, (j1 - T - 1) & 63, 64);
+            const int row = j1 == 0 ? i : (j1 <= T ? rowA : rowB);
+            if (j0 == jA) pA = row;
+            if (j0 == jB) pB = row;
+            j0 = j1;
+            if (j0 <= 0) break;
+        }
+    }
+    if (live && pA >= 1 && pA <= n) { mine = pA - 1; mine_sim = sim[mine][lane]; }
+}
+
+template <bool kOptimal>
 __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
     __shared__ double sim[kMaxBoxes][kMaxTracks];         // [detection][slot]: lane = slot reads consecutive doubles
     __shared__ float data[kMaxTracks][kSlotData];         // box[4], score, keypoints[17][3] of every slot
@@ -152,33 +271,10 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
             const int t = lane;
             const bool live = t < T && id[t] != 0;
             const double thr = (double)a.match_threshold;
-            unsigned long long taken = 0ull;
-            bool open = live, rescan = true;
-            double best = 0.0, mine_sim = 0.0;
-            int best_d = -1, mine = -1;
-            for (int round = 0; round < n; ++round) {
-                if (open && rescan) {
-                    best_d = -1;
-                    for (int d = 0; d < n; ++d) {
-                        if ((taken >> d) & 1ull) continue;
-                        const double v = sim[d][t];
-                        if (v >= thr && (best_d < 0 || v > best)) { best = v; best_d = d; }   // a NaN never passes v >= thr
-                    }
-                    rescan = false;
-                }
-                double v = best;
-                int ct = (open && best_d >= 0) ? t : -1, cd = best_d;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double v2 = __shfl_xor(v, o, 64);
-                    const int t2 = __shfl_xor(ct, o, 64), d2 = __shfl_xor(cd, o, 64);
-                    if (t2 >= 0 && (ct < 0 || v2 > v || (v2 == v && t2 < ct))) { v = v2; ct = t2; cd = d2; }
-                }
-                if (ct < 0) break;                        // (every lane holds the same winner: a uniform exit)
-                taken |= 1ull << cd;
-                if (ct == t) { open = false; mine = cd; mine_sim = v; }
-                else if (best_d == cd) rescan = true;
-            }
+            double mine_sim = 0.0;
+            int mine = -1;
+            if (kOptimal) assign_optimal(sim, n, T, lane, live, thr, mine, mine_sim);
+            else assign_greedy(sim, n, t, live, thr, mine, mine_sim);
             if (live) {
                 if (mine >= 0) {
                     misses[t] = 0; hits[t] += 1; age[t] += 1;
@@ -268,26 +364,42 @@ extern "C" size_t mpn_pose_track_out_bytes(int B, int max_boxes) {
     return (size_t)B * max_boxes * kOutBytes;
 }
 
-extern "C" int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
-                              float match_threshold, float new_track_score, int max_misses, const void* prev, void* next,
-                              void* out, mpn_stream_t stream) {
-    MPN_REQUIRE(record && prev && next && out, MPN_ERR_BAD_ARG, "pose_track: null pointer");
+// the checks and the launch of both entries; `who` is the entry's name in the messages
+static int launch_pose_track(const char* who, bool optimal, const void* record, int B, int max_boxes, int streams,
+                             int max_tracks, int similarity, float match_threshold, float new_track_score, int max_misses,
+                             const void* prev, void* next, void* out, mpn_stream_t stream) {
+    MPN_REQUIRE(record && prev && next && out, MPN_ERR_BAD_ARG, "%s: null pointer", who);
     MPN_REQUIRE(streams >= 1 && B >= 1 && B % streams == 0, MPN_ERR_BAD_SHAPE,
-                "pose_track: B = %d images are not streams = %d times a whole number of frames", B, streams);
+                "%s: B = %d images are not streams = %d times a whole number of frames", who, B, streams);
     MPN_REQUIRE(max_tracks >= 1 && max_tracks <= kMaxTracks, MPN_ERR_BAD_SHAPE,
-                "pose_track: max_tracks = %d, one lane of a wave per slot takes 1..%d", max_tracks, kMaxTracks);
+                "%s: max_tracks = %d, one lane of a wave per slot takes 1..%d", who, max_tracks, kMaxTracks);
     MPN_REQUIRE(max_boxes >= 1 && max_boxes <= kMaxBoxes && (long long)B * max_boxes <= kMaxRows, MPN_ERR_BAD_SHAPE,
-                "pose_track: B = %d, max_boxes = %d (at most %d per image, %d rows)", B, max_boxes, kMaxBoxes, kMaxRows);
-    MPN_REQUIRE(similarity == 0 || similarity == 1, MPN_ERR_BAD_SHAPE, "pose_track: similarity must be 0 (IoU) or 1 (OKS)");
-    MPN_REQUIRE(max_misses >= 0, MPN_ERR_BAD_SHAPE, "pose_track: max_misses = %d is negative", max_misses);
+                "%s: B = %d, max_boxes = %d (at most %d per image, %d rows)", who, B, max_boxes, kMaxBoxes, kMaxRows);
+    MPN_REQUIRE(similarity == 0 || similarity == 1, MPN_ERR_BAD_SHAPE, "%s: similarity must be 0 (IoU) or 1 (OKS)", who);
+    MPN_REQUIRE(max_misses >= 0, MPN_ERR_BAD_SHAPE, "%s: max_misses = %d is negative", who, max_misses);
     MPN_REQUIRE(mpn_aligned16(record) && (((uintptr_t)prev | (uintptr_t)next | (uintptr_t)out) & 7u) == 0, MPN_ERR_BAD_ALIGN,
-                "pose_track: record must be 16-byte, prev / next / out 8-byte aligned");
+                "%s: record must be 16-byte, prev / next / out 8-byte aligned", who);
     MPN_REQUIRE(prev != next, MPN_ERR_BAD_ARG,
-                "pose_track: prev and next are one buffer; the launch is a pure function of (record, prev)");
+                "%s: prev and next are one buffer; the launch is a pure function of (record, prev)", who);
     TrackArgs a = {(const int*)record, (const float*)((const char*)record + header_words(B) * 4), (const int*)prev, (int*)next,
                    (unsigned char*)out, B, max_boxes, streams, max_tracks, similarity, max_misses, match_threshold,
                    new_track_score};
-    pose_track_kernel<<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+    if (optimal) pose_track_kernel<true><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+    else pose_track_kernel<false><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
     MPN_LAUNCH_CHECK();
     return MPN_OK;
+}
+
+extern "C" int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                              float match_threshold, float new_track_score, int max_misses, const void* prev, void* next,
+                              void* out, mpn_stream_t stream) {
+    return launch_pose_track("pose_track", false, record, B, max_boxes, streams, max_tracks, similarity, match_threshold,
+                             new_track_score, max_misses, prev, next, out, stream);
+}
+
+extern "C" int mpn_pose_track_optimal(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                                      float match_threshold, float new_track_score, int max_misses, const void* prev,
+                                      void* next, void* out, mpn_stream_t stream) {
+    return launch_pose_track("pose_track_optimal", true, record, B, max_boxes, streams, max_tracks, similarity, match_threshold,
+                             new_track_score, max_misses, prev, next, out, stream);
 }

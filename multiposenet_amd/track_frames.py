@@ -2,7 +2,7 @@
 
     python -m multiposenet_amd.track_frames --images DIR --out tracks.jsonl
         [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32] [--size W H] [--batch 16]
-        [--similarity oks|iou] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
+        [--similarity oks|iou] [--assignment greedy|optimal] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
         [--score-threshold 0.05] [--smooth [--fps 30] [--min-cutoff 1.0] [--beta 0.007] [--d-cutoff 1.0]
         [--min-keypoint-score 0.0]]
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
@@ -56,6 +56,8 @@ def main(argv=None):
     ap.add_argument("--size", type=int, nargs=2, default=(640, 640), metavar=("W", "H"))
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--similarity", choices=("oks", "iou"), default="oks")
+    ap.add_argument("--assignment", choices=("greedy", "optimal"), default="greedy",
+                    help="how a frame's persons are matched to the tracks: the largest similarity first, or the optimal assignment")
     ap.add_argument("--match-threshold", type=float, default=0.3)
     ap.add_argument("--max-misses", type=int, default=10)
     ap.add_argument("--new-track-score", type=float, default=0.3)
@@ -109,7 +111,7 @@ def main(argv=None):
                    prn_path=args.prn if args.prn is not None else initial_values(seed=0))
     tracker = PoseTracker(streams=1, max_tracks=args.max_tracks, similarity=args.similarity, match_threshold=args.match_threshold,
                           max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'],
-                          smooth=smooth)
+                          smooth=smooth, assignment=args.assignment)
     size = (args.size[1], args.size[0])
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -138,7 +140,7 @@ def main(argv=None):
             frames += len(batch)
     state = tracker.tracks(0)
     summary = {"frames": frames, "persons": persons, "ids_given": state["next_id"] - 1, "live_tracks": len(state["ids"]),
-               "dropped": state["dropped"], "similarity": args.similarity, "out": args.out}
+               "dropped": state["dropped"], "similarity": args.similarity, "assignment": args.assignment, "out": args.out}
     if smooth is not None:
         summary["smooth"] = {"fps": smooth.rate, "min_cutoff": smooth.min_cutoff, "beta": smooth.beta, "d_cutoff": smooth.d_cutoff,
                              "min_keypoint_score": smooth.min_keypoint_score}

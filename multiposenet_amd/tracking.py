@@ -1,5 +1,6 @@
 """Person identities across the frames of a video, on the device: `mpn_pose_track` (include/mpn.h) matches the persons of every
-frame greedily, by box IoU or keypoint OKS, against the tracks the earlier frames left.
+frame greedily, by box IoU or keypoint OKS, against the tracks the earlier frames left; `mpn_pose_track_optimal`
+(`PoseTracker(assignment='optimal')`) solves the frame's linear assignment instead.
 
     tracker = PoseTracker(streams=1, similarity='oks')           # one camera; a batch is consecutive frames
     for frames in batches:
@@ -28,6 +29,7 @@ from . import _lib
 from .pose_metrics import fill_record
 
 SIMILARITIES = {'iou': 0, 'oks': 1}
+ASSIGNMENTS = {'greedy': 'mpn_pose_track', 'optimal': 'mpn_pose_track_optimal'}      # the entry `launch` calls
 MAX_TRACKS = 64                          # slots per stream the kernel takes (one lane of a wave per slot)
 MAX_BOXES = 64                           # detections per image
 NUM_KEYPOINTS = 17
@@ -105,12 +107,19 @@ class PoseTracker:
     free slot, or is counted in `dropped` when there is none. Ids count from 1 per stream and are never reused.
     max_boxes: the detection slots per image of the records this tracker reads (the Detector's params['max_boxes']).
     smooth: None, or a OneEuro: every tracked person's keypoints are filtered on the device as well (`mpn_pose_smooth`), which
-    adds 'keypoints_smoothed' and 'keypoint_velocities' to what `unpack` / `update` / the Detector return."""
+    adds 'keypoints_smoothed' and 'keypoint_velocities' to what `unpack` / `update` / the Detector return.
+    assignment: 'greedy' (the largest similarity first, as above) or 'optimal': the frame's pairs at similarity >=
+    match_threshold are matched so that the sum of their similarities, quantised to steps of 2^-20, is the largest any matching
+    reaches (the Hungarian method on the device, `mpn_pose_track_optimal`): persons side by side or crossing keep their ids
+    where taking the largest pair first would hand them on. Everything else - the state, the rows, the keys - is the same."""
 
     def __init__(self, streams=1, max_tracks=32, similarity='oks', match_threshold=0.3, max_misses=10, new_track_score=0.3,
-                 max_boxes=25, device=None, smooth=None):
+                 max_boxes=25, device=None, smooth=None, assignment='greedy'):
         if similarity not in SIMILARITIES:
             raise ValueError(f"similarity must be one of {sorted(SIMILARITIES)} (got {similarity!r})")
+        if assignment not in ASSIGNMENTS:
+            raise ValueError(f"assignment must be one of {sorted(ASSIGNMENTS)} (got {assignment!r})")
+        self.assignment = assignment
         if smooth is not None and not isinstance(smooth, OneEuro):
             raise ValueError(f"smooth must be None or a tracking.OneEuro (got {smooth!r})")
         self.smooth = smooth
@@ -172,7 +181,7 @@ class PoseTracker:
         """record: the uint8 device tensor mpn_pose_gather wrote for (b, max_boxes); out: uint8 device tensor of
         `track_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`."""
         self.check_batch(b)
-        _lib.call("mpn_pose_track", _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
+        _lib.call(ASSIGNMENTS[self.assignment], _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
                   SIMILARITIES[self.similarity], self.match_threshold, self.new_track_score, self.max_misses,
                   _lib.ptr(self.prev), _lib.ptr(self.next), _lib.ptr(out), _lib.stream_ptr())
         return out

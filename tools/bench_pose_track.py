@@ -25,7 +25,16 @@ A run without a GPU fails.
 measures what `PoseTracker(smooth=OneEuro())` adds and writes it under the "smooth" key of --out, whose other keys stay (the
 file is read first): device time, ALTERNATING in one run, of the captured graph with a smoothing tracker against the same graph
 with a plain tracker, and of the mpn_pose_smooth launch plus its state's commit copy alone against the mpn_pose_track launch plus
-its commit copy alone. The comparison is the plain-tracker graph of the same run; no ratio is fixed in advance."""
+its commit copy alone. The comparison is the plain-tracker graph of the same run; no ratio is fixed in advance.
+
+    timeout -k 10 300 python tools/bench_pose_track.py --assignment optimal [the same options]
+
+measures what `PoseTracker(assignment='optimal')` costs against the greedy tracker and writes it under the "optimal" key of
+--out in the same way: device time, ALTERNATING in one run, of the captured graph and of the track launch plus commit alone,
+for one stream and for one stream per image, each with a greedy and an optimal tracker on the same record; and of the launch
+alone on two records made for it (tests/track_assign_cases.py: the chain of 64 boxes stepping half a box to and fro, and 64
+random overlapping boxes, 64 slots, --batch frames of one stream, IoU) - the longest searches the reference counts. The
+comparison is the greedy launch of the same run; no ratio is fixed in advance."""
 import argparse
 import json
 import os
@@ -133,6 +142,75 @@ def smooth_leg(args, det, frames):
     print(json.dumps({"smooth": result}))
 
 
+def optimal_leg(args, det, frames):
+    from multiposenet_amd.inference import PoseTracker
+    from multiposenet_amd.pose_metrics import fill_record
+    import track_assign_cases as acases
+    import track_assign_ref as opt
+    b, s, thr = args.batch, args.size, args.threshold
+    device = torch.device("cuda", 0)
+    timed, tracked = {}, {}
+    for streams in (1, b):
+        kw = dict(streams=streams, similarity=args.similarity, max_boxes=det.params['max_boxes'])
+        trackers = {"greedy": PoseTracker(**kw), "optimal": PoseTracker(assignment='optimal', **kw)}
+        tag = "one_stream" if streams == 1 else "one_stream_per_image"
+        for name, t in trackers.items():                               # warm-up: graphs captured, states filled
+            for _ in range(3):
+                outs = det.predict_images(frames, size=(s, s), score_threshold=thr, track=t)
+            tracked[f"{name}_{tag}"] = sum(int((o['track_ids'] > 0).sum()) for o in outs) / b
+            ent = next(e for e in det._graphs.values() if getattr(e, 'track', None) is t)
+            whole = ent.outs['record']
+            nbytes = whole.numel() - t.out_bytes(b)
+
+            def track_and_commit(t=t, record=whole[:nbytes], rows=whole[nbytes:]):
+                t.launch(record, rows, b)
+                t.commit()
+            timed[f"graph_{name}_{tag}"] = ent.graph.replay
+            timed[f"track_launch_and_commit_{name}_{tag}"] = track_and_commit
+    # the launch alone on the records made for it: a state with 64 live tracks, then --batch frames in one launch, not committed
+    # (the launch is pure: every repeat does the same work)
+    chain = acases.chain(64)
+    made = {"chain64": [chain[0]] + [chain[1 - f % 2] for f in range(b)], "random64": acases.random64(frames=b + 1)}
+    searches = {}
+    for case, seq in made.items():
+        p = acases.iou_params(64, 0.3)
+        state, log = opt.new_state(1, 64), []
+        opt.run(seq, state, p, log)
+        steps = [e[3] for e in log if e[0] == 'path']
+        searches[case] = {"scan_trips_per_batch": sum(steps), "longest_search": max(steps), "longest_path": opt.longest_path(log)}
+        record = torch.from_numpy(fill_record(seq[1:], b, 64)[0]).to(device)
+        for name in ("greedy", "optimal"):
+            t = PoseTracker(1, 64, 'iou', 0.3, acases.MAX_MISSES, acases.NEW_TRACK_SCORE, 64, assignment=name)
+            t.update(seq[:1])
+            rows = torch.zeros(t.out_bytes(b), dtype=torch.uint8, device=device)
+            timed[f"launch_{name}_{case}"] = lambda t=t, record=record, rows=rows: t.launch(record, rows, b)
+    for fn in timed.values():
+        fn()
+    ms = {name: [] for name in timed}
+    for _ in range(args.rounds):
+        for name, fn in timed.items():
+            ms[name].append(events_ms(fn, 20))
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    ratios = {name.replace("_optimal", ""): med[name] / med[name.replace("_optimal", "_greedy")] for name in med if "_optimal" in name}
+    result = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "batch": b, "source": list(args.source), "size": [s, s],
+              "score_threshold": thr, "similarity": args.similarity, "max_tracks": 32, "rounds": args.rounds,
+              "tracked_per_image": tracked, "made_records": {"similarity": "iou", "max_tracks": 64, "max_boxes": 64, **searches},
+              "device_ms_per_batch": {name: spread(v) for name, v in ms.items()}, "optimal_over_greedy": ratios,
+              "graph_added_ms_one_stream": med["graph_optimal_one_stream"] - med["graph_greedy_one_stream"]}
+    merged = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            merged = json.load(f)
+    merged["optimal"] = result
+    out_dir = os.path.dirname(args.out)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"optimal": result}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -146,6 +224,8 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--out", default=os.path.join("profiles", "pose_track.json"))
     ap.add_argument("--smooth", action="store_true", help="only the smoothing leg; merged into --out under 'smooth'")
+    ap.add_argument("--assignment", default="greedy", choices=["greedy", "optimal"],
+                    help="optimal: only the optimal-assignment leg; merged into --out under 'optimal'")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_pose_track: no GPU (a measurement path does not fall back)")
@@ -159,6 +239,8 @@ def main():
     max_boxes = det.params['max_boxes']
     if args.smooth:
         return smooth_leg(args, det, frames)
+    if args.assignment == "optimal":
+        return optimal_leg(args, det, frames)
     tracker = PoseTracker(streams=args.streams, similarity=args.similarity, max_boxes=max_boxes)
     p = ref.Params(tracker.max_tracks, args.similarity, tracker.match_threshold, tracker.max_misses, tracker.new_track_score)
     host_state = ref.new_state(args.streams, tracker.max_tracks)
@@ -229,9 +311,9 @@ def main():
     result["track_rate_over_plain"] = rate["predict_images_track"] / rate["predict_images"]
     result["track_rate_over_host_tracker"] = rate["predict_images_track"] / rate["predict_images_host_tracker"]
     result["track_share_of_graph_device_time"] = statistics.median(track_ms) / statistics.median(graph_ms)
-    if os.path.exists(args.out):                                       # the --smooth run's record stays
+    if os.path.exists(args.out):                                       # the --smooth and --assignment optimal runs' records stay
         with open(args.out) as f:
-            result.update({k: v for k, v in json.load(f).items() if k == "smooth"})
+            result.update({k: v for k, v in json.load(f).items() if k in ("smooth", "optimal")})
     out_dir = os.path.dirname(args.out)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
