@@ -923,9 +923,66 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
  *                     the unquantised f64 s of its pair. The arithmetic is in 64-bit integers. The loops over rows, over
  *                     the repeat of a row and over its path are bounded (64, 129, 129 trips): should a bound be hit, the
  *                     frame's remaining detections stay unmatched.
+ *
+ *   mpn_pose_track_motion   either entry with a constant-velocity prediction in the track's role: a frame's detections are
+ *                     compared with where each track is expected in that frame, not with the pose it was last seen with, and
+ *                     the tracks that are live but not detected in a frame ("coasting") are reported at their predicted pose.
+ *                     record, B, max_boxes, streams, max_tracks, similarity, match_threshold, new_track_score, max_misses,
+ *                     prev, next, out: as for mpn_pose_track; the track state and the output rows keep their layout and
+ *                     meaning. assignment: 0 = step 1 of mpn_pose_track (greedy), 1 = that of mpn_pose_track_optimal.
+ *                     Every float operation below is one IEEE f32 operation in the order written, without contraction;
+ *                     the division is correctly rounded.
+ *                   Motion state, motion_prev and motion_next, mpn_pose_track_motion_state_bytes(streams, max_tracks) bytes
+ *                     DEVICE, per stream in 32-bit words: four zero words; then max_tracks slots of 8 words: int32 id (the
+ *                     track the velocities belong to, 0 = none), int32 seen (the matches the velocities have taken in),
+ *                     f32 vel[6]: vel[0..3] the velocity per frame of the record box (ymin, xmin, ymax, xmax), vel[4..5] that
+ *                     of the keypoint centroid (x, y) - two sets because a record's boxes are normalised to the image and
+ *                     its keypoints are pixels. An all-zero state is the valid empty state. A slot of motion_prev whose id is
+ *                     not the id of the same slot of prev (the track state was reset or replaced on its own) reads as
+ *                     seen = 0, vel = 0. In motion_next a live slot holds its track's id, a free slot is all zero.
+ *                   PURE, as mpn_pose_track: prev and motion_prev are only read, the COMPLETE new states go to next and
+ *                     motion_next, two launches in a row write the same bytes. prev == next and motion_prev == motion_next
+ *                     are refused.
+ *                   The centroid of keypoints[17] is cx = (x_0 + x_1 + ... + x_16) / 17.0f, the sum taken in keypoint order
+ *                     from x_0 on; cy likewise.
+ *                   Per frame, in this order:
+ *                     0. every live slot, with m = its misses and gap = f32(m + 1) (the frames since it was last observed,
+ *                        this one included), is predicted: pbox[c] = box[c] + vel[c] * gap; pkp[k].x = kp[k].x + vel[4] * gap;
+ *                        pkp[k].y = kp[k].y + vel[5] * gap. The score is unchanged. The anchor is the last OBSERVED pose:
+ *                        the position is not filtered.
+ *                     Similarity: mpn_pose_track's arithmetic with pbox / pkp in the track's role (a); for OKS the extent
+ *                        area is that of pkp.
+ *                     1 - 4. as mpn_pose_track (assignment 0) or mpn_pose_track_optimal (assignment 1), word for word; a
+ *                        matched slot still takes the detection's own box, score and keypoints.
+ *                     Velocities. A matched slot, with `last` the slot's pose before step 2 and z the detection, the six
+ *                        components c being box[0..3] and the centroid (x, y) of the keypoints: vobs = (z[c] - last[c]) / gap;
+ *                        g = (seen == 0 && velocity_gain > 0) ? 1.0f : velocity_gain; vel[c] = vel[c] + g * (vobs - vel[c]);
+ *                        then seen += 1 (a track's second observation sets its velocity, later ones blend). An unmatched
+ *                        live slot: vel[c] = vel[c] * damping. A freed slot: all zero. A born slot: its id, seen = 0, vel = 0.
+ *                   coast_out: mpn_pose_track_coast_bytes(B, max_tracks) bytes DEVICE, max_tracks rows of 160 bytes per
+ *                     image: the slots that are live after step 3 and were not matched in the frame (a slot born in the
+ *                     frame is not among them), in slot order, packed at the front of the image's rows, the other rows
+ *                     zero: int32 id, int32 misses (after step 3), f32 pbox[4], f32 pkp[17][2] - the prediction of this
+ *                     frame's step 0.
+ *                   With velocity_gain = 0 every velocity stays 0 (finite poses) and the prediction is the stored pose: the
+ *                     output rows and the track state are byte for byte those of mpn_pose_track / mpn_pose_track_optimal.
+ *                   Checked before any HIP call, the messages begin "pose_track_motion:": mpn_pose_track's checks in its
+ *                     order, with motion_prev / motion_next / coast_out among the null pointers (MPN_ERR_BAD_ARG);
+ *                     assignment in {0, 1} behind similarity (MPN_ERR_BAD_SHAPE); velocity_gain and damping finite and in
+ *                     0..1 behind max_misses (MPN_ERR_BAD_ARG); motion_prev / motion_next / coast_out 8-byte aligned behind
+ *                     the other alignments (MPN_ERR_BAD_ALIGN); motion_prev == motion_next behind prev == next
+ *                     (MPN_ERR_BAD_ARG). The grid depends on streams alone.
+ *   mpn_pose_track_motion_state_bytes   streams * (16 + 32 * max_tracks); 0 for arguments out of range.
+ *   mpn_pose_track_coast_bytes          B * max_tracks * 160; 0 for arguments out of range (B outside 1..4096).
  */
 size_t mpn_pose_track_state_bytes(int streams, int max_tracks);
 size_t mpn_pose_track_out_bytes(int B, int max_boxes);
+size_t mpn_pose_track_motion_state_bytes(int streams, int max_tracks);
+size_t mpn_pose_track_coast_bytes(int B, int max_tracks);
+int mpn_pose_track_motion(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity, int assignment,
+                          float match_threshold, float new_track_score, int max_misses, float velocity_gain, float damping,
+                          const void* prev, void* next, const void* motion_prev, void* motion_next, void* out, void* coast_out,
+                          mpn_stream_t stream);
 int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
                    float match_threshold, float new_track_score, int max_misses, const void* prev, void* next, void* out,
                    mpn_stream_t stream);

@@ -152,6 +152,9 @@ SIGNATURES = {
     "mpn_pose_track_out_bytes": (_Z, [_I, _I]),
     "mpn_pose_track": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
     "mpn_pose_track_optimal": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),
+    "mpn_pose_track_motion_state_bytes": (_Z, [_I, _I]),
+    "mpn_pose_track_coast_bytes": (_Z, [_I, _I]),
+    "mpn_pose_track_motion": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "mpn_pose_smooth_state_bytes": (_Z, [_I, _I]),
     "mpn_pose_smooth_out_bytes": (_Z, [_I, _I]),
     "mpn_pose_smooth": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P]),

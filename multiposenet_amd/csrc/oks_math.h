@@ -24,11 +24,13 @@ __device__ __forceinline__ double oks_term(double dx, double dy, int k, double d
 }
 
 // (max x - min x) * (max y - min y) of keypoints[17][3] = (x, y, score): min / max in f32, the differences and the product in f64
+// (kStride = 2: of keypoints[17][2] = (x, y))
+template <int kStride = 3>
 __device__ __forceinline__ double keypoint_extent_area(const float* kp) {
     float xl = kp[0], xh = kp[0], yl = kp[1], yh = kp[1];
     for (int k = 1; k < kOksKeypoints; ++k) {
-        xl = fminf(xl, kp[3 * k]); xh = fmaxf(xh, kp[3 * k]);
-        yl = fminf(yl, kp[3 * k + 1]); yh = fmaxf(yh, kp[3 * k + 1]);
+        xl = fminf(xl, kp[kStride * k]); xh = fmaxf(xh, kp[kStride * k]);
+        yl = fminf(yl, kp[kStride * k + 1]); yh = fmaxf(yh, kp[kStride * k + 1]);
     }
     return ((double)xh - (double)xl) * ((double)yh - (double)yl);
 }

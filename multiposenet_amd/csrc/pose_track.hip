@@ -4,18 +4,24 @@
 //                    {track_id, slot, hits, flags, similarity}. PURE: prev is never written; the caller advances the state by
 //                    copying next over prev (include/mpn.h says why: a captured launch runs twice on an entry's first call).
 //   mpn_pose_track_optimal   the same entry with phase C the optimal (Hungarian) assignment under integer weights; every
-//                    other phase is the same code (pose_track_kernel<kOptimal>).
+//                    other phase is the same code (pose_track_kernel<kOptimal, false>).
+//   mpn_pose_track_motion    either assignment with a constant-velocity prediction in the track's role (pose_track_kernel<.,
+//                    true>): a velocity state of its own (prev / next, pure in the same way) and one 160-byte row per
+//                    coasting track (live, not detected in the frame) at its predicted pose.
 // ONE block per stream (B = streams * F images, stream s owns images s*F .. s*F+F-1 in time order); the block walks its F frames
 // in order with the working state in LDS. Per frame:
-//   phase A  the extent area of every live track's keypoints (OKS), the per-detection tables cleared
+//   phase A  (motion: step 0, the predicted box and keypoints of every live slot -> LDS, which take the stored pose's place in
+//            phases A and B;) the extent area of every live track's keypoints (OKS), the per-detection tables cleared
 //   phase B  the similarity of every (live track, detection) pair -> LDS, transposed [detection][track]: 64 x 64 f64 = 32 KB
 //   phase C  greedy matching by wave 0, lane = track slot: every lane keeps the best open detection of its row (ties: the
 //            smaller detection), a 6-step xor butterfly takes the largest (ties: the smaller slot); a lane rescans its row
 //            only when the detection it held was taken. No barrier inside the rounds, at most min(tracks, detections) of them.
 //            (optimal: assign_optimal below, also wave 0 alone and without a barrier)
-//   phase D  hits / age / misses of the live tracks, tracks past max_misses freed
+//   phase D  hits / age / misses of the live tracks, tracks past max_misses freed (motion: the velocities of the matched slots
+//            updated from the detection and the pose it replaces, those of the others damped; the coasting slots ranked)
 //   phase E  births in row order into the lowest free slots: two ballots and popcounts, no serial walk
-//   phase F  the detections' box, score and keypoints copied into their slots, free slots zeroed, the output rows
+//   phase F  the detections' box, score and keypoints copied into their slots, free slots zeroed, the output rows (motion: and
+//            the frame's coasting rows)
 // Latency-bound glue like mpn_oks_match (microseconds behind a network pass of milliseconds): not tuned beyond that.
 #include "common.h"
 #include "oks_math.h"
@@ -38,9 +44,18 @@ static_assert(kSlotWords == 60 && kSlotWords % 4 == 0 && kOffScore == kOffBox + 
 // an output row: int32 track_id, slot, hits, flags, f64 similarity
 constexpr int kOutBytes = 24;
 constexpr int kFlagNew = 1, kFlagOverflow = 2;
+// motion: the state of one stream is four zero words, then max_tracks slots of {id, seen, vel[6]}: the velocity per frame of
+// box[4] and of the keypoint centroid (x, y)
+constexpr int kMotionHeaderWords = 4, kVelocities = 6, kMotionSlotWords = 2 + kVelocities;
+// a predicted pose, box[4] and keypoints[17][2]; a coasting row is {id, misses} and that pose
+constexpr int kPredWords = 4 + 2 * kOksKeypoints, kPredKeypoints = 4, kCoastWords = 2 + kPredWords;
+static_assert(kMotionSlotWords == 8 && kCoastWords == 40, "motion state slot and coasting row layout");
 
 inline size_t header_words(int B) { return ((size_t)(2 * B + 2) + 3) / 4 * 4; }
 __host__ __device__ inline size_t stream_words(int max_tracks) { return kStateHeaderWords + (size_t)max_tracks * kSlotWords; }
+__host__ __device__ inline size_t motion_stream_words(int max_tracks) {
+    return kMotionHeaderWords + (size_t)max_tracks * kMotionSlotWords;
+}
 
 struct TrackArgs {
     const int* header;
@@ -50,6 +65,11 @@ struct TrackArgs {
     unsigned char* out;
     int B, max_boxes, streams, max_tracks, similarity, max_misses;
     float match_threshold, new_track_score;
+    // mpn_pose_track_motion only
+    const int* motion_prev;
+    int* motion_next;
+    unsigned* coast;
+    float velocity_gain, damping;
 };
 
 // IoU of two record boxes (ymin, xmin, ymax, xmax) in f32; every min / max is a comparison (a NaN operand takes the other
@@ -67,15 +87,28 @@ __device__ __forceinline__ float iou_of(const float* a, const float* b) {
 }
 
 // computeOks with the track's stored keypoints in the ground-truth role, all 17 visible; area = their extent area
+// (kStride = 2: the track's predicted keypoints[17][2])
+template <int kStride = 3>
 __device__ __forceinline__ double oks_track(const float* track_kp, double area, const float* det_kp) {
     const double denom = area + kEps;
     double sum = 0.0;
     for (int k = 0; k < kOksKeypoints; ++k) {
-        const double dx = (double)det_kp[3 * k] - (double)track_kp[3 * k];
-        const double dy = (double)det_kp[3 * k + 1] - (double)track_kp[3 * k + 1];
+        const double dx = (double)det_kp[3 * k] - (double)track_kp[kStride * k];
+        const double dy = (double)det_kp[3 * k + 1] - (double)track_kp[kStride * k + 1];
         sum += oks_term(dx, dy, k, denom);
     }
     return sum / (double)kOksKeypoints;
+}
+
+// the centroid of keypoints[17][3]: the sums in keypoint order from the first keypoint on, then / 17, in f32
+__device__ __forceinline__ void centroid_of(const float* kp, float& cx, float& cy) {
+    float sx = kp[0], sy = kp[1];
+    for (int k = 1; k < kOksKeypoints; ++k) {
+        sx = sx + kp[3 * k];
+        sy = sy + kp[3 * k + 1];
+    }
+    cx = sx / 17.0f;
+    cy = sy / 17.0f;
 }
 
 // Phase C of mpn_pose_track: the greedy rounds. Wave 0, lane = track slot t; `mine` is the detection the slot takes, -1 = none.
@@ -193,7 +226,7 @@ __device__ __forceinline__ void assign_optimal(const double (*sim)[kMaxTracks], 
     if (live && pA >= 1 && pA <= n) { mine = pA - 1; mine_sim = sim[mine][lane]; }
 }
 
-template <bool kOptimal>
+template <bool kOptimal, bool kMotion>
 __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
     __shared__ double sim[kMaxBoxes][kMaxTracks];         // [detection][slot]: lane = slot reads consecutive doubles
     __shared__ float data[kMaxTracks][kSlotData];         // box[4], score, keypoints[17][3] of every slot
@@ -204,6 +237,12 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
     __shared__ int dflags[kMaxBoxes];
     __shared__ int free_slot[kMaxTracks];                 // the r-th free slot
     __shared__ int counters[2];                           // next_id, dropped
+    // motion (no instantiation without it names these: they take no LDS there)
+    __shared__ float vel[kMotion ? kMaxTracks : 1][kVelocities];
+    __shared__ int seen[kMotion ? kMaxTracks : 1];
+    __shared__ float pred[kMotion ? kMaxTracks : 1][kPredWords];     // step 0: box[4], keypoints[17][2] of every live slot
+    __shared__ int coast_row[kMotion ? kMaxTracks : 1];   // the frame's coasting row of a slot, -1 = none
+    __shared__ int num_coast;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = a.max_tracks, F = a.B / a.streams;
     const int all_rows = a.B * a.max_boxes;
@@ -217,6 +256,12 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
     if (tid < T) {
         const int* p = pst + kStateHeaderWords + tid * kSlotWords;
         id[tid] = p[0]; hits[tid] = p[1]; age[tid] = p[2]; misses[tid] = p[3];
+        if constexpr (kMotion) {                          // a slot whose velocities belong to another track, or to none, starts anew
+            const int* m = a.motion_prev + (size_t)s * motion_stream_words(T) + kMotionHeaderWords + tid * kMotionSlotWords;
+            const bool own = p[0] != 0 && m[0] == p[0];
+            seen[tid] = own ? m[1] : 0;
+            for (int c = 0; c < kVelocities; ++c) vel[tid][c] = own ? __int_as_float(m[2 + c]) : 0.f;
+        }
     }
     if (tid == 0) {
         counters[0] = pst[0] < 1 ? 1 : pst[0];            // an all-zero state is the empty state: next_id reads as 1
@@ -249,7 +294,21 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
         const float* rows = a.rows + (size_t)first * kRowWords;
 
         // phase A
-        if (tid < T && a.similarity == 1 && id[tid] != 0) tarea[tid] = keypoint_extent_area(&data[tid][kDataKeypoints]);
+        if constexpr (kMotion) {
+            for (int i = tid; i < T * kPredWords; i += kThreads) {
+                const int t = i / kPredWords, w = i - t * kPredWords;
+                if (id[t] == 0) continue;
+                const float gap = (float)(misses[t] + 1);
+                const int xy = (w - kPredKeypoints) & 1;
+                const int c = w < kPredKeypoints ? w : 4 + xy;
+                const int from = w < kPredKeypoints ? w : kDataKeypoints + 3 * ((w - kPredKeypoints) >> 1) + xy;
+                pred[t][w] = data[t][from] + vel[t][c] * gap;
+            }
+            __syncthreads();
+            if (tid < T && a.similarity == 1 && id[tid] != 0) tarea[tid] = keypoint_extent_area<2>(&pred[tid][kPredKeypoints]);
+        } else {
+            if (tid < T && a.similarity == 1 && id[tid] != 0) tarea[tid] = keypoint_extent_area(&data[tid][kDataKeypoints]);
+        }
         if (tid < kMaxBoxes) { dslot[tid] = -1; dflags[tid] = 0; dsim[tid] = 0.0; }
         __syncthreads();
 
@@ -259,8 +318,12 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
             double v = 0.0;
             if (id[t] != 0) {
                 const float* row = rows + (size_t)d * kRowWords;
-                v = a.similarity == 0 ? (double)iou_of(&data[t][0], row + kOffBox)
-                                      : oks_track(&data[t][kDataKeypoints], tarea[t], row + kOffKeypoints);
+                if constexpr (kMotion)
+                    v = a.similarity == 0 ? (double)iou_of(&pred[t][0], row + kOffBox)
+                                          : oks_track<2>(&pred[t][kPredKeypoints], tarea[t], row + kOffKeypoints);
+                else
+                    v = a.similarity == 0 ? (double)iou_of(&data[t][0], row + kOffBox)
+                                          : oks_track(&data[t][kDataKeypoints], tarea[t], row + kOffKeypoints);
             }
             sim[d][t] = v;
         }
@@ -277,12 +340,37 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
             else assign_greedy(sim, n, t, live, thr, mine, mine_sim);
             if (live) {
                 if (mine >= 0) {
+                    if constexpr (kMotion) {              // the observed velocity: the detection against the pose it replaces
+                        const float gap = (float)(misses[t] + 1);
+                        const float* z = rows + (size_t)mine * kRowWords;
+                        float last[kVelocities], obs[kVelocities];
+                        for (int c = 0; c < 4; ++c) { last[c] = data[t][c]; obs[c] = z[kOffBox + c]; }
+                        centroid_of(&data[t][kDataKeypoints], last[4], last[5]);
+                        centroid_of(z + kOffKeypoints, obs[4], obs[5]);
+                        const float g = (seen[t] == 0 && a.velocity_gain > 0.f) ? 1.0f : a.velocity_gain;
+                        for (int c = 0; c < kVelocities; ++c) {
+                            const float vobs = (obs[c] - last[c]) / gap;
+                            vel[t][c] = vel[t][c] + g * (vobs - vel[t][c]);
+                        }
+                        seen[t] += 1;
+                    }
                     misses[t] = 0; hits[t] += 1; age[t] += 1;
                     dslot[mine] = t; dsim[mine] = mine_sim;
                 } else {
                     misses[t] += 1; age[t] += 1;
-                    if (misses[t] > a.max_misses) { id[t] = 0; hits[t] = 0; age[t] = 0; misses[t] = 0; }
+                    const bool freed = misses[t] > a.max_misses;
+                    if (freed) { id[t] = 0; hits[t] = 0; age[t] = 0; misses[t] = 0; }
+                    if constexpr (kMotion) {
+                        if (freed) seen[t] = 0;
+                        for (int c = 0; c < kVelocities; ++c) vel[t][c] = freed ? 0.f : vel[t][c] * a.damping;
+                    }
                 }
+            }
+            if constexpr (kMotion) {                      // the coasting slots, in slot order
+                const bool coasting = live && mine < 0 && id[t] != 0;
+                const unsigned long long coast_mask = __ballot(coasting);
+                if (t < T) coast_row[t] = coasting ? __popcll(coast_mask & ((1ull << lane) - 1ull)) : -1;
+                if (lane == 0) num_coast = __popcll(coast_mask);
             }
         }
         __syncthreads();
@@ -307,6 +395,10 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
                 if (r < num_free) {
                     const int t = free_slot[r];
                     id[t] = next_id + r; hits[t] = 1; age[t] = 1; misses[t] = 0;
+                    if constexpr (kMotion) {              // (a free slot's are zero already)
+                        seen[t] = 0;
+                        for (int c = 0; c < kVelocities; ++c) vel[t][c] = 0.f;
+                    }
                     dslot[lane] = t; dflags[lane] = kFlagNew;
                 } else {
                     dflags[lane] = kFlagOverflow;
@@ -338,6 +430,16 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
             ((int*)o)[3] = dflags[tid];
             *(double*)(o + 16) = dsim[tid];
         }
+        if constexpr (kMotion) {                          // the image's max_tracks coasting rows: step 0's pose, the rest zero
+            unsigned* rows_out = a.coast + (size_t)b * T * kCoastWords;
+            for (int i = tid; i < T * kCoastWords; i += kThreads) {
+                const int t = i / kCoastWords, w = i - t * kCoastWords;
+                const int r = coast_row[t];
+                if (r >= 0)
+                    rows_out[r * kCoastWords + w] = w == 0 ? (unsigned)id[t] : w == 1 ? (unsigned)misses[t] : __float_as_uint(pred[t][w - 2]);
+                if (t >= num_coast) rows_out[i] = 0u;
+            }
+        }
         __syncthreads();
     }
 
@@ -350,6 +452,15 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
         p[0] = id[tid]; p[1] = hits[tid]; p[2] = age[tid]; p[3] = misses[tid];
     }
     if (tid < kStateHeaderWords) nst[tid] = tid < 2 ? counters[tid] : 0;
+    if constexpr (kMotion) {
+        int* mst = a.motion_next + (size_t)s * motion_stream_words(T);
+        if (tid < T) {
+            int* m = mst + kMotionHeaderWords + tid * kMotionSlotWords;
+            m[0] = id[tid]; m[1] = seen[tid];
+            for (int c = 0; c < kVelocities; ++c) m[2 + c] = __float_as_int(vel[tid][c]);
+        }
+        if (tid < kMotionHeaderWords) mst[tid] = 0;
+    }
 }
 
 }  // namespace
@@ -364,11 +475,29 @@ extern "C" size_t mpn_pose_track_out_bytes(int B, int max_boxes) {
     return (size_t)B * max_boxes * kOutBytes;
 }
 
-// the checks and the launch of both entries; `who` is the entry's name in the messages
-static int launch_pose_track(const char* who, bool optimal, const void* record, int B, int max_boxes, int streams,
-                             int max_tracks, int similarity, float match_threshold, float new_track_score, int max_misses,
-                             const void* prev, void* next, void* out, mpn_stream_t stream) {
-    MPN_REQUIRE(record && prev && next && out, MPN_ERR_BAD_ARG, "%s: null pointer", who);
+extern "C" size_t mpn_pose_track_motion_state_bytes(int streams, int max_tracks) {
+    if (streams < 1 || streams > kMaxRows || max_tracks < 1 || max_tracks > kMaxTracks) return 0;
+    return (size_t)streams * motion_stream_words(max_tracks) * 4;
+}
+
+extern "C" size_t mpn_pose_track_coast_bytes(int B, int max_tracks) {
+    if (B < 1 || B > kMaxRows || max_tracks < 1 || max_tracks > kMaxTracks) return 0;
+    return (size_t)B * max_tracks * kCoastWords * 4;
+}
+
+// what mpn_pose_track_motion passes on top of its siblings' arguments
+struct MotionLaunch {
+    float velocity_gain, damping;
+    const void* prev;
+    void* next;
+    void* coast;
+};
+
+// the checks and the launch of all entries; `who` is the entry's name in the messages, `m` is null for the entries without motion
+static int launch_pose_track(const char* who, int assignment, const MotionLaunch* m, const void* record, int B, int max_boxes,
+                             int streams, int max_tracks, int similarity, float match_threshold, float new_track_score,
+                             int max_misses, const void* prev, void* next, void* out, mpn_stream_t stream) {
+    MPN_REQUIRE(record && prev && next && out && (!m || (m->prev && m->next && m->coast)), MPN_ERR_BAD_ARG, "%s: null pointer", who);
     MPN_REQUIRE(streams >= 1 && B >= 1 && B % streams == 0, MPN_ERR_BAD_SHAPE,
                 "%s: B = %d images are not streams = %d times a whole number of frames", who, B, streams);
     MPN_REQUIRE(max_tracks >= 1 && max_tracks <= kMaxTracks, MPN_ERR_BAD_SHAPE,
@@ -376,16 +505,34 @@ static int launch_pose_track(const char* who, bool optimal, const void* record, 
     MPN_REQUIRE(max_boxes >= 1 && max_boxes <= kMaxBoxes && (long long)B * max_boxes <= kMaxRows, MPN_ERR_BAD_SHAPE,
                 "%s: B = %d, max_boxes = %d (at most %d per image, %d rows)", who, B, max_boxes, kMaxBoxes, kMaxRows);
     MPN_REQUIRE(similarity == 0 || similarity == 1, MPN_ERR_BAD_SHAPE, "%s: similarity must be 0 (IoU) or 1 (OKS)", who);
+    MPN_REQUIRE(assignment == 0 || assignment == 1, MPN_ERR_BAD_SHAPE, "%s: assignment must be 0 (greedy) or 1 (optimal)", who);
     MPN_REQUIRE(max_misses >= 0, MPN_ERR_BAD_SHAPE, "%s: max_misses = %d is negative", who, max_misses);
+    if (m) {                                              // (a NaN fails both comparisons)
+        MPN_REQUIRE(m->velocity_gain >= 0.f && m->velocity_gain <= 1.f, MPN_ERR_BAD_ARG,
+                    "%s: velocity_gain = %g must be in 0..1", who, (double)m->velocity_gain);
+        MPN_REQUIRE(m->damping >= 0.f && m->damping <= 1.f, MPN_ERR_BAD_ARG, "%s: damping = %g must be in 0..1", who,
+                    (double)m->damping);
+    }
     MPN_REQUIRE(mpn_aligned16(record) && (((uintptr_t)prev | (uintptr_t)next | (uintptr_t)out) & 7u) == 0, MPN_ERR_BAD_ALIGN,
                 "%s: record must be 16-byte, prev / next / out 8-byte aligned", who);
+    MPN_REQUIRE(!m || (((uintptr_t)m->prev | (uintptr_t)m->next | (uintptr_t)m->coast) & 7u) == 0, MPN_ERR_BAD_ALIGN,
+                "%s: motion_prev / motion_next / coast_out must be 8-byte aligned", who);
     MPN_REQUIRE(prev != next, MPN_ERR_BAD_ARG,
                 "%s: prev and next are one buffer; the launch is a pure function of (record, prev)", who);
+    MPN_REQUIRE(!m || m->prev != m->next, MPN_ERR_BAD_ARG,
+                "%s: motion_prev and motion_next are one buffer; the launch is a pure function of (record, prev, motion_prev)", who);
     TrackArgs a = {(const int*)record, (const float*)((const char*)record + header_words(B) * 4), (const int*)prev, (int*)next,
                    (unsigned char*)out, B, max_boxes, streams, max_tracks, similarity, max_misses, match_threshold,
-                   new_track_score};
-    if (optimal) pose_track_kernel<true><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
-    else pose_track_kernel<false><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+                   new_track_score, nullptr, nullptr, nullptr, 0.f, 0.f};
+    if (m) {
+        a.motion_prev = (const int*)m->prev; a.motion_next = (int*)m->next; a.coast = (unsigned*)m->coast;
+        a.velocity_gain = m->velocity_gain; a.damping = m->damping;
+        if (assignment == 1) pose_track_kernel<true, true><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+        else pose_track_kernel<false, true><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+    } else {
+        if (assignment == 1) pose_track_kernel<true, false><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+        else pose_track_kernel<false, false><<<streams, kThreads, 0, (hipStream_t)stream>>>(a);
+    }
     MPN_LAUNCH_CHECK();
     return MPN_OK;
 }
@@ -393,13 +540,22 @@ static int launch_pose_track(const char* who, bool optimal, const void* record, 
 extern "C" int mpn_pose_track(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
                               float match_threshold, float new_track_score, int max_misses, const void* prev, void* next,
                               void* out, mpn_stream_t stream) {
-    return launch_pose_track("pose_track", false, record, B, max_boxes, streams, max_tracks, similarity, match_threshold,
+    return launch_pose_track("pose_track", 0, nullptr, record, B, max_boxes, streams, max_tracks, similarity, match_threshold,
                              new_track_score, max_misses, prev, next, out, stream);
 }
 
 extern "C" int mpn_pose_track_optimal(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
                                       float match_threshold, float new_track_score, int max_misses, const void* prev,
                                       void* next, void* out, mpn_stream_t stream) {
-    return launch_pose_track("pose_track_optimal", true, record, B, max_boxes, streams, max_tracks, similarity, match_threshold,
-                             new_track_score, max_misses, prev, next, out, stream);
+    return launch_pose_track("pose_track_optimal", 1, nullptr, record, B, max_boxes, streams, max_tracks, similarity,
+                             match_threshold, new_track_score, max_misses, prev, next, out, stream);
+}
+
+extern "C" int mpn_pose_track_motion(const void* record, int B, int max_boxes, int streams, int max_tracks, int similarity,
+                                     int assignment, float match_threshold, float new_track_score, int max_misses,
+                                     float velocity_gain, float damping, const void* prev, void* next, const void* motion_prev,
+                                     void* motion_next, void* out, void* coast_out, mpn_stream_t stream) {
+    const MotionLaunch m = {velocity_gain, damping, motion_prev, motion_next, coast_out};
+    return launch_pose_track("pose_track_motion", assignment, &m, record, B, max_boxes, streams, max_tracks, similarity,
+                             match_threshold, new_track_score, max_misses, prev, next, out, stream);
 }

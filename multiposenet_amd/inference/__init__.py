@@ -3,4 +3,4 @@ from .detector import Detector  # noqa: F401
 from .draw import TrackStyle  # noqa: F401
 from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401
 from .maps import MapPlotter, plot_maps  # noqa: F401
-from ..tracking import PoseTracker, OneEuro  # noqa: F401
+from ..tracking import PoseTracker, OneEuro, ConstantVelocity  # noqa: F401

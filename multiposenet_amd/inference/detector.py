@@ -388,7 +388,11 @@ class Detector:
                 with smooth=OneEuro(...) (needs the PRN) also adds 'keypoints_smoothed' f32 [n, 17, 3] - the One-Euro filtered
                 (x, y) of every tracked person's joints with the frame's score, in the coordinates of this call's 'keypoints' -
                 and 'keypoint_velocities' f32 [n, 17, 2] in pixels per second: one mpn_pose_smooth launch behind the track
-                launch in the same graph, its rows in the same copy. Without `track_style`, `annotate` still draws the frame's own
+                launch in the same graph, its rows in the same copy. A tracker made with motion=ConstantVelocity(...) matches
+                against the tracks' predicted poses (mpn_pose_track_motion in place of mpn_pose_track) and adds 'coasting_ids' int32
+                [m], 'coasting_misses' int32 [m], 'coasting_boxes' f32 [m, 4] and 'coasting_keypoints' f32 [m, 17, 2]: the tracks of
+                the image's stream that are alive but were not detected in it, at their predicted pose, in the coordinates of this
+                call's 'boxes' and 'keypoints'; the rows lie behind the others in the same copy. Without `track_style`, `annotate` still draws the frame's own
                 detections in red and white.
             track_style: None, or an inference.TrackStyle (needs annotate and track): 'annotated' / 'annotated_jpeg' then carry
                 the identities - mpn_draw_tracks in place of mpn_draw_detections, on the record, the track rows and (for

@@ -5,6 +5,7 @@
         [--similarity oks|iou] [--assignment greedy|optimal] [--match-threshold 0.3] [--max-misses 10] [--new-track-score 0.3] [--max-tracks 32]
         [--score-threshold 0.05] [--smooth [--fps 30] [--min-cutoff 1.0] [--beta 0.007] [--d-cutoff 1.0]
         [--min-keypoint-score 0.0]]
+        [--motion [--velocity-gain 0.5] [--damping 1.0]]
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
@@ -16,7 +17,11 @@ advance the tracks by frames the video does not have. --out gets one JSON line p
 track id (0 = untracked), the box (ymin, xmin, ymax, xmax, normalised to the frame) and the keypoints (x, y, score) in the
 frame's pixels. --smooth runs a One-Euro filter over every tracked joint on the device as well (`tracking.OneEuro`; --fps is
 the video's frame rate) and adds "keypoints_smoothed" (x, y, score) and "keypoint_velocities" (pixels per second) to every
-line; beta multiplies a speed in frame pixels and so depends on the resolution. --frames-out DIR also writes every frame as
+line; beta multiplies a speed in frame pixels and so depends on the resolution. --motion matches every frame's persons
+against where the tracks are expected (`tracking.ConstantVelocity`: a velocity per track, --velocity-gain the weight of a new
+observation of it, --damping its decay per frame without a detection) and adds "coasting_ids", "coasting_boxes" and
+"coasting_keypoints" (x, y) to every line: the tracks that are alive but were not detected in the frame, at their predicted
+pose. --frames-out DIR also writes every frame as
 DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in a colour per track (`inference.TrackStyle`;
 --draw-smoothed draws the smoothed keypoints, --hide-untracked leaves persons without an id out) - drawn and JPEG-encoded on
 the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
@@ -69,6 +74,10 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=0.007)
     ap.add_argument("--d-cutoff", type=float, default=1.0)
     ap.add_argument("--min-keypoint-score", type=float, default=0.0)
+    ap.add_argument("--motion", action="store_true",
+                    help="match against the tracks' constant-velocity prediction and report the coasting tracks")
+    ap.add_argument("--velocity-gain", type=float, default=0.5, help="weight of a newly observed velocity, 0..1 (--motion)")
+    ap.add_argument("--damping", type=float, default=1.0, help="factor on a track's velocity per frame without a detection, 0..1 (--motion)")
     ap.add_argument("--frames-out", metavar="DIR", help="write every frame as DIR/<name>.jpg with its tracked persons drawn on it")
     ap.add_argument("--jpeg-quality", type=int, default=75, help="of the written frames (--frames-out)")
     ap.add_argument("--label-size", type=int, default=10, help="font size of the id labels (--frames-out)")
@@ -77,6 +86,13 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
+    motion = None
+    if args.motion:
+        from .tracking import ConstantVelocity
+        try:
+            motion = ConstantVelocity(velocity_gain=args.velocity_gain, damping=args.damping)
+        except ValueError as e:
+            ap.error(str(e))
     names = sorted(f for f in os.listdir(args.images) if f.lower().endswith(EXTENSIONS))
     if not names:
         raise SystemExit(f"no image files {EXTENSIONS} under {args.images}")
@@ -111,7 +127,7 @@ def main(argv=None):
                    prn_path=args.prn if args.prn is not None else initial_values(seed=0))
     tracker = PoseTracker(streams=1, max_tracks=args.max_tracks, similarity=args.similarity, match_threshold=args.match_threshold,
                           max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'],
-                          smooth=smooth, assignment=args.assignment)
+                          smooth=smooth, motion=motion, assignment=args.assignment)
     size = (args.size[1], args.size[0])
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -132,6 +148,10 @@ def main(argv=None):
                 if smooth is not None:
                     line["keypoints_smoothed"] = o["keypoints_smoothed"].tolist()
                     line["keypoint_velocities"] = o["keypoint_velocities"].tolist()
+                if motion is not None:
+                    line["coasting_ids"] = o["coasting_ids"].tolist()
+                    line["coasting_boxes"] = o["coasting_boxes"].tolist()
+                    line["coasting_keypoints"] = o["coasting_keypoints"].tolist()
                 out.write(json.dumps(line) + "\n")
                 if draw:
                     with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
@@ -144,6 +164,8 @@ def main(argv=None):
     if smooth is not None:
         summary["smooth"] = {"fps": smooth.rate, "min_cutoff": smooth.min_cutoff, "beta": smooth.beta, "d_cutoff": smooth.d_cutoff,
                              "min_keypoint_score": smooth.min_keypoint_score}
+    if motion is not None:
+        summary["motion"] = {"velocity_gain": motion.velocity_gain, "damping": motion.damping}
     print(json.dumps(summary))
     return state
 

@@ -19,6 +19,13 @@ launch, outside the graph; the Detector does that once per call. `update()` is t
 and joint, keyed by the slot and the id the track launch gave the row, with a prev / next state of its own that `commit()`
 advances in the same way. The units are pixels of the call's 'keypoints': `beta` multiplies a speed in pixels per second and
 so depends on the resolution.
+
+    tracker = PoseTracker(streams=1, motion=ConstantVelocity())  # + 'coasting_ids' / _misses / _boxes / _keypoints
+
+`motion=` makes the launch `mpn_pose_track_motion`: every track carries a velocity per frame of its box and of its keypoint
+centroid, a frame's detections are compared with where the track is expected in that frame (the last observed pose plus the
+velocity times the frames since), and the tracks that are alive but were not detected in a frame come back at that expected
+pose. The velocities are a third prev / next state that `commit()` advances.
 """
 import itertools
 import math
@@ -41,6 +48,11 @@ _OUT = np.dtype([('track_id', np.int32), ('slot', np.int32), ('hits', np.int32),
 _HEAD = np.dtype([('next_id', np.int32), ('dropped', np.int32), ('pad', np.int32, (2,))])
 _SLOT = np.dtype([('id', np.int32), ('hits', np.int32), ('age', np.int32), ('misses', np.int32), ('box', np.float32, (4,)),
                   ('score', np.float32), ('keypoints', np.float32, (NUM_KEYPOINTS, 3))])
+
+# a coasting row of mpn_pose_track_motion and its motion state of one stream
+_COAST = np.dtype([('id', np.int32), ('misses', np.int32), ('box', np.float32, (4,)), ('keypoints', np.float32, (NUM_KEYPOINTS, 2))])
+_MOTION_HEAD = np.dtype([('pad', np.int32, (4,))])
+_MOTION_SLOT = np.dtype([('id', np.int32), ('seen', np.int32), ('vel', np.float32, (6,))])
 
 # a row of mpn_pose_smooth's output and its state of one stream
 _SMOOTH_OUT = np.dtype([('keypoints', np.float32, (NUM_KEYPOINTS, 3)), ('velocities', np.float32, (NUM_KEYPOINTS, 2))])
@@ -97,6 +109,49 @@ class OneEuro:
         return "OneEuro(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
 
 
+class ConstantVelocity:
+    """The parameters of the constant-velocity prediction `PoseTracker(motion=...)` matches against. Immutable.
+
+    velocity_gain: the weight in 0..1 of a newly observed velocity (the step from a track's last observed pose to the detection
+    it is matched with, per frame) against the velocity the track carried; a track's second observation sets its velocity
+    outright. 0 keeps every velocity 0: the tracker then matches as one without motion=. damping: the factor in 0..1 a
+    track's velocity is multiplied with in every frame it is not detected in; 1 lets it coast at full speed.
+    The defaults are NOT tuned: there are no trained weights and no video in this repository to tune them on."""
+    __slots__ = ('velocity_gain', 'damping')
+
+    def __init__(self, velocity_gain=0.5, damping=1.0):
+        values = dict(velocity_gain=velocity_gain, damping=damping)
+        for name, v in values.items():
+            try:
+                with np.errstate(over='ignore'):
+                    v = float(np.float32(v))                        # what the launch receives
+            except (TypeError, ValueError):
+                raise ValueError(f"ConstantVelocity: {name} must be a number (got {v!r})") from None
+            if not math.isfinite(v):
+                raise ValueError(f"ConstantVelocity: {name} must be finite (got {values[name]!r})")
+            if not 0 <= v <= 1:
+                raise ValueError(f"ConstantVelocity: {name} must be in 0..1 (got {values[name]!r})")
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("ConstantVelocity is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("ConstantVelocity is immutable")
+
+    def astuple(self):
+        return (self.velocity_gain, self.damping)
+
+    def __eq__(self, other):
+        return isinstance(other, ConstantVelocity) and self.astuple() == other.astuple()
+
+    def __hash__(self):
+        return hash(self.astuple())
+
+    def __repr__(self):
+        return "ConstantVelocity(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+
 class PoseTracker:
     """The tracks of `streams` independent cameras, `max_tracks` slots each, on the device.
 
@@ -108,13 +163,19 @@ class PoseTracker:
     max_boxes: the detection slots per image of the records this tracker reads (the Detector's params['max_boxes']).
     smooth: None, or a OneEuro: every tracked person's keypoints are filtered on the device as well (`mpn_pose_smooth`), which
     adds 'keypoints_smoothed' and 'keypoint_velocities' to what `unpack` / `update` / the Detector return.
+    motion: None, or a ConstantVelocity: the launch is `mpn_pose_track_motion` - a detection is compared with the pose its
+    track is predicted to have in the frame (box and keypoints moved by the track's velocity times the frames since it was
+    last detected), so that a person who was hidden for a few frames, or who moves by more than a box width per frame, keeps
+    the id. What a matched track stores is still the detection itself. Adds the coasting tracks of every image - alive, not
+    detected in it - at their predicted pose: 'coasting_ids' int32 [m], 'coasting_misses' int32 [m], 'coasting_boxes' f32 [m,4],
+    'coasting_keypoints' f32 [m,17,2]. With motion=None nothing changes.
     assignment: 'greedy' (the largest similarity first, as above) or 'optimal': the frame's pairs at similarity >=
     match_threshold are matched so that the sum of their similarities, quantised to steps of 2^-20, is the largest any matching
     reaches (the Hungarian method on the device, `mpn_pose_track_optimal`): persons side by side or crossing keep their ids
     where taking the largest pair first would hand them on. Everything else - the state, the rows, the keys - is the same."""
 
     def __init__(self, streams=1, max_tracks=32, similarity='oks', match_threshold=0.3, max_misses=10, new_track_score=0.3,
-                 max_boxes=25, device=None, smooth=None, assignment='greedy'):
+                 max_boxes=25, device=None, smooth=None, motion=None, assignment='greedy'):
         if similarity not in SIMILARITIES:
             raise ValueError(f"similarity must be one of {sorted(SIMILARITIES)} (got {similarity!r})")
         if assignment not in ASSIGNMENTS:
@@ -123,6 +184,9 @@ class PoseTracker:
         if smooth is not None and not isinstance(smooth, OneEuro):
             raise ValueError(f"smooth must be None or a tracking.OneEuro (got {smooth!r})")
         self.smooth = smooth
+        if motion is not None and not isinstance(motion, ConstantVelocity):
+            raise ValueError(f"motion must be None or a tracking.ConstantVelocity (got {motion!r})")
+        self.motion = motion
         self.streams, self.max_tracks, self.max_boxes = int(streams), int(max_tracks), int(max_boxes)
         self.similarity, self.max_misses = similarity, int(max_misses)
         self.match_threshold, self.new_track_score = float(match_threshold), float(new_track_score)
@@ -151,6 +215,13 @@ class PoseTracker:
                 raise _lib.MpnError("mpn_pose_smooth: the state's layout is not the one this binding was written against")
             self.smooth_prev = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
             self.smooth_next = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
+        if motion is not None:
+            self.motion_state_bytes = lib.mpn_pose_track_motion_state_bytes(self.streams, self.max_tracks)
+            self.motion_stream_bytes = _MOTION_HEAD.itemsize + self.max_tracks * _MOTION_SLOT.itemsize
+            if self.motion_state_bytes == 0 or self.motion_state_bytes != self.streams * self.motion_stream_bytes:
+                raise _lib.MpnError("mpn_pose_track_motion: the state's layout is not the one this binding was written against")
+            self.motion_prev = torch.zeros(self.motion_state_bytes, dtype=torch.uint8, device=self.device)
+            self.motion_next = torch.zeros(self.motion_state_bytes, dtype=torch.uint8, device=self.device)
         self._update = {}                                           # update(): device record and rows per batch size
 
     def check_batch(self, b):
@@ -167,20 +238,45 @@ class PoseTracker:
             raise ValueError(f"mpn_pose_track: {b} x {self.max_boxes} slots are more than one launch takes")
         return n
 
-    def out_bytes(self, b):
-        """The bytes of a call's rows for b images: the track rows and, with smooth=, the smoothed rows behind them."""
+    def coast_offset(self, b):
+        """Where the coasting rows of a motion= tracker begin within a call's rows: behind the track rows and any smoothed
+        rows, at the next multiple of 8 bytes."""
         n = self.track_bytes(b)
         if self.smooth is not None:
             m = _lib.lib().mpn_pose_smooth_out_bytes(b, self.max_boxes)
             if m == 0 or m != b * self.max_boxes * _SMOOTH_OUT.itemsize:
                 raise ValueError(f"mpn_pose_smooth: {b} x {self.max_boxes} slots are more than one launch takes")
             n += m
+        return (n + 7) // 8 * 8 if self.motion is not None else n
+
+    def out_bytes(self, b):
+        """The bytes of a call's rows for b images: the track rows, with smooth= the smoothed rows behind them, and with
+        motion= the coasting rows behind those."""
+        n = self.coast_offset(b)
+        if self.motion is not None:
+            m = _lib.lib().mpn_pose_track_coast_bytes(b, self.max_tracks)
+            if m == 0 or m != b * self.max_tracks * _COAST.itemsize:
+                raise ValueError(f"mpn_pose_track_motion: {b} x {self.max_tracks} coasting rows are more than one launch takes")
+            n += m
         return n
 
-    def launch(self, record, out, b):
+    def launch(self, record, out, b, coast=None):
         """record: the uint8 device tensor mpn_pose_gather wrote for (b, max_boxes); out: uint8 device tensor of
-        `track_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`."""
+        `track_bytes(b)`. Reads `prev`, writes `next` and out; the state does not advance before `commit()`. A motion= tracker
+        also reads `motion_prev` and writes `motion_next` and the coasting rows: to `coast`, or, without it, into `out` at
+        `coast_offset(b)` (out is then a call's whole `out_bytes(b)`)."""
         self.check_batch(b)
+        if self.motion is not None:
+            if coast is None:
+                coast = out[self.coast_offset(b):self.out_bytes(b)]
+            if coast.numel() < self.out_bytes(b) - self.coast_offset(b):
+                raise ValueError(f"launch: a motion= tracker writes {self.out_bytes(b) - self.coast_offset(b)} bytes of coasting "
+                                 f"rows for {b} images (got room for {coast.numel()})")
+            _lib.call("mpn_pose_track_motion", _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
+                      SIMILARITIES[self.similarity], int(self.assignment == 'optimal'), self.match_threshold, self.new_track_score,
+                      self.max_misses, self.motion.velocity_gain, self.motion.damping, _lib.ptr(self.prev), _lib.ptr(self.next),
+                      _lib.ptr(self.motion_prev), _lib.ptr(self.motion_next), _lib.ptr(out), _lib.ptr(coast), _lib.stream_ptr())
+            return out
         _lib.call(ASSIGNMENTS[self.assignment], _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
                   SIMILARITIES[self.similarity], self.match_threshold, self.new_track_score, self.max_misses,
                   _lib.ptr(self.prev), _lib.ptr(self.next), _lib.ptr(out), _lib.stream_ptr())
@@ -188,7 +284,7 @@ class PoseTracker:
 
     def launch_smooth(self, record, track_out, out, b):
         """record and track_out: what `launch` read and wrote (uint8 device tensors); out: uint8 device tensor of
-        `out_bytes(b) - track_bytes(b)`. Reads `smooth_prev`, writes `smooth_next` and out; `commit()` advances the state."""
+        `mpn_pose_smooth_out_bytes(b, max_boxes)`. Reads `smooth_prev`, writes `smooth_next` and out; `commit()` advances the state."""
         if self.smooth is None:
             raise ValueError("launch_smooth: this tracker was made without smooth=")
         self.check_batch(b)
@@ -199,16 +295,20 @@ class PoseTracker:
 
     def launch_all(self, record, out, b):
         """`launch` and, with smooth=, `launch_smooth` behind it: out is a uint8 device tensor of `out_bytes(b)`, the track rows
-        first."""
+        first (then the smoothed rows, then the coasting rows of motion=)."""
         n = self.track_bytes(b)
-        self.launch(record, out[:n], b)
+        at = self.coast_offset(b)
+        self.launch(record, out[:n], b, out[at:] if self.motion is not None else None)
         if self.smooth is not None:
-            self.launch_smooth(record, out[:n], out[n:], b)
+            self.launch_smooth(record, out[:n], out[n:at], b)
         return out
 
     def commit(self):
-        """The last launch's state becomes the current one: one small device copy on the current stream (two with smooth=)."""
+        """The last launch's state becomes the current one: one small device copy on the current stream (one more with smooth=,
+        one more with motion=)."""
         self.prev.copy_(self.next, non_blocking=True)
+        if self.motion is not None:
+            self.motion_prev.copy_(self.motion_next, non_blocking=True)
         if self.smooth is not None:
             self.smooth_prev.copy_(self.smooth_next, non_blocking=True)
 
@@ -220,6 +320,9 @@ class PoseTracker:
             if self.smooth is not None:
                 self.smooth_prev.zero_()
                 self.smooth_next.zero_()
+            if self.motion is not None:
+                self.motion_prev.zero_()
+                self.motion_next.zero_()
             return
         if not 0 <= int(stream) < self.streams:
             raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
@@ -230,26 +333,41 @@ class PoseTracker:
             at = int(stream) * self.smooth_stream_bytes
             self.smooth_prev[at:at + self.smooth_stream_bytes].zero_()
             self.smooth_next[at:at + self.smooth_stream_bytes].zero_()
+        if self.motion is not None:
+            at = int(stream) * self.motion_stream_bytes
+            self.motion_prev[at:at + self.motion_stream_bytes].zero_()
+            self.motion_next[at:at + self.motion_stream_bytes].zero_()
 
     def unpack(self, out, counts):
         """A host copy of the output rows (uint8 array) and the record's per-image counts -> a list of dicts, one per image:
         'track_ids' int32 [n] (0 = untracked), 'track_hits' int32 [n], 'track_new' bool [n], 'track_similarity' f64 [n],
         in the image's record order. With smooth= the smoothed rows lie behind the track rows and add 'keypoints_smoothed' f32
         [n,17,3] (x, y, score; raw for an untracked person, a joint's first sample and a sample below min_keypoint_score) and
-        'keypoint_velocities' f32 [n,17,2] (pixels per second; 0 there)."""
+        'keypoint_velocities' f32 [n,17,2] (pixels per second; 0 there). With motion= the coasting rows lie behind those and add
+        'coasting_ids' int32 [m], 'coasting_misses' int32 [m] (frames in a row without a detection, this one included),
+        'coasting_boxes' f32 [m,4] and 'coasting_keypoints' f32 [m,17,2]: the image's tracks that are alive and were not detected
+        in it, in slot order, at the pose predicted for this frame."""
         slots = len(counts) * self.max_boxes
         rows = np.frombuffer(out, np.uint8, slots * _OUT.itemsize).view(_OUT)
         smooth = None
         if self.smooth is not None:
             smooth = np.frombuffer(out, np.uint8, slots * _SMOOTH_OUT.itemsize, slots * _OUT.itemsize).view(_SMOOTH_OUT)
+        coast = None
+        if self.motion is not None:
+            coast = np.frombuffer(out, np.uint8, len(counts) * self.max_tracks * _COAST.itemsize,
+                                  self.coast_offset(len(counts))).view(_COAST).reshape(len(counts), self.max_tracks)
         res, s = [], 0
-        for n in counts:
+        for i, n in enumerate(counts):
             r = rows[s:s + int(n)]
             res.append({'track_ids': r['track_id'].copy(), 'track_hits': r['hits'].copy(),
                         'track_new': (r['flags'] & FLAG_NEW) != 0, 'track_similarity': r['similarity'].copy()})
             if smooth is not None:
                 res[-1]['keypoints_smoothed'] = smooth['keypoints'][s:s + int(n)].copy()
                 res[-1]['keypoint_velocities'] = smooth['velocities'][s:s + int(n)].copy()
+            if coast is not None:
+                c = coast[i][coast[i]['id'] != 0]
+                res[-1].update({'coasting_ids': c['id'].copy(), 'coasting_misses': c['misses'].copy(),
+                                'coasting_boxes': c['box'].copy(), 'coasting_keypoints': c['keypoints'].copy()})
             s += int(n)
         return res
 
@@ -258,7 +376,10 @@ class PoseTracker:
         'age', 'misses' int32 [m], 'boxes' f32 [m,4], 'scores' f32 [m], 'keypoints' f32 [m,17,3]}. With smooth= also 'frames'
         (the frames the stream's filters have seen), 'keypoints_smoothed' f32 [m,17,2] (x_hat, y_hat of the live slots; of a
         slot whose track was not detected since the slot changed hands, the earlier track's) and 'keypoint_last' int32 [m,17]
-        (the frame number of each joint's last sample, 0 = none)."""
+        (the frame number of each joint's last sample, 0 = none). With motion= also 'velocities' f32 [m,6] (per frame: of the
+        box's ymin, xmin, ymax, xmax, normalised, and of the keypoint centroid's x, y in pixels), 'seen' int32 [m] (the matches
+        a track's velocity has taken in) and 'boxes_predicted' f32 [m,4], 'keypoints_predicted' f32 [m,17,2]: where the next
+        frame's detections are compared with, computed here from the copied state in the kernel's float32 steps."""
         if not 0 <= int(stream) < self.streams:
             raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
         at = int(stream) * self.stream_bytes
@@ -277,6 +398,17 @@ class PoseTracker:
             res['frames'] = int(raw[:_SMOOTH_HEAD.itemsize].view(_SMOOTH_HEAD)[0]['frames'])
             res['keypoints_smoothed'] = joints['hat'][..., :2].copy()
             res['keypoint_last'] = joints['last'].copy()
+        if self.motion is not None:
+            at = int(stream) * self.motion_stream_bytes
+            raw = self.motion_prev[at:at + self.motion_stream_bytes].cpu().numpy()
+            m = raw[_MOTION_HEAD.itemsize:].view(_MOTION_SLOT)[live]
+            own = (m['id'] == s['id'])[:, None]                     # (as the launch reads a slot another track left)
+            vel = np.where(own, m['vel'], np.float32(0)).astype(np.float32)
+            gap = (s['misses'] + 1).astype(np.float32)[:, None]
+            res['velocities'] = vel
+            res['seen'] = np.where(own[:, 0], m['seen'], 0).astype(np.int32)
+            res['boxes_predicted'] = s['box'] + vel[:, :4] * gap
+            res['keypoints_predicted'] = s['keypoints'][:, :, :2] + (vel[:, 4:] * gap)[:, None, :]
         return res
 
     def update(self, outputs):

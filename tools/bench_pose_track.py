@@ -34,7 +34,16 @@ measures what `PoseTracker(assignment='optimal')` costs against the greedy track
 for one stream and for one stream per image, each with a greedy and an optimal tracker on the same record; and of the launch
 alone on two records made for it (tests/track_assign_cases.py: the chain of 64 boxes stepping half a box to and fro, and 64
 random overlapping boxes, 64 slots, --batch frames of one stream, IoU) - the longest searches the reference counts. The
-comparison is the greedy launch of the same run; no ratio is fixed in advance."""
+comparison is the greedy launch of the same run; no ratio is fixed in advance.
+
+    timeout -k 10 300 python tools/bench_pose_track.py --motion [--assignment greedy|optimal] [the same options]
+
+measures what `PoseTracker(motion=ConstantVelocity())` adds and writes it under the "motion" key of --out in the same way:
+device time, ALTERNATING in one run and on the same record, of the captured graph with a motion tracker against the graph with
+a plain tracker of the same assignment, and of the track launch plus the commit copies alone (mpn_pose_track_motion and two
+state copies against the plain entry and one), for one stream and for one stream per image. The frames are one frame panned by
+4 pixels a frame, so that tracks go on and carry velocities. The yardstick is the plain tracker of the same run; no ratio is
+fixed in advance, and nothing is said about tracking quality."""
 import argparse
 import json
 import os
@@ -142,6 +151,60 @@ def smooth_leg(args, det, frames):
     print(json.dumps({"smooth": result}))
 
 
+def motion_leg(args, det, frames):
+    from multiposenet_amd.inference import ConstantVelocity, PoseTracker
+    b, s, thr = args.batch, args.size, args.threshold
+    frames = [np.roll(frames[0], 4 * f, axis=1) for f in range(b)]     # (as in smooth_leg: one camera's consecutive frames)
+    timed, tracked, coasting = {}, {}, {}
+    for streams in (1, b):
+        kw = dict(streams=streams, similarity=args.similarity, max_boxes=det.params['max_boxes'], assignment=args.assignment)
+        trackers = {"plain": PoseTracker(**kw), "motion": PoseTracker(motion=ConstantVelocity(), **kw)}
+        tag = "one_stream" if streams == 1 else "one_stream_per_image"
+        for name, t in trackers.items():                               # warm-up: graphs captured, states filled
+            for _ in range(3):
+                outs = det.predict_images(frames, size=(s, s), score_threshold=thr, track=t)
+            tracked[f"{name}_{tag}"] = sum(int((o['track_ids'] > 0).sum()) for o in outs) / b
+            if name == "motion":
+                coasting[tag] = sum(len(o['coasting_ids']) for o in outs) / b
+            ent = next(e for e in det._graphs.values() if getattr(e, 'track', None) is t)
+            whole = ent.outs['record']
+            nbytes = whole.numel() - t.out_bytes(b)
+
+            def track_and_commit(t=t, record=whole[:nbytes], rows=whole[nbytes:]):
+                t.launch(record, rows, b)
+                t.commit()
+            timed[f"graph_{name}_{tag}"] = ent.graph.replay
+            timed[f"track_launch_and_commit_{name}_{tag}"] = track_and_commit
+    for fn in timed.values():
+        fn()
+    ms = {name: [] for name in timed}
+    for _ in range(args.rounds):
+        for name, fn in timed.items():
+            ms[name].append(events_ms(fn, 20))
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    ratios = {name.replace("_motion", ""): med[name] / med[name.replace("_motion", "_plain")] for name in med if "_motion" in name}
+    result = {"device": torch.cuda.get_device_name(0), "dtype": args.dtype, "batch": b, "source": list(args.source), "size": [s, s],
+              "score_threshold": thr, "similarity": args.similarity, "assignment": args.assignment, "max_tracks": t.max_tracks,
+              "rounds": args.rounds, "constant_velocity": repr(t.motion), "tracked_per_image": tracked,
+              "coasting_per_image": coasting, "coasting_rows_d2h_bytes_per_batch": int(t.out_bytes(b) - t.coast_offset(b)),
+              "motion_state_bytes_one_stream_per_image": int(t.motion_state_bytes),
+              "device_ms_per_batch": {name: spread(v) for name, v in ms.items()}, "motion_over_plain": ratios,
+              "graph_added_ms_one_stream": med["graph_motion_one_stream"] - med["graph_plain_one_stream"],
+              "graph_added_ms_one_stream_per_image": med["graph_motion_one_stream_per_image"] - med["graph_plain_one_stream_per_image"]}
+    merged = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            merged = json.load(f)
+    merged["motion"] = result
+    out_dir = os.path.dirname(args.out)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(merged, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"motion": result}))
+
+
 def optimal_leg(args, det, frames):
     from multiposenet_amd.inference import PoseTracker
     from multiposenet_amd.pose_metrics import fill_record
@@ -226,6 +289,8 @@ def main():
     ap.add_argument("--smooth", action="store_true", help="only the smoothing leg; merged into --out under 'smooth'")
     ap.add_argument("--assignment", default="greedy", choices=["greedy", "optimal"],
                     help="optimal: only the optimal-assignment leg; merged into --out under 'optimal'")
+    ap.add_argument("--motion", action="store_true",
+                    help="only the motion leg (with --assignment: of that assignment); merged into --out under 'motion'")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_pose_track: no GPU (a measurement path does not fall back)")
@@ -239,6 +304,8 @@ def main():
     max_boxes = det.params['max_boxes']
     if args.smooth:
         return smooth_leg(args, det, frames)
+    if args.motion:
+        return motion_leg(args, det, frames)
     if args.assignment == "optimal":
         return optimal_leg(args, det, frames)
     tracker = PoseTracker(streams=args.streams, similarity=args.similarity, max_boxes=max_boxes)
@@ -313,7 +380,7 @@ def main():
     result["track_share_of_graph_device_time"] = statistics.median(track_ms) / statistics.median(graph_ms)
     if os.path.exists(args.out):                                       # the --smooth and --assignment optimal runs' records stay
         with open(args.out) as f:
-            result.update({k: v for k, v in json.load(f).items() if k in ("smooth", "optimal")})
+            result.update({k: v for k, v in json.load(f).items() if k in ("smooth", "optimal", "motion")})
     out_dir = os.path.dirname(args.out)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
