@@ -7,6 +7,8 @@
 and returns the seven outputs of OUTPUT_NAMES (create_pb.py:22-26) with the score filter of inference/detector.py:54-59.
 The reference freezes three checkpoints into one `.pb` (create_pb.py:170-185); here the three variable sets are three `.npz`
 files keyed by the reference's variable names (multiposenet_amd.checkpoint)."""
+import collections
+
 import numpy as np
 import torch
 
@@ -137,6 +139,41 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps')):
+    """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
+    'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
+    (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
+    return_heatmaps."""
+    __slots__ = ()
+
+    @property
+    def jpeg(self):
+        """(quality, sampling) of annotate='jpeg', else None."""
+        return self.annotate if isinstance(self.annotate, tuple) else None
+
+    def tail(self, b):
+        """What the options add behind the base of an entry's key for b images: every combination an entry of its own."""
+        key = ()
+        if self.annotate:
+            key += ('annotate', 'jpeg', self.jpeg[1]) if self.jpeg else ('annotate',)
+        if self.plot_maps:
+            key += ('maps',)
+        key += self.oks + self.tta
+        if self.track is not None:
+            key += ('track', self.track.serial, b)
+        return key + self.style
+
+
+def record_layout(b, max_boxes, oks=None, track=None):
+    """The bytes a call brings to the host in one copy, as three slices: mpn_pose_gather's record; behind it the rows of
+    mpn_oks_match (oks: the entry's pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's
+    tracking.PoseTracker, which lays out its own rows: `row_offsets`). A part that is not there is empty; a record of 0 bytes:
+    more slots than mpn_pose_gather packs."""
+    record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
+    rows = record + (oks.out_bytes if oks is not None else 0)
+    return slice(0, record), slice(record, rows), slice(rows, rows + (track.out_bytes(b) if track is not None else 0))
+
+
 class _Entry:
     """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
     input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
@@ -169,7 +206,7 @@ def unpack_record(record, b, max_boxes, with_keypoints=True):
     lib = _lib.lib()
     first, stride = lib.mpn_pose_gather_row_offset(b, max_boxes, 0), lib.mpn_pose_gather_row_offset(b, max_boxes, 1)
     stride -= first
-    if stride != _ROW.itemsize or len(record) < lib.mpn_pose_gather_record_bytes(b, max_boxes):
+    if stride != _ROW.itemsize or len(record) < record_layout(b, max_boxes)[0].stop:
         raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
     header = record[:first].view(np.int32)
     total, counts, num_boxes, overflow = int(header[0]), header[1:1 + b], header[1 + b:1 + 2 * b], int(header[1 + 2 * b])
@@ -402,18 +439,18 @@ class Detector:
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
-        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
-        style = check_track_style(track_style, annotate, track)
-        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
-        b, h, w = check_batch(images)
-        thr = float(score_threshold)
-        oks = self._check_groundtruth(groundtruth, b)
-        trk = self._check_track(track, b)
-        ent = self._batch_entry(b, h, w, thr, bool(annotate), jp, plot_maps, oks, self._check_tta(flip, scales, h, w), trk, track, style)
-        if oks:
+        opts, (b, h, w) = self._options(
+            lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
+            jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
+            scales=scales, track=track, track_style=track_style)
+        # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
+        ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
+                          lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
+                          (b * h * w * 3,), fixed_frames=True)
+        if opts.oks:
             ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
-        if jp and ent.encode_plan.quality != jp[0]:                 # the frames are fixed: only another quality needs new descriptors
-            self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), jp))
+        if opts.jpeg and ent.encode_plan.quality != opts.jpeg[0]:   # the frames are fixed: only another quality needs new descriptors
+            self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), opts.jpeg))
         stage = ent.stage.numpy()
         if isinstance(images, np.ndarray):
             stage[...] = images
@@ -421,18 +458,30 @@ class Detector:
             for i, im in enumerate(images):
                 stage[i] = im
         ent.x[:b].copy_(ent.stage, non_blocking=True)               # ONE host-to-device copy
-        outs = self._run(ent, lambda: self._device_side_batch(ent.x, thr, annotate=ent.draw, encode=ent.encode, plotter=ent.maps,
-                                                              oks=ent.oks, aug=ent.tta, track=ent.track, style=ent.style))
-        if trk:
+        outs = self._run(ent, lambda: self._device_side_batch(ent, opts.thr))
+        if ent.track is not None:
             ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
-        return self._finish(ent, outs, b, return_heatmaps)
+        return self._finish(ent, outs, b, opts.return_heatmaps)
 
-    def _check_tta(self, flip, scales, h, w):
-        """check_tta for this Detector: averaging heatmaps needs the keypoint subnet's heatmap head."""
-        key = check_tta(flip, scales, h, w)
-        if key and not self._has_heatmaps():
+    def _options(self, shape, **given):
+        """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
+        returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style. shape(): the method's own
+        checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
+        (b, height, width) of the network input."""
+        jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
+        style = check_track_style(given['track_style'], given['annotate'], given['track'])
+        plot_maps = check_plot_maps(given['plot_maps'], self._has_heatmaps)
+        shaped = shape()
+        b, h, w = shaped[:3]
+        thr = float(given['score_threshold'])
+        oks = self._check_groundtruth(given['groundtruth'], b)
+        self._check_track(given['track'], b)
+        tta_key = check_tta(given['flip'], given['scales'], h, w)
+        if tta_key and not self._has_heatmaps():
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
-        return key
+        return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
+                        given['return_heatmaps']), shaped
 
     def _check_groundtruth(self, groundtruth, b):
         """The `groundtruth` argument of the predict_* methods -> () or the tail of the entry's key."""
@@ -447,9 +496,10 @@ class Detector:
         return ('oks', self.oks_score, int(self.oks_max_dets))
 
     def _check_track(self, track, b):
-        """The `track` argument of the predict_* methods -> () or the tail of the entry's key. Before any device work."""
+        """The `track` argument of the predict_* methods: raises unless it is None or a tracker this Detector can run over b
+        images. Before any device work."""
         if track is None:
-            return ()
+            return
         from ..tracking import PoseTracker
         if not isinstance(track, PoseTracker):
             raise ValueError("track must be a tracking.PoseTracker")
@@ -466,16 +516,6 @@ class Detector:
         if torch.device(track.device) != torch.device(self.net.device):
             raise ValueError(f"track=: the tracker lives on {track.device}, this Detector on {self.net.device}")
         track.out_bytes(b)
-        return ('track', track.serial, b)
-
-    def _place_style(self, style):
-        """A check_track_style key -> None or (TrackStyle, its table on the device): uploaded once, when the entry is made."""
-        if not style:
-            return None
-        return style[1], torch.from_numpy(style[1].tables().copy()).to(self.net.device)
-
-    def _oks_buffers(self, b, oks):
-        return pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, self.net.device, oks[1], oks[2])
 
     @staticmethod
     def _place_encode(ent, plan):
@@ -508,14 +548,13 @@ class Detector:
         if 'record' in outs:
             record = host['record'].numpy()
             persons = unpack_record(record, b, self.params['max_boxes'], self.assigner is not None)
+            _, oks_rows, track_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track)
+            counts = record[4:4 + 4 * b].view(np.int32)
             if ent.oks is not None:                                 # the match rows lie behind the record: they came with it
-                at = _lib.lib().mpn_pose_gather_record_bytes(b, self.params['max_boxes'])
-                for p, table in zip(persons, ent.oks.unpack(record[at:], record[4:4 + 4 * b].view(np.int32))):
+                for p, table in zip(persons, ent.oks.unpack(record[oks_rows], counts)):
                     p['oks'] = table
             if ent.track is not None:                               # the track rows lie behind those: the same copy
-                at = _lib.lib().mpn_pose_gather_record_bytes(b, self.params['max_boxes'])
-                at += ent.oks.out_bytes if ent.oks is not None else 0
-                for p, ids in zip(persons, ent.track.unpack(record[at:], record[4:4 + 4 * b].view(np.int32))):
+                for p, ids in zip(persons, ent.track.unpack(record[track_rows], counts)):
                     p.update(ids)
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
@@ -534,69 +573,69 @@ class Detector:
                 p['maps'] = frame
         return persons
 
-    def _batch_entry(self, b, h, w, thr, annotate=False, jp=None, plot_maps=False, oks=(), tta_key=(), trk=(), track=None,
-                     style=()):
-        """The buffers of one (b, h, w, threshold[, annotate][, plot_maps][, oks][, tta][, track]): pinned staging, the device input (with the
-        mirrors behind the batch and the inputs of the extra scales for a check_tta key), fixed drawing and
-        encode descriptors (`_run` adds the captured graph). use_graph False: the same buffers under a key of `_eager_batches`."""
-        key = (b, h, w, thr) if self.use_graph else ('eager', b, h, w)
-        if annotate:
-            key += ('annotate', 'jpeg', jp[1]) if jp else ('annotate',)
-        if plot_maps:
-            key += ('maps',)
-        key += oks + tta_key + trk + style
+    def _entry(self, opts, base, shape, make, capacity, fixed_frames=False):
+        """The entry of one key, base + opts.tail(b), in `_graphs` (use_graph False: `_eager_batches`), made on its first use
+        (`_run` adds the captured graph). make(): an _Entry with the staging and device buffers of the path. To it come the
+        device input for shape = (b, h, w) (with the mirrors behind the batch and the inputs of the extra scales for flip /
+        scales) and what each option needs: the drawing's buffers, sized for sources of capacity[0] bytes; the JPEG encoder,
+        which reserves capacity[1:]; the MapPlotter; the ground-truth buffers; the tracker; the style with its table, which
+        goes to the device once, here. fixed_frames (predict_batch): the frames are the batch itself, so the drawing and
+        encode descriptors are placed here, for good, and the encoder reserves what their plan needs."""
+        b, h, w = shape
+        key = base + opts.tail(b)
         store = self._graphs if self.use_graph else self._eager_batches
         ent = store.get(key)
         if ent is not None:
             return ent
         dev = self.net.device
-        ent = _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory())
-        self._place_input(ent, b, h, w, tta_key)
-        if annotate:                                                # the frames are the batch itself: fixed descriptors
-            ent.draw = draw.Buffers(b, self.params['max_boxes'], b * h * w * 3, dev)
-            ent.draw.place(*_batch_frames(b, h, w))
-        if jp:                                                      # the frames lie where the drawing writes them: fixed sizes
-            plan = _encode_plan(*_batch_frames(b, h, w), jp)
+        ent = make()
+        if opts.tta:
+            ent.tta = tta.Buffers(opts.tta[1], opts.tta[2], b, h, w, dev)
+            ent.x = ent.tta.x
+        else:
+            ent.x = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev)
+        if opts.annotate:
+            ent.draw = draw.Buffers(b, self.params['max_boxes'], capacity[0], dev)
+            if fixed_frames:
+                ent.draw.place(*_batch_frames(b, h, w))
+        if opts.jpeg:                                               # the frames lie where the drawing writes them
+            plan = _encode_plan(*_batch_frames(b, h, w), opts.jpeg) if fixed_frames else None
             ent.encode = jpeg.JpegBatchEncoder(dev)
-            ent.encode.reserve(b, *plan.need)
-            self._place_encode(ent, plan)
-        if plot_maps:
+            ent.encode.reserve(b, *(plan.need if plan else capacity[1:]))
+            if plan:
+                self._place_encode(ent, plan)
+        if opts.plot_maps:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
-        if oks:
-            ent.oks = self._oks_buffers(b, oks)
-        ent.track = track if trk else None
-        ent.style = self._place_style(style)
+        if opts.oks:
+            ent.oks = pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, dev, opts.oks[1], opts.oks[2])
+        ent.track = opts.track
+        if opts.style:
+            ent.style = opts.style[1], torch.from_numpy(opts.style[1].tables().copy()).to(dev)
         store[key] = ent
         return ent
 
-    def _place_input(self, ent, b, h, w, tta_key):
-        """The device input of a new entry: uint8 [b, h, w, 3], or the tta.Buffers of a check_tta key and their base input."""
-        if tta_key:
-            ent.tta = tta.Buffers(tta_key[1], tta_key[2], b, h, w, self.net.device)
-            ent.x = ent.tta.x
-        else:
-            ent.x = torch.empty((b, h, w, 3), dtype=torch.uint8, device=self.net.device)
-
-    def _device_side_batch(self, x, score_threshold, extent=None, annotate=None, frames=None, encode=None, plotter=None,
-                           oks=None, aug=None, track=None, style=None):
-        """_device_side for b images, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN runs ONCE over all
-        b * max_boxes slots (an instance of that batch size on the shared variables). extent (predict_images): f32 [b, 4] on
-        the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to the source images. annotate (a
-        draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat uint8; default:
-        the batch x itself) -> 'annotated', the packed RGBA frames. encode (a jpeg.JpegBatchEncoder whose descriptors are in
-        place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the device as 'encoded'.
-        plotter (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
-        oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
-        the record in the same buffer, so that they reach the host in the record's copy.
-        track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
+    def _device_side_batch(self, ent, score_threshold, extent=None, frames=None):
+        """_device_side for the b images of the entry's input ent.x, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN
+        runs ONCE over all b * max_boxes slots (an instance of that batch size on the shared variables). extent
+        (predict_images): f32 [b, 4] on the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to
+        the source images. What the entry holds decides the rest:
+        ent.draw (a draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat
+        uint8; default: the batch x itself) -> 'annotated', the packed RGBA frames. ent.encode (a jpeg.JpegBatchEncoder whose
+        descriptors are in place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the
+        device as 'encoded'.
+        ent.maps (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
+        ent.oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
+        the record in the same buffer (`record_layout`), so that they reach the host in the record's copy.
+        ent.track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
         tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits). A tracker
         with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
-        style ((TrackStyle, its table on the device), with annotate and track): the drawing is mpn_draw_tracks, which reads
+        ent.style ((TrackStyle, its table on the device), with draw and track): the drawing is mpn_draw_tracks, which reads
         those rows in place.
-        aug (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
+        ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
         net = self.net
+        x, annotate, aug, track = ent.x, ent.draw, ent.tta, ent.track
         if aug is not None and aug.flip:
             tta.mirror_images(x[:aug.b], x[aug.b:])
         heat, seg, feats = self._keypoint_pass(x)
@@ -612,14 +651,14 @@ class Detector:
             feats = {k: (raw[:b], aff) for k, (raw, aff) in feats.items()}
         b, h, w, _ = x.shape
         dev = {'heat': heat, 'seg': seg}
-        if plotter is not None:
-            dev['maps'] = plotter.launch(x, heat, seg, normalise=True)
+        if ent.maps is not None:
+            dev['maps'] = ent.maps.launch(x, heat, seg, normalise=True)
         if annotate is not None and frames is None:
             frames = x.view(-1)
         if self.retinanet is None:
             if annotate is not None:                                # no detector: the frames with alpha 255
                 dev['annotated'] = annotate.launch(frames, None, False)
-            return self._encode_frames(dev, encode)
+            return self._encode_frames(dev, ent.encode)
         pred = self._detect(feats, b, h, w)
         max_boxes = pred['boxes'].shape[1]
         kscore = kpos = None
@@ -627,14 +666,12 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        lib = _lib.lib()
-        nbytes = lib.mpn_pose_gather_record_bytes(b, max_boxes)
+        in_record, oks_rows, track_rows = record_layout(b, max_boxes, ent.oks, track)
+        nbytes = in_record.stop
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        oks_bytes = oks.out_bytes if oks is not None else 0
-        track_bytes = track.out_bytes(b) if track is not None else 0
-        whole = torch.empty(nbytes + oks_bytes + track_bytes, dtype=torch.uint8, device=net.device)
-        record = whole[:nbytes]
+        whole = torch.empty(track_rows.stop, dtype=torch.uint8, device=net.device)
+        record = whole[in_record]
         if extent is None:
             _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
                       _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
@@ -643,19 +680,20 @@ class Detector:
             _lib.call("mpn_pose_gather_sized", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']),
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
-        if oks is not None:
-            oks.launch(record, whole[nbytes:nbytes + oks_bytes])
+        if ent.oks is not None:
+            ent.oks.launch(record, whole[oks_rows])
         if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
-            track.launch_all(record, whole[nbytes + oks_bytes:], b)
+            track.launch_all(record, whole[track_rows], b)
         dev['record'] = whole
-        if annotate is not None and style is not None:              # identities: mpn_draw_tracks on the rows just written
-            rows = whole[nbytes + oks_bytes:]
+        if annotate is not None and ent.style is not None:          # identities: mpn_draw_tracks on the rows just written
+            style, table = ent.style
+            rows = whole[track_rows]
             n = track.track_bytes(b)
-            smoothed = rows[n:] if style[0].keypoints == 'smoothed' else None
-            dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, style[1], self.assigner is not None)
+            smoothed = rows[n:] if style.keypoints == 'smoothed' else None
+            dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, table, self.assigner is not None)
         elif annotate is not None:
             dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
-        return self._encode_frames(dev, encode)
+        return self._encode_frames(dev, ent.encode)
 
     def _keypoint_pass(self, x):
         """Backbone and keypoint subnet over a uint8 batch: (sigmoid heatmaps, mask, backbone features)."""
@@ -714,13 +752,14 @@ class Detector:
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
         raises ValueError.
         """
-        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
-        style = check_track_style(track_style, annotate, track)
-        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
-        items = resample.check_images(images)
-        height, width = resample.check_size(size)
-        plan = resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
-        tta_key = self._check_tta(flip, scales, height, width)
+        def shape():
+            items = resample.check_images(images)
+            height, width = resample.check_size(size)
+            return len(items), height, width, items, resample.Plan([im.shape[:2] for im in items], height, width, keep_aspect_ratio)
+        opts, (_, _, _, items, plan) = self._options(
+            shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
+            jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
+            track=track, track_style=track_style)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -728,8 +767,7 @@ class Detector:
                 stage[at:at + im.size] = im.reshape(-1)
             nb = plan.stage_bytes                                   # this batch's bytes, not the buffers' capacity
             ent.sources[:nb].copy_(ent.stage[:nb], non_blocking=True)       # ONE host-to-device copy of the frames
-        return self._predict_sources(plan, upload, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key, track, style)
+        return self._predict_sources(plan, upload, opts, groundtruth)
 
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
@@ -755,20 +793,22 @@ class Detector:
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
-        jp = check_annotate(annotate, jpeg_quality, jpeg_subsampling)
-        style = check_track_style(track_style, annotate, track)
-        plot_maps = check_plot_maps(plot_maps, self._has_heatmaps)
-        if isinstance(jpegs, (bytes, bytearray, memoryview)):
-            raise ValueError("jpegs must be a list of bytes (got one bytes object)")
-        items = list(jpegs)
-        if len(items) < 1:
-            raise ValueError("empty batch")
-        if any(not isinstance(j, (bytes, bytearray, memoryview)) for j in items):
-            raise ValueError("a JPEG must be bytes")
-        infos = [jpeg.jpeg_info(j) for j in items]
-        height, width = resample.check_size(size)
-        plan = resample.Plan([(i['height'], i['width']) for i in infos], height, width, keep_aspect_ratio, align=16)
-        tta_key = self._check_tta(flip, scales, height, width)
+        def shape():
+            if isinstance(jpegs, (bytes, bytearray, memoryview)):
+                raise ValueError("jpegs must be a list of bytes (got one bytes object)")
+            items = list(jpegs)
+            if len(items) < 1:
+                raise ValueError("empty batch")
+            if any(not isinstance(j, (bytes, bytearray, memoryview)) for j in items):
+                raise ValueError("a JPEG must be bytes")
+            infos = [jpeg.jpeg_info(j) for j in items]
+            height, width = resample.check_size(size)
+            return len(items), height, width, items, resample.Plan([(i['height'], i['width']) for i in infos], height, width,
+                                                                   keep_aspect_ratio, align=16)
+        opts, (_, _, _, items, plan) = self._options(
+            shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
+            jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
+            track=track, track_style=track_style)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -779,56 +819,45 @@ class Detector:
                 ent.jpeg = jpeg.JpegBatchDecoder(self.net.device)
             ent.jpeg.decode(entries, ent.sources, plan.src_offsets, torch.cuda.current_stream(self.net.device))
             self.jpeg_staged_bytes, self.jpeg_fallbacks = ent.jpeg.staged_bytes, ent.jpeg.fallbacks
-        return self._predict_sources(plan, decode, jp, annotate, score_threshold, return_heatmaps, plot_maps, groundtruth,
-                                     tta_key, track, style)
+        return self._predict_sources(plan, decode, opts, groundtruth)
 
-    def _predict_sources(self, plan, put_sources, jp, annotate, score_threshold, return_heatmaps, plot_maps=False,
-                         groundtruth=None, tta_key=(), track=None, style=()):
+    def _predict_sources(self, plan, put_sources, opts, groundtruth):
         """predict_images and predict_jpegs behind their argument checks. put_sources(ent) queues what brings this batch's
         frames to `ent.sources` where `plan` packs them; around it, in stream order: the descriptors, extents and tables in
-        one copy, the frames, the drawing's and the encoder's descriptors, the graph."""
-        b, thr = plan.b, float(score_threshold)
-        eplan = _encode_plan(plan.sizes, plan.src_offsets, jp) if jp else None
-        oks = self._check_groundtruth(groundtruth, b)
-        trk = self._check_track(track, b)
-        ent = self._images_entry(b, plan.height, plan.width, thr, plan, bool(annotate), eplan, plot_maps, oks, tta_key, trk, track, style)
+        one copy, the frames, the drawing's and the encoder's descriptors, the ground truth, the graph."""
+        b = plan.b
+        eplan = _encode_plan(plan.sizes, plan.src_offsets, opts.jpeg) if opts.jpeg else None
+        ent = self._images_entry(plan, opts, eplan)
         nw = plan.meta_words                                        # this batch's words, not the buffers' capacity
         ent.meta_stage.numpy()[:nw] = plan.meta
         ent.meta[:nw].copy_(ent.meta_stage[:nw], non_blocking=True)
         put_sources(ent)
-        if annotate:
+        if opts.annotate:
             ent.draw.place(plan.sizes, plan.src_offsets)
-        if jp:
+        if eplan:
             self._place_encode(ent, eplan)
-        if oks:
+        if opts.oks:
             ent.oks.place(groundtruth)
-        outs = self._run(ent, lambda: self._device_side_images(ent, thr))
-        if trk:
+        outs = self._run(ent, lambda: self._device_side_images(ent, opts.thr))
+        if ent.track is not None:
             ent.track.commit()                                      # as in predict_batch: once per call, outside the graph
-        persons = self._finish(ent, outs, b, return_heatmaps)
-        if return_heatmaps:
+        persons = self._finish(ent, outs, b, opts.return_heatmaps)
+        if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):
                 p['resized_size'] = new_size
         return persons
 
-    def _images_entry(self, b, h, w, thr, plan, annotate=False, eplan=None, plot_maps=False, oks=(), tta_key=(), trk=(),
-                      track=None, style=()):
-        """The persistent state of predict_images for one (b, h, w, threshold) and one CAPACITY (bytes of packed sources, words
-        of descriptors + tables, bytes of intermediates, each a power of two): pinned staging, device buffers, the captured
-        graph. A batch that fits the capacity of an earlier one replays its graph whatever its mix of sizes; one that
-        exceeds it gets larger buffers and a new graph. annotate: an entry (and capacity) of its own, with the packed RGBA
-        output sized from the capacity of the sources - it grows with them. eplan (annotate='jpeg'): an entry per sampling, whose
-        capacity also covers the encoder's coefficients, streams and workspace. plot_maps: an entry of its own with a
-        MapPlotter for the canvas batch. oks (groundtruth=): an entry of its own with the ground-truth buffers. tta_key (flip=,
-        scales=): an entry of its own whose canvas batch has the mirrors behind it, with the inputs of the extra scales.
-        trk (track=): an entry of its own per tracker, whose graph reads and writes that tracker's state buffers."""
+    def _images_entry(self, plan, opts, eplan):
+        """The persistent state of predict_images for one (b, h, w, threshold), one set of options (`_Options.tail`: each an
+        entry, and a capacity, of its own) and one CAPACITY (bytes of packed sources, words of descriptors + tables, bytes of
+        intermediates, each a power of two): pinned staging, device buffers, the captured graph. A batch that fits the
+        capacity of an earlier one replays its graph whatever its mix of sizes; one that exceeds it gets larger buffers and a
+        new graph. With annotate the packed RGBA output is sized from the capacity of the sources - it grows with them. eplan
+        (annotate='jpeg'): the capacity also covers the encoder's coefficients, streams and workspace."""
+        b, h, w = plan.b, plan.height, plan.width
         store = self._graphs if self.use_graph else self._eager_batches
         need = (plan.stage_bytes, plan.meta_words, plan.work_bytes) + (eplan.need if eplan else ())
-        base = ('images', b, h, w, thr)
-        tail = (('annotate', 'jpeg', eplan.subsampling) if eplan else ('annotate',)) if annotate else ()
-        if plot_maps:
-            tail += ('maps',)
-        tail += oks + tta_key + trk + style
+        base, tail = ('images', b, h, w, opts.thr), opts.tail(b)
         cap_key = (base, self.use_graph) + tail
         cap = self._image_capacity.get(cap_key)
         if cap is None or any(n > c for n, c in zip(need, cap)):
@@ -836,33 +865,18 @@ class Detector:
                 store.pop(base + (cap,) + tail, None)      # superseded: its buffers and graph are never looked up again
             cap = tuple(resample.capacity_for(max(n, c)) for n, c in zip(need, cap or (0,) * len(need)))
             self._image_capacity[cap_key] = cap
-        key = base + (cap,) + tail
-        ent = store.get(key)
-        if ent is not None:
-            return ent
-        dev = self.net.device
         stage_bytes, meta_words, work_bytes = cap[:3]
-        if _lib.lib().mpn_image_resize_desc_bytes() != resample.DESC_WORDS * 4:
-            raise _lib.MpnError("mpn_image_resize: the descriptor's layout is not the one this binding was written against")
-        ent = _Entry(stage=torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
-                     sources=torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
-                     meta_stage=torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
-                     meta=torch.zeros(meta_words, dtype=torch.int32, device=dev),
-                     work=torch.empty(work_bytes, dtype=torch.uint8, device=dev))
-        self._place_input(ent, b, h, w, tta_key)
-        if annotate:
-            ent.draw = draw.Buffers(b, self.params['max_boxes'], stage_bytes, dev)
-        if eplan:
-            ent.encode = jpeg.JpegBatchEncoder(dev)
-            ent.encode.reserve(b, *cap[3:])
-        if plot_maps:
-            ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
-        if oks:
-            ent.oks = self._oks_buffers(b, oks)
-        ent.track = track if trk else None
-        ent.style = self._place_style(style)
-        store[key] = ent
-        return ent
+
+        def make():
+            dev = self.net.device
+            if _lib.lib().mpn_image_resize_desc_bytes() != resample.DESC_WORDS * 4:
+                raise _lib.MpnError("mpn_image_resize: the descriptor's layout is not the one this binding was written against")
+            return _Entry(stage=torch.zeros(stage_bytes, dtype=torch.uint8).pin_memory(),
+                          sources=torch.zeros(stage_bytes, dtype=torch.uint8, device=dev),
+                          meta_stage=torch.zeros(meta_words, dtype=torch.int32).pin_memory(),
+                          meta=torch.zeros(meta_words, dtype=torch.int32, device=dev),
+                          work=torch.empty(work_bytes, dtype=torch.uint8, device=dev))
+        return self._entry(opts, base + (cap,), (b, h, w), make, (stage_bytes,) + cap[3:])
 
     def _device_side_images(self, ent, thr):
         """mpn_image_resize (ragged sources -> the uint8 canvas batch) -> _device_side_batch with mpn_pose_gather_sized last."""
@@ -873,8 +887,7 @@ class Detector:
         tables = meta[b * (resample.DESC_WORDS + 4):]
         _lib.call("mpn_image_resize", _lib.ptr(ent.sources), _lib.ptr(tables), _lib.ptr(meta), b, h, w, _lib.ptr(x),
                   _lib.ptr(ent.work), ent.work.numel(), _lib.stream_ptr())
-        return self._device_side_batch(x, thr, extent, annotate=ent.draw, frames=ent.sources, encode=ent.encode, plotter=ent.maps,
-                                       oks=ent.oks, aug=ent.tta, track=ent.track, style=ent.style)
+        return self._device_side_batch(ent, thr, extent, frames=ent.sources)
 
     def _assigner_for(self, n):
         a = self._batch_assigners.get(n)

@@ -64,7 +64,46 @@ _SMOOTH_SLOT = np.dtype([('id', np.int32),
 _serials = itertools.count(1)
 
 
-class OneEuro:
+class _Parameters:
+    """Launch parameters as float32 values in the subclass's `__slots__`, checked (a number, finite, then the subclass's
+    `_rule`) and immutable; equal and hashed by value."""
+    __slots__ = ()
+
+    def __init__(self, **values):
+        cls = type(self).__name__
+        for name, given in values.items():
+            try:
+                with np.errstate(over='ignore'):
+                    v = float(np.float32(given))                    # what the launch receives (too large: inf, refused below)
+            except (TypeError, ValueError):
+                raise ValueError(f"{cls}: {name} must be a number (got {given!r})") from None
+            if not math.isfinite(v):
+                raise ValueError(f"{cls}: {name} must be finite (got {given!r})")
+            rule = self._rule(name, v)
+            if rule:
+                raise ValueError(f"{cls}: {name} must be {rule} (got {given!r})")
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    def astuple(self):
+        return tuple(getattr(self, n) for n in self.__slots__)
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self.astuple() == other.astuple()
+
+    def __hash__(self):
+        return hash(self.astuple())
+
+    def __repr__(self):
+        return f"{type(self).__name__}(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+
+
+class OneEuro(_Parameters):
     """The parameters of the One-Euro filter `PoseTracker(smooth=...)` runs on every tracked joint. Immutable.
 
     rate: frames per second of a stream (a frame a person is missing from still counts as 1 / rate seconds).
@@ -75,41 +114,17 @@ class OneEuro:
     __slots__ = ('rate', 'min_cutoff', 'beta', 'd_cutoff', 'min_keypoint_score')
 
     def __init__(self, rate=30.0, min_cutoff=1.0, beta=0.007, d_cutoff=1.0, min_keypoint_score=0.0):
-        values = dict(rate=rate, min_cutoff=min_cutoff, beta=beta, d_cutoff=d_cutoff, min_keypoint_score=min_keypoint_score)
-        for name, v in values.items():
-            try:
-                with np.errstate(over='ignore'):
-                    v = float(np.float32(v))                        # what the launch receives (too large: inf, refused below)
-            except (TypeError, ValueError):
-                raise ValueError(f"OneEuro: {name} must be a number (got {v!r})") from None
-            if not math.isfinite(v):
-                raise ValueError(f"OneEuro: {name} must be finite (got {values[name]!r})")
-            if name in ('rate', 'min_cutoff', 'd_cutoff') and not v > 0:
-                raise ValueError(f"OneEuro: {name} must be > 0 (got {values[name]!r})")
-            if name == 'beta' and not v >= 0:
-                raise ValueError(f"OneEuro: beta must be >= 0 (got {values[name]!r})")
-            object.__setattr__(self, name, v)
+        super().__init__(rate=rate, min_cutoff=min_cutoff, beta=beta, d_cutoff=d_cutoff, min_keypoint_score=min_keypoint_score)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("OneEuro is immutable")
-
-    def __delattr__(self, name):
-        raise AttributeError("OneEuro is immutable")
-
-    def astuple(self):
-        return (self.rate, self.min_cutoff, self.beta, self.d_cutoff, self.min_keypoint_score)
-
-    def __eq__(self, other):
-        return isinstance(other, OneEuro) and self.astuple() == other.astuple()
-
-    def __hash__(self):
-        return hash(self.astuple())
-
-    def __repr__(self):
-        return "OneEuro(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+    @staticmethod
+    def _rule(name, v):
+        if name in ('rate', 'min_cutoff', 'd_cutoff') and not v > 0:
+            return "> 0"
+        if name == 'beta' and not v >= 0:
+            return ">= 0"
 
 
-class ConstantVelocity:
+class ConstantVelocity(_Parameters):
     """The parameters of the constant-velocity prediction `PoseTracker(motion=...)` matches against. Immutable.
 
     velocity_gain: the weight in 0..1 of a newly observed velocity (the step from a track's last observed pose to the detection
@@ -120,36 +135,19 @@ class ConstantVelocity:
     __slots__ = ('velocity_gain', 'damping')
 
     def __init__(self, velocity_gain=0.5, damping=1.0):
-        values = dict(velocity_gain=velocity_gain, damping=damping)
-        for name, v in values.items():
-            try:
-                with np.errstate(over='ignore'):
-                    v = float(np.float32(v))                        # what the launch receives
-            except (TypeError, ValueError):
-                raise ValueError(f"ConstantVelocity: {name} must be a number (got {v!r})") from None
-            if not math.isfinite(v):
-                raise ValueError(f"ConstantVelocity: {name} must be finite (got {values[name]!r})")
-            if not 0 <= v <= 1:
-                raise ValueError(f"ConstantVelocity: {name} must be in 0..1 (got {values[name]!r})")
-            object.__setattr__(self, name, v)
+        super().__init__(velocity_gain=velocity_gain, damping=damping)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("ConstantVelocity is immutable")
+    @staticmethod
+    def _rule(name, v):
+        if not 0 <= v <= 1:
+            return "in 0..1"
 
-    def __delattr__(self, name):
-        raise AttributeError("ConstantVelocity is immutable")
 
-    def astuple(self):
-        return (self.velocity_gain, self.damping)
-
-    def __eq__(self, other):
-        return isinstance(other, ConstantVelocity) and self.astuple() == other.astuple()
-
-    def __hash__(self):
-        return hash(self.astuple())
-
-    def __repr__(self):
-        return "ConstantVelocity(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.__slots__) + ")"
+# the prev / next state pairs of a tracker: (prefix of the attributes `prev`, `next`, `state_bytes`, `stream_bytes`; the
+# option that asks for the pair; the library's size function; the head and slot of one stream; the name in messages)
+_STATES = (('', None, 'mpn_pose_track_state_bytes', _HEAD, _SLOT, 'mpn_pose_track'),
+           ('smooth_', 'smooth', 'mpn_pose_smooth_state_bytes', _SMOOTH_HEAD, _SMOOTH_SLOT, 'mpn_pose_smooth'),
+           ('motion_', 'motion', 'mpn_pose_track_motion_state_bytes', _MOTION_HEAD, _MOTION_SLOT, 'mpn_pose_track_motion'))
 
 
 class PoseTracker:
@@ -199,30 +197,36 @@ class PoseTracker:
         if self.max_misses < 0:
             raise ValueError(f"max_misses must not be negative (got {max_misses})")
         import torch
-        lib = _lib.lib()
-        self.state_bytes = lib.mpn_pose_track_state_bytes(self.streams, self.max_tracks)
-        self.stream_bytes = _HEAD.itemsize + self.max_tracks * _SLOT.itemsize
-        if self.state_bytes == 0 or self.state_bytes != self.streams * self.stream_bytes:
-            raise _lib.MpnError("mpn_pose_track: the state's layout is not the one this binding was written against")
         self.device = torch.device(device) if device is not None else _lib.current_device()
+        for prefix, _, size, head, slot, name in self._states():
+            state_bytes = getattr(_lib.lib(), size)(self.streams, self.max_tracks)
+            stream_bytes = head.itemsize + self.max_tracks * slot.itemsize
+            if state_bytes == 0 or state_bytes != self.streams * stream_bytes:
+                raise _lib.MpnError(f"{name}: the state's layout is not the one this binding was written against")
+            setattr(self, prefix + 'state_bytes', state_bytes)
+            setattr(self, prefix + 'stream_bytes', stream_bytes)
+            for which in ('prev', 'next'):
+                setattr(self, prefix + which, torch.zeros(state_bytes, dtype=torch.uint8, device=self.device))
         self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
-        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        if smooth is not None:
-            self.smooth_state_bytes = lib.mpn_pose_smooth_state_bytes(self.streams, self.max_tracks)
-            self.smooth_stream_bytes = _SMOOTH_HEAD.itemsize + self.max_tracks * _SMOOTH_SLOT.itemsize
-            if self.smooth_state_bytes == 0 or self.smooth_state_bytes != self.streams * self.smooth_stream_bytes:
-                raise _lib.MpnError("mpn_pose_smooth: the state's layout is not the one this binding was written against")
-            self.smooth_prev = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
-            self.smooth_next = torch.zeros(self.smooth_state_bytes, dtype=torch.uint8, device=self.device)
-        if motion is not None:
-            self.motion_state_bytes = lib.mpn_pose_track_motion_state_bytes(self.streams, self.max_tracks)
-            self.motion_stream_bytes = _MOTION_HEAD.itemsize + self.max_tracks * _MOTION_SLOT.itemsize
-            if self.motion_state_bytes == 0 or self.motion_state_bytes != self.streams * self.motion_stream_bytes:
-                raise _lib.MpnError("mpn_pose_track_motion: the state's layout is not the one this binding was written against")
-            self.motion_prev = torch.zeros(self.motion_state_bytes, dtype=torch.uint8, device=self.device)
-            self.motion_next = torch.zeros(self.motion_state_bytes, dtype=torch.uint8, device=self.device)
         self._update = {}                                           # update(): device record and rows per batch size
+
+    def _states(self):
+        """The rows of _STATES this tracker keeps: the track state, with smooth= the filters', with motion= the velocities'."""
+        return [s for s in _STATES if s[1] is None or getattr(self, s[1]) is not None]
+
+    def _pairs(self, stream=None):
+        """(row of _STATES, prev, next) of every state this tracker keeps: whole, or cut to the bytes of one stream."""
+        if stream is not None and not 0 <= int(stream) < self.streams:
+            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
+        res = []
+        for state in self._states():
+            prev, nxt = getattr(self, state[0] + 'prev'), getattr(self, state[0] + 'next')
+            if stream is not None:
+                n = getattr(self, state[0] + 'stream_bytes')
+                part = slice(int(stream) * n, int(stream) * n + n)
+                prev, nxt = prev[part], nxt[part]
+            res.append((state, prev, nxt))
+        return res
 
     def check_batch(self, b):
         """The number of images of a call -> frames per stream."""
@@ -230,35 +234,39 @@ class PoseTracker:
             raise ValueError(f"track=: {b} images are not a whole number of frames for each of {self.streams} streams")
         return b // self.streams
 
+    def row_offsets(self, b):
+        """The layout of a call's rows for b images -> (n, at, end): mpn_pose_track's rows in [0, n), with smooth= the
+        smoothed rows behind them, with motion= the coasting rows in [at, end), behind those at the next multiple of 8 bytes
+        (at = end = where the rows end without motion=). Every size is the library's, checked against this binding's rows."""
+        self.check_batch(b)
+
+        def rows(size, per_image, row, what):
+            n = getattr(_lib.lib(), size)(b, per_image)
+            if n == 0 or n != b * per_image * row.itemsize:
+                raise ValueError(f"{what} are more than one launch takes")
+            return n
+        n = at = rows('mpn_pose_track_out_bytes', self.max_boxes, _OUT, f"mpn_pose_track: {b} x {self.max_boxes} slots")
+        if self.smooth is not None:
+            at += rows('mpn_pose_smooth_out_bytes', self.max_boxes, _SMOOTH_OUT, f"mpn_pose_smooth: {b} x {self.max_boxes} slots")
+        if self.motion is None:
+            return n, at, at
+        at = (at + 7) // 8 * 8
+        return n, at, at + rows('mpn_pose_track_coast_bytes', self.max_tracks, _COAST,
+                                f"mpn_pose_track_motion: {b} x {self.max_tracks} coasting rows")
+
     def track_bytes(self, b):
         """The bytes of mpn_pose_track's rows for b images."""
-        self.check_batch(b)
-        n = _lib.lib().mpn_pose_track_out_bytes(b, self.max_boxes)
-        if n == 0 or n != b * self.max_boxes * _OUT.itemsize:
-            raise ValueError(f"mpn_pose_track: {b} x {self.max_boxes} slots are more than one launch takes")
-        return n
+        return self.row_offsets(b)[0]
 
     def coast_offset(self, b):
         """Where the coasting rows of a motion= tracker begin within a call's rows: behind the track rows and any smoothed
         rows, at the next multiple of 8 bytes."""
-        n = self.track_bytes(b)
-        if self.smooth is not None:
-            m = _lib.lib().mpn_pose_smooth_out_bytes(b, self.max_boxes)
-            if m == 0 or m != b * self.max_boxes * _SMOOTH_OUT.itemsize:
-                raise ValueError(f"mpn_pose_smooth: {b} x {self.max_boxes} slots are more than one launch takes")
-            n += m
-        return (n + 7) // 8 * 8 if self.motion is not None else n
+        return self.row_offsets(b)[1]
 
     def out_bytes(self, b):
         """The bytes of a call's rows for b images: the track rows, with smooth= the smoothed rows behind them, and with
         motion= the coasting rows behind those."""
-        n = self.coast_offset(b)
-        if self.motion is not None:
-            m = _lib.lib().mpn_pose_track_coast_bytes(b, self.max_tracks)
-            if m == 0 or m != b * self.max_tracks * _COAST.itemsize:
-                raise ValueError(f"mpn_pose_track_motion: {b} x {self.max_tracks} coasting rows are more than one launch takes")
-            n += m
-        return n
+        return self.row_offsets(b)[2]
 
     def launch(self, record, out, b, coast=None):
         """record: the uint8 device tensor mpn_pose_gather wrote for (b, max_boxes); out: uint8 device tensor of
@@ -267,10 +275,11 @@ class PoseTracker:
         `coast_offset(b)` (out is then a call's whole `out_bytes(b)`)."""
         self.check_batch(b)
         if self.motion is not None:
+            _, at, end = self.row_offsets(b)
             if coast is None:
-                coast = out[self.coast_offset(b):self.out_bytes(b)]
-            if coast.numel() < self.out_bytes(b) - self.coast_offset(b):
-                raise ValueError(f"launch: a motion= tracker writes {self.out_bytes(b) - self.coast_offset(b)} bytes of coasting "
+                coast = out[at:end]
+            if coast.numel() < end - at:
+                raise ValueError(f"launch: a motion= tracker writes {end - at} bytes of coasting "
                                  f"rows for {b} images (got room for {coast.numel()})")
             _lib.call("mpn_pose_track_motion", _lib.ptr(record), b, self.max_boxes, self.streams, self.max_tracks,
                       SIMILARITIES[self.similarity], int(self.assignment == 'optimal'), self.match_threshold, self.new_track_score,
@@ -296,8 +305,7 @@ class PoseTracker:
     def launch_all(self, record, out, b):
         """`launch` and, with smooth=, `launch_smooth` behind it: out is a uint8 device tensor of `out_bytes(b)`, the track rows
         first (then the smoothed rows, then the coasting rows of motion=)."""
-        n = self.track_bytes(b)
-        at = self.coast_offset(b)
+        n, at, _ = self.row_offsets(b)
         self.launch(record, out[:n], b, out[at:] if self.motion is not None else None)
         if self.smooth is not None:
             self.launch_smooth(record, out[:n], out[n:at], b)
@@ -306,37 +314,14 @@ class PoseTracker:
     def commit(self):
         """The last launch's state becomes the current one: one small device copy on the current stream (one more with smooth=,
         one more with motion=)."""
-        self.prev.copy_(self.next, non_blocking=True)
-        if self.motion is not None:
-            self.motion_prev.copy_(self.motion_next, non_blocking=True)
-        if self.smooth is not None:
-            self.smooth_prev.copy_(self.smooth_next, non_blocking=True)
+        for _, prev, nxt in self._pairs():
+            prev.copy_(nxt, non_blocking=True)
 
     def reset(self, stream=None):
         """Forget every track and start the ids at 1 again: of all streams, or of one."""
-        if stream is None:
-            self.prev.zero_()
-            self.next.zero_()
-            if self.smooth is not None:
-                self.smooth_prev.zero_()
-                self.smooth_next.zero_()
-            if self.motion is not None:
-                self.motion_prev.zero_()
-                self.motion_next.zero_()
-            return
-        if not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        at = int(stream) * self.stream_bytes
-        self.prev[at:at + self.stream_bytes].zero_()
-        self.next[at:at + self.stream_bytes].zero_()
-        if self.smooth is not None:
-            at = int(stream) * self.smooth_stream_bytes
-            self.smooth_prev[at:at + self.smooth_stream_bytes].zero_()
-            self.smooth_next[at:at + self.smooth_stream_bytes].zero_()
-        if self.motion is not None:
-            at = int(stream) * self.motion_stream_bytes
-            self.motion_prev[at:at + self.motion_stream_bytes].zero_()
-            self.motion_next[at:at + self.motion_stream_bytes].zero_()
+        for _, prev, nxt in self._pairs(stream):
+            prev.zero_()
+            nxt.zero_()
 
     def unpack(self, out, counts):
         """A host copy of the output rows (uint8 array) and the record's per-image counts -> a list of dicts, one per image:
@@ -347,15 +332,14 @@ class PoseTracker:
         'coasting_ids' int32 [m], 'coasting_misses' int32 [m] (frames in a row without a detection, this one included),
         'coasting_boxes' f32 [m,4] and 'coasting_keypoints' f32 [m,17,2]: the image's tracks that are alive and were not detected
         in it, in slot order, at the pose predicted for this frame."""
-        slots = len(counts) * self.max_boxes
-        rows = np.frombuffer(out, np.uint8, slots * _OUT.itemsize).view(_OUT)
+        n, at, end = self.row_offsets(len(counts))
+        rows = np.frombuffer(out, np.uint8, n).view(_OUT)
         smooth = None
         if self.smooth is not None:
-            smooth = np.frombuffer(out, np.uint8, slots * _SMOOTH_OUT.itemsize, slots * _OUT.itemsize).view(_SMOOTH_OUT)
+            smooth = np.frombuffer(out, np.uint8, len(rows) * _SMOOTH_OUT.itemsize, n).view(_SMOOTH_OUT)
         coast = None
         if self.motion is not None:
-            coast = np.frombuffer(out, np.uint8, len(counts) * self.max_tracks * _COAST.itemsize,
-                                  self.coast_offset(len(counts))).view(_COAST).reshape(len(counts), self.max_tracks)
+            coast = np.frombuffer(out, np.uint8, end - at, at).view(_COAST).reshape(len(counts), self.max_tracks)
         res, s = [], 0
         for i, n in enumerate(counts):
             r = rows[s:s + int(n)]
@@ -380,28 +364,23 @@ class PoseTracker:
         box's ymin, xmin, ymax, xmax, normalised, and of the keypoint centroid's x, y in pixels), 'seen' int32 [m] (the matches
         a track's velocity has taken in) and 'boxes_predicted' f32 [m,4], 'keypoints_predicted' f32 [m,17,2]: where the next
         frame's detections are compared with, computed here from the copied state in the kernel's float32 steps."""
-        if not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        at = int(stream) * self.stream_bytes
-        raw = self.prev[at:at + self.stream_bytes].cpu().numpy()
-        head = raw[:_HEAD.itemsize].view(_HEAD)[0]
-        slots = raw[_HEAD.itemsize:].view(_SLOT)
+        host = {}                                                   # per pair: the stream's head and its slots
+        for (prefix, _, _, head, slot, _), prev, _ in self._pairs(stream):
+            raw = prev.cpu().numpy()
+            host[prefix] = raw[:head.itemsize].view(head)[0], raw[head.itemsize:].view(slot)
+        head, slots = host['']
         live = np.nonzero(slots['id'] != 0)[0]
         s = slots[live]
         res = {'next_id': max(int(head['next_id']), 1), 'dropped': int(head['dropped']), 'slots': live,
                'ids': s['id'].copy(), 'hits': s['hits'].copy(), 'age': s['age'].copy(), 'misses': s['misses'].copy(),
                'boxes': s['box'].copy(), 'scores': s['score'].copy(), 'keypoints': s['keypoints'].copy()}
         if self.smooth is not None:
-            at = int(stream) * self.smooth_stream_bytes
-            raw = self.smooth_prev[at:at + self.smooth_stream_bytes].cpu().numpy()
-            joints = raw[_SMOOTH_HEAD.itemsize:].view(_SMOOTH_SLOT)['joints'][live]
-            res['frames'] = int(raw[:_SMOOTH_HEAD.itemsize].view(_SMOOTH_HEAD)[0]['frames'])
+            joints = host['smooth_'][1]['joints'][live]
+            res['frames'] = int(host['smooth_'][0]['frames'])
             res['keypoints_smoothed'] = joints['hat'][..., :2].copy()
             res['keypoint_last'] = joints['last'].copy()
         if self.motion is not None:
-            at = int(stream) * self.motion_stream_bytes
-            raw = self.motion_prev[at:at + self.motion_stream_bytes].cpu().numpy()
-            m = raw[_MOTION_HEAD.itemsize:].view(_MOTION_SLOT)[live]
+            m = host['motion_'][1][live]
             own = (m['id'] == s['id'])[:, None]                     # (as the launch reads a slot another track left)
             vel = np.where(own, m['vel'], np.float32(0)).astype(np.float32)
             gap = (s['misses'] + 1).astype(np.float32)[:, None]

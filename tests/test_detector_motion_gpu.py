@@ -92,6 +92,50 @@ def test_smooth_annotate_and_style_with_a_motion_tracker(det):
     assert COAST_KEYS <= set(plain) and 'annotated' in plain and 'keypoints_smoothed' not in plain
 
 
+def _value(v):
+    """A result value as something `==` compares byte for byte: arrays with dtype and shape, the tables of 'oks' key by key."""
+    if isinstance(v, dict):
+        return {k: _value(x) for k, x in v.items()}
+    if isinstance(v, bytes):
+        return v
+    v = np.asarray(v)
+    return v.dtype.str, v.shape, v.tobytes()
+
+
+def test_every_row_block_behind_one_record(det):
+    """One predict_images call over two frames of one camera with groundtruth=, annotate='jpeg', a tracker with smooth= and
+    motion= and a style that draws the smoothed keypoints: the OKS rows, the track rows, the smoothed rows and the coasting
+    rows (padded: 25 slots) all lie behind the one record, and the drawing reads two of the blocks in place. Every key equals,
+    byte for byte, the key of the call that switches on only the option it belongs to, with a fresh tracker of its own."""
+    from multiposenet_amd.inference import ConstantVelocity, OneEuro, PoseTracker, TrackStyle
+    from test_detector_oks_gpu import _groundtruth
+    style = TrackStyle(keypoints='smoothed')
+    frames = list(_images()[:2])
+
+    def call(tracked=False, **options):
+        if tracked:
+            options['track'] = PoseTracker(streams=1, max_tracks=MAX_TRACKS, smooth=OneEuro(), motion=ConstantVelocity())
+        return det.predict_images(frames, size=(H, W), score_threshold=0.0, **options)
+    plain = call()
+    gts = _groundtruth(plain, [(H, W)] * 2, 0.01, without=1)
+    assert len(gts[0]['keypoints']) >= 3
+    alone = {'oks': call(groundtruth=gts), 'annotated_jpeg': call(True, annotate='jpeg', track_style=style)}
+    tracked = call(True)
+    n0 = len(det._graphs)
+    got = call(True, groundtruth=gts, annotate='jpeg', track_style=style)
+    assert len(det._graphs) == n0 + 1
+    smooth_keys = {'keypoints_smoothed', 'keypoint_velocities'}
+    for i, o in enumerate(got):
+        assert set(o) == set(plain[i]) | {'oks', 'annotated_jpeg'} | TRACK_KEYS | smooth_keys | COAST_KEYS
+        _check_shapes(o)
+        for k, v in o.items():
+            want = plain[i] if k in plain[i] else alone[k][i] if k in alone else tracked[i]
+            assert _value(v) == _value(want[k]), f"image {i} {k}"
+    n = len(got[0]['boxes'])
+    np.testing.assert_array_equal(got[0]['track_ids'], np.arange(1, n + 1))      # the first frame starts a track per person
+    assert n >= 3 and got[0]['annotated_jpeg'][:2] == b"\xff\xd8" and (got[0]['oks']['matches'][:, 0, 0] >= 0).any()
+
+
 def test_a_plain_tracker_returns_no_new_key(det):
     from multiposenet_amd.inference import PoseTracker
     images = _images()
