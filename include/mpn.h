@@ -838,6 +838,52 @@ int mpn_oks_match(const void* record, int B, int max_boxes, const double* gt, co
                   mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Keypoint-similarity NMS of the record's persons: duplicate poses (two boxes on one person that box NMS kept apart) are
+ * dropped by their OKS with a better pose. A pure function from one record to another of the same layout, one block per image
+ * and one block that compacts; no atomics.
+ *
+ *   mpn_pose_nms   record_in: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place: of the header
+ *                     counts[B], each clamped to 0..max_boxes (the persons of image i are the rows behind the clamped counts
+ *                     of the images before it, in record order p = 0..n-1; total is not read), num_boxes[B] and the overflow
+ *                     word; of a row its score, keypoint_scores and keypoints.
+ *                   Semantics, in float64 in this order without contraction unless f32 is named. Per image:
+ *                     order score: score_mode 0 the row's box score; 1 box score * (sum of keypoint_scores in order / 17) in
+ *                     f32 (mpn_oks_match's score_mode). Persons are visited in descending order score, equal scores in record
+ *                     order; a NaN order score sorts behind every number, in record order.
+ *                     a_p = (max x - min x) * (max y - min y) of the row's 17 keypoints (min / max in f32, the differences and
+ *                     the product in f64). Similarity of p, q: the joints that count are those with keypoints[k][2] >=
+ *                     min_keypoint_score (f32 compare) in BOTH rows, m of them; m == 0: 0; else denom = (a_p + a_q) / 2 +
+ *                     2^-52, e_k = (dx^2 + dy^2) / vars[k] / denom / 2 with dx = (double)x_q - (double)x_p, dy likewise and
+ *                     mpn_oks_match's vars; the similarity is (sum of exp(-e_k) over the counting joints in k order) / m.
+ *                     It is symmetric; each unordered pair is computed once.
+ *                     Suppression: in visit order a person that is not suppressed is KEPT and suppresses every person behind
+ *                     it that is not yet suppressed and whose similarity with it is > (double)threshold (strict). A
+ *                     suppressed person suppresses nothing.
+ *                   record_out: record_bytes >= mpn_pose_gather_record_bytes(B, max_boxes) bytes DEVICE, the layout of
+ *                     record_in: total and counts[B] are the kept numbers, num_boxes[B] and overflow are copied through, the
+ *                     kept rows are byte copies of their input rows, dense, in record order (scores are not rewritten), every
+ *                     other row and the header's padding are zero. It must not overlap record_in.
+ *                   info: info_bytes >= mpn_pose_nms_info_bytes(B, max_boxes) bytes DEVICE: int32 suppressed[B] (the clamped
+ *                     count minus the kept number), zero words up to a multiple of 16 bytes; then one 8-byte row per record
+ *                     row, aligned with record_out's rows 0 .. total-1, every other row zero: int32 source (the person's index
+ *                     p among its image's persons in record_in), int32 absorbed (the persons this one suppressed); then the
+ *                     launch's workspace, 8 bytes per slot (image, p), p < max_boxes: int32 keep (1 / 0), int32 absorbed (0
+ *                     unless kept), both 0 for p >= n.
+ *                   sim_out (may be NULL): f64 [B, max_boxes, max_boxes] DEVICE, the similarity of persons p != q < n of each
+ *                     image; the diagonal and everything else zero.
+ *                   Checked before any HIP call, in this order: null record_in / record_out / info, score_mode not 0 / 1, a
+ *                     NaN threshold or min_keypoint_score (MPN_ERR_BAD_ARG); B, max_boxes >= 1, max_boxes <= 64 (a person's
+ *                     suppression set is one 64-bit mask), B * max_boxes <= 4096 (MPN_ERR_BAD_SHAPE); record_in == record_out
+ *                     or overlapping ranges (MPN_ERR_BAD_ARG); the records 16-byte, info and sim_out 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN); record_bytes, info_bytes (MPN_ERR_WORKSPACE). The grids depend on B alone: a
+ *                     captured launch serves any later record.
+ *   mpn_pose_nms_info_bytes   0 for arguments out of range.
+ */
+size_t mpn_pose_nms_info_bytes(int B, int max_boxes);
+int mpn_pose_nms(const void* record_in, int B, int max_boxes, float threshold, float min_keypoint_score, int score_mode,
+                 void* record_out, size_t record_bytes, void* info, size_t info_bytes, double* sim_out, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Person identities across the frames of a video: the record's persons of every frame are matched against the tracks the
  * earlier frames left, one block per stream: greedily (mpn_pose_track) or by the optimal assignment (mpn_pose_track_optimal).
  *

@@ -148,6 +148,8 @@ SIGNATURES = {
     "mpn_oks_gt_row_bytes": (_Z, []),
     "mpn_oks_match_out_bytes": (_Z, [_I, _I]),
     "mpn_oks_match": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "mpn_pose_nms_info_bytes": (_Z, [_I, _I]),
+    "mpn_pose_nms": (_I, [_P, _I, _I, _F, _F, _I, _P, _Z, _P, _Z, _P, _P]),
     "mpn_pose_track_state_bytes": (_Z, [_I, _I]),
     "mpn_pose_track_out_bytes": (_Z, [_I, _I]),
     "mpn_pose_track": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P]),

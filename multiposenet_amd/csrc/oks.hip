@@ -114,13 +114,7 @@ __global__ __launch_bounds__(kThreads) void oks_match_kernel(OksArgs a) {
     // phase 0
     for (int i = tid; i < n; i += kThreads) {
         const float* row = a.rows + (size_t)(first + i) * kRowWords;
-        float s = row[kOffScore];
-        if (a.score_mode == 1) {
-            float m = 0.f;
-            for (int k = 0; k < kK; ++k) m += row[kOffKScore + k];
-            s = s * (m / 17.0f);
-        }
-        score[i] = s;
+        score[i] = order_score(row[kOffScore], row + kOffKScore, a.score_mode);
         area[i] = keypoint_extent_area(row + kOffKeypoints);
     }
     __syncthreads();

@@ -23,6 +23,15 @@ __device__ __forceinline__ double oks_term(double dx, double dy, int k, double d
     return exp(-e);
 }
 
+// The score a record row's detection is ordered by (mpn_oks_match's and mpn_pose_nms's score_mode), in f32: 0 the box score;
+// 1 the box score * (sum of the row's 17 keypoint_scores in order / 17)
+__device__ __forceinline__ float order_score(float box_score, const float* keypoint_scores, int score_mode) {
+    if (score_mode != 1) return box_score;
+    float m = 0.f;
+    for (int k = 0; k < kOksKeypoints; ++k) m += keypoint_scores[k];
+    return box_score * (m / 17.0f);
+}
+
 // (max x - min x) * (max y - min y) of keypoints[17][3] = (x, y, score): min / max in f32, the differences and the product in f64
 // (kStride = 2: of keypoints[17][2] = (x, y))
 template <int kStride = 3>

@@ -4,6 +4,7 @@
         [--model keypoints.npz] [--detector detector.npz] [--prn prn.npz] [--dtype bf16|f32]
         [--batch 16] [--size W H] [--keep-aspect-ratio] [--score-threshold 0.05] [--score box|box*keypoints] [--out FILE]
         [--flip] [--scales W H [W H ...]]
+        [--pose-nms [THRESHOLD]] [--pose-nms-min-keypoint-score X] [--pose-nms-score box|box*keypoints]
 
 --val-dataset: TFRecord shards of the keypoint contract (input_pipeline/tfrecord.py; tools/make_toy_tfrecords.py writes toy
 ones). Their JPEG bytes go through `Detector.predict_jpegs`, their persons become the ground truth
@@ -11,7 +12,9 @@ ones). Their JPEG bytes go through `Detector.predict_jpegs`, their persons becom
 --annotations / --images: COCO's person_keypoints_*.json and the directory of its JPEG files; COCO's own areas and crowds.
 The matching runs inside the Detector's captured graph (`groundtruth=`); the ten numbers are printed and appended to --out
 as one JSON line. --flip and --scales are the Detector's test-time augmentation (`flip=`, `scales=`): heatmaps averaged on the
-device over the mirror image and over further input sizes of --size's aspect ratio. Without a model file the weights are seeded random ones: the numbers then only show that the path runs."""
+device over the mirror image and over further input sizes of --size's aspect ratio. --pose-nms drops duplicate poses in front
+of the matching (`pose_nms=`, an `inference.PoseNms`: keypoint-similarity NMS inside the same graph; alone it uses the class's
+default threshold, which is not tuned). Without a model file the weights are seeded random ones: the numbers then only show that the path runs."""
 import argparse
 import json
 import os
@@ -69,7 +72,10 @@ def main(argv=None):
     ap.add_argument("--out", default="pose_eval.jsonl")
     ap.add_argument("--flip", action="store_true", help="average the heatmaps with those of the mirror image")
     ap.add_argument("--scales", type=int, nargs="+", default=[], metavar="N", help="further network input sizes: W H [W H ...]")
+    from . import pose_nms
+    pose_nms.add_arguments(ap)
     args = ap.parse_args(argv)
+    nms = pose_nms.from_arguments(ap, args)
     if bool(args.val_dataset) == bool(args.annotations):
         ap.error("give --val-dataset DIR, or --annotations JSON with --images DIR")
     if args.annotations and not args.images:
@@ -98,7 +104,8 @@ def main(argv=None):
     images = persons = 0
     for jpegs, gts in batches:
         outs = det.predict_jpegs(jpegs, size=(args.size[1], args.size[0]), keep_aspect_ratio=args.keep_aspect_ratio,
-                                 score_threshold=args.score_threshold, groundtruth=gts, flip=args.flip, scales=scales)
+                                 score_threshold=args.score_threshold, groundtruth=gts, flip=args.flip, scales=scales,
+                                 pose_nms=nms)
         evaluator.update(outs, gts)
         images += len(jpegs)
         persons += sum(len(o["scores"]) for o in outs)
@@ -110,6 +117,8 @@ def main(argv=None):
     line = dict(stats, images=images, detections=persons, groundtruth=int(evaluator.num_groundtruth[0]), dtype=args.dtype,
                 size=list(args.size), keep_aspect_ratio=args.keep_aspect_ratio, score_threshold=args.score_threshold, score=args.score,
                 flip=args.flip, scales=[list(s) for s in scales])
+    if nms is not None:
+        line["pose_nms"] = {"threshold": nms.threshold, "min_keypoint_score": nms.min_keypoint_score, "score": nms.score}
     with open(args.out, "a") as f:
         f.write(json.dumps(line) + "\n")
     print(json.dumps(line))

@@ -4,3 +4,4 @@ from .draw import TrackStyle  # noqa: F401
 from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401
 from .maps import MapPlotter, plot_maps  # noqa: F401
 from ..tracking import PoseTracker, OneEuro, ConstantVelocity  # noqa: F401
+from ..pose_nms import PoseNms, PoseSuppressor, pose_nms  # noqa: F401

@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib
 from .. import pose_metrics
+from .. import pose_nms as pose_nms_stage
 from ..net import KeypointNet
 from . import draw, jpeg, maps, resample, tta
 
@@ -139,11 +140,11 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps."""
+    return_heatmaps; the PoseNms of pose_nms= or None."""
     __slots__ = ()
 
     @property
@@ -161,17 +162,23 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
         key += self.oks + self.tta
         if self.track is not None:
             key += ('track', self.track.serial, b)
-        return key + self.style
+        key += self.style
+        if self.pose_nms is not None:
+            key += ('pose_nms', self.pose_nms)
+        return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None):
-    """The bytes a call brings to the host in one copy, as three slices: mpn_pose_gather's record; behind it the rows of
-    mpn_oks_match (oks: the entry's pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's
-    tracking.PoseTracker, which lays out its own rows: `row_offsets`). A part that is not there is empty; a record of 0 bytes:
-    more slots than mpn_pose_gather packs."""
+def record_layout(b, max_boxes, oks=None, track=None, nms=None):
+    """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
+    filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
+    pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
+    rows: `row_offsets`); behind that, at the next multiple of 16 bytes, mpn_pose_nms's info block (nms: the entry's
+    pose_nms.PoseNmsBuffers). A part that is not there is empty; a record of 0 bytes: more slots than mpn_pose_gather packs."""
     record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
     rows = record + (oks.out_bytes if oks is not None else 0)
-    return slice(0, record), slice(record, rows), slice(rows, rows + (track.out_bytes(b) if track is not None else 0))
+    end = rows + (track.out_bytes(b) if track is not None else 0)
+    info = slice((end + 15) // 16 * 16, (end + 15) // 16 * 16 + nms.info_bytes) if nms is not None else slice(end, end)
+    return slice(0, record), slice(record, rows), slice(rows, end), info
 
 
 class _Entry:
@@ -180,10 +187,10 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -379,7 +386,8 @@ class Detector:
 
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
-                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None):
+                      jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
+                      pose_nms=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -436,13 +444,21 @@ class Detector:
                 keypoints='smoothed') the smoothed rows the graph has just produced: every tracked person's box, dots and an
                 id label in the colour of its track, untracked persons as before or hidden. The style is part of the
                 graph's key; its table goes to the device once, when the entry is made. None changes nothing.
+            pose_nms: None, or an inference.PoseNms (needs the detector and the PRN, max_boxes <= 64): keypoint-similarity NMS
+                of every image's persons. The gather writes its record to a device buffer of the entry that never leaves
+                the device; one mpn_pose_nms behind it inside the captured graph - a graph of its own per PoseNms - writes
+                the filtered record where the record lies otherwise, so that groundtruth=, track=, annotate= and the JPEG
+                encoder read the surviving persons with no change of their own. Every dict then holds only the survivors
+                and gains 'pose_nms_source' int32 [n] (a survivor's index among the image's persons before the stage),
+                'pose_nms_absorbed' int32 [n] (the persons it suppressed) and 'pose_nms_suppressed' (np.int32); they arrive
+                in the record's one copy. 'num_boxes' is still the count before the score filter. None changes nothing.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -466,7 +482,8 @@ class Detector:
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style. shape(): the method's own
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms (checked last; may be
+        absent: None). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
@@ -480,8 +497,22 @@ class Detector:
         tta_key = check_tta(given['flip'], given['scales'], h, w)
         if tta_key and not self._has_heatmaps():
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
+        nms = self._check_pose_nms(given.get('pose_nms'))
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps']), shaped
+                        given['return_heatmaps'], nms), shaped
+
+    def _check_pose_nms(self, nms):
+        """The `pose_nms` argument of the predict_* methods -> None or the PoseNms. Before any device work."""
+        if nms is None:
+            return None
+        if not isinstance(nms, pose_nms_stage.PoseNms):
+            raise ValueError("pose_nms must be None or an inference.PoseNms")
+        if self.retinanet is None:
+            raise ValueError("pose_nms= needs the person detector (detector_path): without it no persons are detected")
+        if self.assigner is None:
+            raise ValueError("pose_nms= compares keypoints, which need the PRN (prn_path)")
+        pose_nms_stage.check_max_boxes(self.params['max_boxes'])
+        return nms
 
     def _check_groundtruth(self, groundtruth, b):
         """The `groundtruth` argument of the predict_* methods -> () or the tail of the entry's key."""
@@ -548,7 +579,7 @@ class Detector:
         if 'record' in outs:
             record = host['record'].numpy()
             persons = unpack_record(record, b, self.params['max_boxes'], self.assigner is not None)
-            _, oks_rows, track_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track)
+            _, oks_rows, track_rows, nms_info = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms)
             counts = record[4:4 + 4 * b].view(np.int32)
             if ent.oks is not None:                                 # the match rows lie behind the record: they came with it
                 for p, table in zip(persons, ent.oks.unpack(record[oks_rows], counts)):
@@ -556,6 +587,9 @@ class Detector:
             if ent.track is not None:                               # the track rows lie behind those: the same copy
                 for p, ids in zip(persons, ent.track.unpack(record[track_rows], counts)):
                     p.update(ids)
+            if ent.nms is not None:                                 # mpn_pose_nms's info block lies behind those: the same copy
+                for p, extra in zip(persons, ent.nms.unpack(record[nms_info], counts)):
+                    p.update(extra)
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -579,7 +613,7 @@ class Detector:
         device input for shape = (b, h, w) (with the mirrors behind the batch and the inputs of the extra scales for flip /
         scales) and what each option needs: the drawing's buffers, sized for sources of capacity[0] bytes; the JPEG encoder,
         which reserves capacity[1:]; the MapPlotter; the ground-truth buffers; the tracker; the style with its table, which
-        goes to the device once, here. fixed_frames (predict_batch): the frames are the batch itself, so the drawing and
+        goes to the device once, here; the mpn_pose_nms stage with its buffer for the unfiltered record. fixed_frames (predict_batch): the frames are the batch itself, so the drawing and
         encode descriptors are placed here, for good, and the encoder reserves what their plan needs."""
         b, h, w = shape
         key = base + opts.tail(b)
@@ -609,6 +643,8 @@ class Detector:
         if opts.oks:
             ent.oks = pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, dev, opts.oks[1], opts.oks[2])
         ent.track = opts.track
+        if opts.pose_nms is not None:
+            ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
         if opts.style:
             ent.style = opts.style[1], torch.from_numpy(opts.style[1].tables().copy()).to(dev)
         store[key] = ent
@@ -631,6 +667,9 @@ class Detector:
         with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
         ent.style ((TrackStyle, its table on the device), with draw and track): the drawing is mpn_draw_tracks, which reads
         those rows in place.
+        ent.nms (a pose_nms.PoseNmsBuffers): the gather writes to its buffer, which stays on the device, and mpn_pose_nms writes
+        the filtered record where the record lies otherwise: every launch above reads that one. Its info block lies behind the
+        tracker's rows. Pure, like the tracker's launches.
         ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -666,12 +705,13 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        in_record, oks_rows, track_rows = record_layout(b, max_boxes, ent.oks, track)
+        in_record, oks_rows, track_rows, nms_info = record_layout(b, max_boxes, ent.oks, track, ent.nms)
         nbytes = in_record.stop
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        whole = torch.empty(track_rows.stop, dtype=torch.uint8, device=net.device)
-        record = whole[in_record]
+        whole = torch.empty(nms_info.stop, dtype=torch.uint8, device=net.device)
+        filtered = whole[in_record]
+        record = ent.nms.raw if ent.nms is not None else filtered    # what the gather writes
         if extent is None:
             _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
                       _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold), h, w, _lib.ptr(record), nbytes,
@@ -680,6 +720,8 @@ class Detector:
             _lib.call("mpn_pose_gather_sized", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']),
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
+        if ent.nms is not None:                                     # every launch below reads the filtered record
+            record = ent.nms.launch(filtered, whole[nms_info])
         if ent.oks is not None:
             ent.oks.launch(record, whole[oks_rows])
         if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
@@ -720,7 +762,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -747,6 +789,7 @@ class Detector:
             track: as for `predict_batch`; the tracker sees the boxes normalised to the source images and the keypoints in
                 source pixels, as they are returned.
             track_style: as for `predict_batch`; the identities are drawn on the SOURCE frames.
+            pose_nms: as for `predict_batch`; the similarity is that of the keypoints in source pixels, as they are returned.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -759,7 +802,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style)
+            track=track, track_style=track_style, pose_nms=pose_nms)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -772,7 +815,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None, flip=False, scales=None, track=None, track_style=None):
+                      groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -789,7 +832,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales, track, track_style: as for `predict_images`.
+            flip, scales, track, track_style, pose_nms: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -808,7 +851,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style)
+            track=track, track_style=track_style, pose_nms=pose_nms)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):

@@ -6,6 +6,7 @@
         [--score-threshold 0.05] [--smooth [--fps 30] [--min-cutoff 1.0] [--beta 0.007] [--d-cutoff 1.0]
         [--min-keypoint-score 0.0]]
         [--motion [--velocity-gain 0.5] [--damping 1.0]]
+        [--pose-nms [THRESHOLD]] [--pose-nms-min-keypoint-score X] [--pose-nms-score box|box*keypoints]
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
@@ -21,7 +22,8 @@ line; beta multiplies a speed in frame pixels and so depends on the resolution. 
 against where the tracks are expected (`tracking.ConstantVelocity`: a velocity per track, --velocity-gain the weight of a new
 observation of it, --damping its decay per frame without a detection) and adds "coasting_ids", "coasting_boxes" and
 "coasting_keypoints" (x, y) to every line: the tracks that are alive but were not detected in the frame, at their predicted
-pose. --frames-out DIR also writes every frame as
+pose. --pose-nms drops duplicate poses in front of the tracker (`pose_nms=`, an `inference.PoseNms`: keypoint-similarity NMS
+inside the same graph; alone it uses the class's default threshold, which is not tuned). --frames-out DIR also writes every frame as
 DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in a colour per track (`inference.TrackStyle`;
 --draw-smoothed draws the smoothed keypoints, --hide-untracked leaves persons without an id out) - drawn and JPEG-encoded on
 the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
@@ -83,9 +85,12 @@ def main(argv=None):
     ap.add_argument("--label-size", type=int, default=10, help="font size of the id labels (--frames-out)")
     ap.add_argument("--draw-smoothed", action="store_true", help="draw the smoothed keypoints (--frames-out, needs --smooth)")
     ap.add_argument("--hide-untracked", action="store_true", help="leave persons without an id out of the frames (--frames-out)")
+    from . import pose_nms
+    pose_nms.add_arguments(ap)
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
+    nms = pose_nms.from_arguments(ap, args)
     motion = None
     if args.motion:
         from .tracking import ConstantVelocity
@@ -138,10 +143,11 @@ def main(argv=None):
                 with open(os.path.join(args.images, name), "rb") as f:
                     files.append(f.read())
             if all(_is_jpeg(data) for data in files):
-                outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, **draw)
+                outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, pose_nms=nms,
+                                        **draw)
             else:
                 outs = det.predict_images([_pixels(data) for data in files], size=size, score_threshold=args.score_threshold,
-                                          track=tracker, **draw)
+                                          track=tracker, pose_nms=nms, **draw)
             for name, o in zip(batch, outs):
                 line = {"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
                         "keypoints": o["keypoints"].tolist()}
@@ -166,6 +172,8 @@ def main(argv=None):
                              "min_keypoint_score": smooth.min_keypoint_score}
     if motion is not None:
         summary["motion"] = {"velocity_gain": motion.velocity_gain, "damping": motion.damping}
+    if nms is not None:
+        summary["pose_nms"] = {"threshold": nms.threshold, "min_keypoint_score": nms.min_keypoint_score, "score": nms.score}
     print(json.dumps(summary))
     return state
 
