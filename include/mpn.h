@@ -1098,6 +1098,75 @@ int mpn_pose_smooth(const void* record, const void* track_rows, int B, int max_b
                     void* next, void* out, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Tracking accuracy: a frame's tracked persons against annotated persons that carry identities, by the CLEAR MOT mapping rule
+ * (Bernardin & Stiefelhagen 2008) under keypoint OKS, one block per stream. What MOTA, MOTP and IDF1 are accumulated from.
+ *
+ *   mpn_track_eval   record: what mpn_pose_gather[_sized] wrote for (B, max_boxes), DEVICE, read in place exactly as
+ *                     mpn_pose_track reads it (the header's total and counts, clamped the same way; only rows 0 .. total-1;
+ *                     of a row only keypoints[17][3]).
+ *                   track_rows: the `out` of mpn_pose_track for the same record, DEVICE; of a row only int32 track_id is read.
+ *                     A row with id 0 is UNTRACKED: it takes no part below and is only counted.
+ *                   gt f64 [B, max_gt, 64], gt_counts int32 [B] DEVICE: mpn_oks_match's rows, unchanged (a count above max_gt
+ *                     reads max_gt rows); of a row the keypoints, bbox, area and the ignore flag are read.
+ *                   gt_identity int32 [B, max_gt] DEVICE: the person's dense identity index within its stream. A value outside
+ *                     0 .. max_identities-1 means the row has NO MEMORY: its stored id reads as 0 and nothing is stored.
+ *                   Streams: B = streams * F, stream s owns images s*F .. s*F+F-1 in time order, as in mpn_pose_track.
+ *                   PURE, as mpn_pose_track and for the same reason: the launch reads prev and writes the COMPLETE new state
+ *                     to next and the rows to out; it never writes prev, and running it twice in a row gives the same bytes.
+ *                     The caller advances the state by copying next over prev. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   State, prev and next, mpn_track_eval_state_bytes(streams, max_identities) bytes DEVICE, per stream in
+ *                     32-bit words: int32 frames (the frames evaluated), three zero words; then max_identities int32: the
+ *                     track id the identity was last matched to, 0 = never. An all-zero state is the valid empty state.
+ *                   Similarity s(g, h) of ground-truth row g and record row h: mpn_oks_match's f64 OKS (the v > 0 keypoints
+ *                     of the ground truth, or the distance to its doubled box when it has none; the ground truth's own area),
+ *                     without contraction. The pair is ELIGIBLE when h is tracked and s >= threshold; a NaN never is.
+ *                   Per frame, in this order; `stored(g)` is the state's value for g's identity as the stream's earlier frames
+ *                     left it (0 without memory):
+ *                     1. kept correspondences: the ground truths that are not ignored, in row order: if stored(g) != 0 and a
+ *                        tracked row h of the frame has track_id == stored(g), (g, h) is eligible and h is not yet taken, g
+ *                        is matched to h (flag "kept"; of several such rows the lowest).
+ *                     2. the ground truths that are neither ignored nor kept and the tracked rows that are not taken are
+ *                        matched by the maximum-weight matching of their eligible pairs: weight w = q + 1 + 2^27 with q =
+ *                        floor(s * 2^20) clamped to 0 .. 2^20 (mpn_pose_track_optimal's quantum). 64 quanta sum to less than
+ *                        2^27, so a matching with more pairs outweighs any with fewer, and among those of equal size the
+ *                        larger sum of quanta wins. The algorithm is the one stated under mpn_pose_track_optimal, word for
+ *                        word, with rows i = 1..ng ALL the image's ground truths in row order (an ignored or kept one has
+ *                        no eligible pair and lands on its dummy at delta 0, which moves no potential: leaving such rows
+ *                        out, as the kernel does, changes nothing), columns j = 1..n the image's record rows,
+ *                        j = n+1..n+ng the dummies, cost(i, j) = -w where eligible.
+ *                     3. a tracked row that is unmatched and has an eligible pair with any ignored ground truth is IGNORED.
+ *                     4. a matched ground truth whose stored id is non-zero and differs from the matched track_id is a
+ *                        SWITCH; every matched ground truth with memory stores its track_id (in row order: of two rows with
+ *                        one identity index the later); an unmatched ground truth that is not ignored is a MISS; a tracked
+ *                        row that is neither matched nor ignored is a FALSE POSITIVE.
+ *                   out: out_bytes >= mpn_track_eval_out_bytes(B, max_boxes, max_gt) DEVICE, three tables one behind the other:
+ *                     B frame rows of 48 bytes: int32 num_gt (not ignored), num_hyp (tracked and not ignored), matches
+ *                       (switches included), switches, misses, false_positives, ignored_hyp, untracked; f64 the sum of the
+ *                       matched pairs' unquantised s, added in ground-truth row order from 0.0; 8 bytes of zero.
+ *                     B * max_gt ground-truth rows of 32 bytes, row (image, g); rows g >= the image's count are zero: int32
+ *                       the matched track_id (0 = none), int32 the matched row's index among the image's persons (-1 =
+ *                       none), int32 flags (bit 0 matched, bit 1 switch, bit 2 kept, bit 3 ignored), int32 stored(g) before
+ *                       the frame, f64 s of the match (0 = none), uint64 overlap mask: bit p set when person p of the image
+ *                       is tracked and (g, p) is eligible (for ignored rows too).
+ *                     B * max_boxes rows of 8 bytes aligned with the record's rows 0 .. total-1, every other row zero: int32
+ *                       the matched ground truth's index in its image or -1; int32 flags (bit 0 false positive, bit 1
+ *                       ignored, bit 2 untracked).
+ *                   Checked before any HIP call, the messages begin "track_eval:": null pointers (MPN_ERR_BAD_ARG);
+ *                     streams >= 1, B % streams == 0, 1 <= max_boxes <= 64, B * max_boxes <= 4096, 1 <= max_gt <= 64,
+ *                     1 <= max_identities <= 1024 (MPN_ERR_BAD_SHAPE); a NaN threshold (MPN_ERR_BAD_ARG); record 16-byte,
+ *                     track_rows / gt / prev / next / out 8-byte, gt_counts / gt_identity 4-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN); prev == next (MPN_ERR_BAD_ARG); state_bytes and out_bytes (MPN_ERR_WORKSPACE). The
+ *                     grid depends on streams alone: a captured launch serves any later record, ground truth and state.
+ *   mpn_track_eval_state_bytes   streams * (16 + 4 * max_identities); 0 for arguments out of range.
+ *   mpn_track_eval_out_bytes     B * (48 + 32 * max_gt + 8 * max_boxes); 0 for arguments out of range.
+ */
+size_t mpn_track_eval_state_bytes(int streams, int max_identities);
+size_t mpn_track_eval_out_bytes(int B, int max_boxes, int max_gt);
+int mpn_track_eval(const void* record, const void* track_rows, int B, int max_boxes, int streams, const double* gt,
+                   const int* gt_counts, const int* gt_identity, int max_gt, int max_identities, double threshold,
+                   const void* prev, void* next, size_t state_bytes, void* out, size_t out_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

@@ -160,6 +160,9 @@ SIGNATURES = {
     "mpn_pose_smooth_state_bytes": (_Z, [_I, _I]),
     "mpn_pose_smooth_out_bytes": (_Z, [_I, _I]),
     "mpn_pose_smooth": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "mpn_track_eval_state_bytes": (_Z, [_I, _I]),
+    "mpn_track_eval_out_bytes": (_Z, [_I, _I, _I]),
+    "mpn_track_eval": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _D, _P, _P, _Z, _P, _Z, _P]),
     "mpn_coco_masks_image_desc_bytes": (_Z, []),
     "mpn_coco_masks_part_desc_bytes": (_Z, []),
     "mpn_coco_masks_plane_words": (_Z, [_I, _I]),

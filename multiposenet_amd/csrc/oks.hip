@@ -19,7 +19,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kK = kOksKeypoints;
 constexpr int kMaxGt = 64;              // the matched set of a lane is one 64-bit mask
 constexpr int kMaxDets = 20;            // rows of the OKS matrix in LDS
 constexpr int kMaxT = 10;               // thresholds a row has room for
@@ -28,8 +27,6 @@ constexpr int kMaxBoxes = 256;          // detections of one image (LDS tables o
 constexpr int kMaxRows = 4096;          // mpn_pose_gather's own limit on B * max_boxes
 // the record's row (pose_gather.hip), in 32-bit words
 constexpr int kRowWords = 108, kOffScore = 5, kOffKScore = 6, kOffKeypoints = 57;
-// a ground-truth row, in doubles: keypoints[17][3] (x, y, v), bbox (x, y, w, h), area, ignore, iscrowd, padding
-constexpr int kGtDoubles = 64, kGtBox = 51, kGtArea = 55, kGtIgnore = 56, kGtCrowd = 57;
 // an output row, in bytes: int32 rank, f32 score, f64 area, int32 match[3][10], uint32 ignore[3], 4 bytes of padding
 constexpr int kOutBytes = 152, kOutMatch = 16, kOutIgnore = kOutMatch + 4 * kRanges * kMaxT;
 static_assert(kOutIgnore + 4 * kRanges + 4 == kOutBytes && kOutBytes % 8 == 0, "output row layout");
@@ -50,30 +47,6 @@ struct OksArgs {
     double* oks_out;
     int B, max_boxes, max_gt, num_thresholds, score_mode, max_dets;
 };
-
-// computeOks for one (detection, ground truth): kp = the record row's keypoints[17][3] (f32), g = the ground-truth row
-__device__ double oks_of(const float* kp, const double* g) {
-    int k1 = 0;
-    for (int k = 0; k < kK; ++k) k1 += g[3 * k + 2] > 0.0;
-    const double bx = g[kGtBox], by = g[kGtBox + 1], bw = g[kGtBox + 2], bh = g[kGtBox + 3];
-    const double x0 = bx - bw, x1 = bx + bw * 2, y0 = by - bh, y1 = by + bh * 2;
-    const double denom = g[kGtArea] + kEps;
-    double sum = 0.0;
-    for (int k = 0; k < kK; ++k) {
-        const double xd = (double)kp[3 * k], yd = (double)kp[3 * k + 1];
-        double dx, dy;
-        if (k1 > 0) {
-            if (!(g[3 * k + 2] > 0.0)) continue;
-            dx = xd - g[3 * k];
-            dy = yd - g[3 * k + 1];
-        } else {
-            dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1);
-            dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
-        }
-        sum += oks_term(dx, dy, k, denom);
-    }
-    return sum / (double)(k1 > 0 ? k1 : kK);
-}
 
 __global__ __launch_bounds__(kThreads) void oks_match_kernel(OksArgs a) {
     __shared__ double oks[kMaxDets][kMaxGt];

@@ -1,5 +1,5 @@
-// The arithmetic of object keypoint similarity that oks.hip (detections against ground truth) and pose_track.hip (detections
-// against the tracks of the previous frames) share: COCO's per-keypoint variances, one keypoint's exp term and the area of a
+// The arithmetic of object keypoint similarity that oks.hip and track_eval.hip (detections against ground truth) and
+// pose_track.hip (detections against the tracks of the previous frames) share: COCO's per-keypoint variances, one keypoint's exp term and the area of a
 // keypoint set's bounding box. IEEE float64 in COCOeval's order, contraction off; exp is the device library's (<= 1 ulp).
 #pragma once
 #include "common.h"
@@ -42,6 +42,34 @@ __device__ __forceinline__ double keypoint_extent_area(const float* kp) {
         yl = fminf(yl, kp[kStride * k + 1]); yh = fmaxf(yh, kp[kStride * k + 1]);
     }
     return ((double)xh - (double)xl) * ((double)yh - (double)yl);
+}
+
+// a ground-truth row of mpn_oks_match and mpn_track_eval, in doubles: keypoints[17][3] (x, y, v), bbox (x, y, w, h), area,
+// ignore, iscrowd, padding
+constexpr int kGtDoubles = 64, kGtBox = 51, kGtArea = 55, kGtIgnore = 56, kGtCrowd = 57;
+
+// computeOks for one (detection, ground truth): kp = the record row's keypoints[17][3] (f32), g = the ground-truth row
+__device__ inline double oks_of(const float* kp, const double* g) {
+    int k1 = 0;
+    for (int k = 0; k < kOksKeypoints; ++k) k1 += g[3 * k + 2] > 0.0;
+    const double bx = g[kGtBox], by = g[kGtBox + 1], bw = g[kGtBox + 2], bh = g[kGtBox + 3];
+    const double x0 = bx - bw, x1 = bx + bw * 2, y0 = by - bh, y1 = by + bh * 2;
+    const double denom = g[kGtArea] + kEps;
+    double sum = 0.0;
+    for (int k = 0; k < kOksKeypoints; ++k) {
+        const double xd = (double)kp[3 * k], yd = (double)kp[3 * k + 1];
+        double dx, dy;
+        if (k1 > 0) {
+            if (!(g[3 * k + 2] > 0.0)) continue;
+            dx = xd - g[3 * k];
+            dy = yd - g[3 * k + 1];
+        } else {
+            dx = fmax(0.0, x0 - xd) + fmax(0.0, xd - x1);
+            dy = fmax(0.0, y0 - yd) + fmax(0.0, yd - y1);
+        }
+        sum += oks_term(dx, dy, k, denom);
+    }
+    return sum / (double)(k1 > 0 ? k1 : kOksKeypoints);
 }
 
 }  // namespace

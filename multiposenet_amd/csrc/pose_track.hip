@@ -16,7 +16,7 @@
 //   phase C  greedy matching by wave 0, lane = track slot: every lane keeps the best open detection of its row (ties: the
 //            smaller detection), a 6-step xor butterfly takes the largest (ties: the smaller slot); a lane rescans its row
 //            only when the detection it held was taken. No barrier inside the rounds, at most min(tracks, detections) of them.
-//            (optimal: assign_optimal below, also wave 0 alone and without a barrier)
+//            (optimal: assign_optimal of hungarian.h, also wave 0 alone and without a barrier)
 //   phase D  hits / age / misses of the live tracks, tracks past max_misses freed (motion: the velocities of the matched slots
 //            updated from the detection and the pose it replaces, those of the others damped; the coasting slots ranked)
 //   phase E  births in row order into the lowest free slots: two ballots and popcounts, no serial walk
@@ -24,6 +24,7 @@
 //            the frame's coasting rows)
 // Latency-bound glue like mpn_oks_match (microseconds behind a network pass of milliseconds): not tuned beyond that.
 #include "common.h"
+#include "hungarian.h"
 #include "oks_math.h"
 
 #pragma clang fp contract(off)
@@ -143,88 +144,9 @@ __device__ __forceinline__ void assign_greedy(const double (*sim)[kMaxTracks], i
     }
 }
 
-// the weight of an eligible pair is quantum + 1: floor(s * 2^20) in f64 (the product is exact), clamped before the conversion
-constexpr double kQuanta = 1048576.0;
-__device__ __forceinline__ long long quantum_of(double s) {
-    double q = floor(s * kQuanta);
-    q = q < 0.0 ? 0.0 : (q > kQuanta ? kQuanta : q);
-    return (long long)q;
-}
-
-// Phase C of mpn_pose_track_optimal: the shortest-augmenting-path Hungarian method of include/mpn.h in 64-bit integers (a cost
-// is at most 2^20 + 1 in size; a delta is at most the reduced cost of the way to row i's own dummy, -u[i] - v[T + i], so the
-// potentials grow by a few costs per row: about 64 * 2^20 = 2^26 at 64 x 64, 36 bits short of the type). Wave 0; rows are the
-// detections 1..n, columns 1..T the slots, T+1..T+n the rows' dummies. Lane L owns column L + 1 (slot L; "A") and column
-// T + L + 1 (the dummy of row L + 1; "B") - their v, minv, way, used and p - and the potential u of row L + 1. What the
-// current column and row decide (j0, i0, delta, the tree's rows) is the same value in every lane: a value fetched from its
-// owner by a shuffle, or the outcome of the butterfly. No LDS is written, no barrier, no atomics. Every loop has a
-// compile-time bound: a row whose search or flip does not end within it ends the frame's matching with the rows before it
-// (which cannot happen: a search takes a new column into its tree in every trip and there are at most 128).
-constexpr int kMaxCols = kMaxTracks + kMaxBoxes;
-constexpr long long kAbsent = 1ll << 62;
-
-__device__ __forceinline__ void assign_optimal(const double (*sim)[kMaxTracks], int n, int T, int lane, bool live, double thr,
-                                               int& mine, double& mine_sim) {
-    const int jA = lane < T ? lane + 1 : -1, jB = T + lane + 1;
-    long long u = 0, vA = 0, vB = 0;
-    int pA = 0, pB = 0;
-    for (int i = 1; i <= kMaxBoxes; ++i) {
-        if (i > n) break;
-        long long minvA = kAbsent, minvB = kAbsent;
-        int wayA = 0, wayB = 0;
-        bool usedA = false, usedB = false, reached = false;
-        unsigned long long tree = 0ull;                   // the rows whose column is used (and row i, on column 0)
-        int j0 = 0, i0 = i;
-        for (int trip = 0; trip <= kMaxCols; ++trip) {
-            usedA = usedA || j0 == jA;
-            usedB = usedB || j0 == jB;
-            tree |= 1ull << (i0 - 1);
-            const long long u0 = __shfl(u, i0 - 1, 64);
-            if (live && !usedA) {
-                const double s = sim[i0 - 1][lane];
-                if (s >= thr) {                           // (a NaN is never eligible)
-                    const long long cur = -(quantum_of(s) + 1) - u0 - vA;
-                    if (cur < minvA) { minvA = cur; wayA = j0; }
-                }
-            }
-            if (lane == i0 - 1 && !usedB) {
-                const long long cur = -u0 - vB;
-                if (cur < minvB) { minvB = cur; wayB = j0; }
-            }
-            // delta = the smallest minv of the unused columns, ties to the smaller column (jA < jB within a lane)
-            long long delta = kAbsent;
-            int j1 = -1;
-            if (!usedA && minvA != kAbsent) { delta = minvA; j1 = jA; }
-            if (!usedB && minvB != kAbsent && (j1 < 0 || minvB < delta)) { delta = minvB; j1 = jB; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const long long v2 = __shfl_xor(delta, o, 64);
-                const int j2 = __shfl_xor(j1, o, 64);
-                if (j2 >= 0 && (j1 < 0 || v2 < delta || (v2 == delta && j2 < j1))) { delta = v2; j1 = j2; }
-            }
-            if (j1 < 0) break;                            // (row i's own dummy is always there; uniform)
-            if ((tree >> lane) & 1ull) u += delta;
-            if (usedA) vA -= delta; else if (minvA != kAbsent) minvA -= delta;
-            if (usedB) vB -= delta; else if (minvB != kAbsent) minvB -= delta;
-            j0 = j1;
-            const int rowA = __shfl(pA, (j0 - 1) & 63, 64), rowB = __shfl(pB, (j0 - T - 1) & 63, 64);
-            i0 = j0 <= T ? rowA : rowB;
-            if (i0 < 1 || i0 > n) { reached = i0 == 0; break; }
-        }
-        if (!reached) break;
-        for (int trip = 0; trip <= kMaxCols; ++trip) {    // the path back to column 0: every column takes the row before it
-            const int wA = __shfl(wayA, (j0 - 1) & 63, 64), wB = __shfl(wayB, (j0 - T - 1) & 63, 64);
-            const int j1 = j0 <= T ? wA : wB;
-            const int rowA = __shfl(pA, (j1 - 1) & 63, 64), rowB = __shfl(pB, (j1 - T - 1) & 63, 64);
-            const int row = j1 == 0 ? i : (j1 <= T ? rowA : rowB);
-            if (j0 == jA) pA = row;
-            if (j0 == jB) pB = row;
-            j0 = j1;
-            if (j0 <= 0) break;
-        }
-    }
-    if (live && pA >= 1 && pA <= n) { mine = pA - 1; mine_sim = sim[mine][lane]; }
-}
+// Phase C of mpn_pose_track_optimal: assign_optimal of hungarian.h with the weight quantum + 1 (no bias). Wave 0; rows are the
+// detections 1..n, columns 1..T the slots (lane = slot), T+1..T+n the rows' dummies.
+static_assert(kMaxTracks == kAssignSide && kMaxBoxes == kAssignSide, "one lane of the wave per slot and per detection");
 
 template <bool kOptimal, bool kMotion>
 __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
@@ -336,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void pose_track_kernel(TrackArgs a) {
             const double thr = (double)a.match_threshold;
             double mine_sim = 0.0;
             int mine = -1;
-            if (kOptimal) assign_optimal(sim, n, T, lane, live, thr, mine, mine_sim);
+            if (kOptimal) assign_optimal<0>(sim, n, T, lane, live, thr, mine, mine_sim);
             else assign_greedy(sim, n, t, live, thr, mine, mine_sim);
             if (live) {
                 if (mine >= 0) {

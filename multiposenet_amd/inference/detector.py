@@ -140,11 +140,11 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the PoseNms of pose_nms= or None."""
+    return_heatmaps; the TrackEvaluator of track_eval= or None; the PoseNms of pose_nms= or None (the last field, as ever)."""
     __slots__ = ()
 
     @property
@@ -165,20 +165,28 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
         key += self.style
         if self.pose_nms is not None:
             key += ('pose_nms', self.pose_nms)
+        if self.track_eval is not None:
+            key += ('track_eval', self.track_eval.serial)
         return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None, nms=None):
+def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None):
     """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
     filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
     pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
     rows: `row_offsets`); behind that, at the next multiple of 16 bytes, mpn_pose_nms's info block (nms: the entry's
-    pose_nms.PoseNmsBuffers). A part that is not there is empty; a record of 0 bytes: more slots than mpn_pose_gather packs."""
+    pose_nms.PoseNmsBuffers). A part that is not there is empty; a record of 0 bytes: more slots than mpn_pose_gather packs.
+    track_eval (the entry's track_metrics.TrackEvaluator): a fifth slice, mpn_track_eval's rows behind everything else at the
+    next multiple of 16 bytes; without it the four slices are returned, as ever."""
     record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
     rows = record + (oks.out_bytes if oks is not None else 0)
     end = rows + (track.out_bytes(b) if track is not None else 0)
     info = slice((end + 15) // 16 * 16, (end + 15) // 16 * 16 + nms.info_bytes) if nms is not None else slice(end, end)
-    return slice(0, record), slice(record, rows), slice(rows, end), info
+    parts = slice(0, record), slice(record, rows), slice(rows, end), info
+    if track_eval is None:
+        return parts
+    at = (info.stop + 15) // 16 * 16
+    return parts + (slice(at, at + track_eval.out_bytes(b)),)
 
 
 class _Entry:
@@ -187,10 +195,10 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -387,7 +395,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None):
+                      pose_nms=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -452,19 +460,30 @@ class Detector:
                 and gains 'pose_nms_source' int32 [n] (a survivor's index among the image's persons before the stage),
                 'pose_nms_absorbed' int32 [n] (the persons it suppressed) and 'pose_nms_suppressed' (np.int32); they arrive
                 in the record's one copy. 'num_boxes' is still the count before the score filter. None changes nothing.
+            track_eval: None, or a track_metrics.TrackEvaluator (needs track=, the PRN and a groundtruth= whose dicts carry
+                'track_ids'; the evaluator's streams and max_boxes are the tracker's, its max_gt 64): one mpn_track_eval launch
+                behind the tracker's inside the captured graph - a graph of its own per evaluator - scores the identities
+                against the annotated ones over the record the tracker read (the filtered one with pose_nms=). The ground-truth
+                rows are those groundtruth= placed; the identity indices go up in one more small copy; the rows lie behind
+                every other part of the result buffer and arrive in the record's one copy. The launch only reads the
+                evaluator's state; the call advances it once, beside the tracker's. Every dict gains 'track_eval'
+                (`TrackEvaluator.unpack`: the frame's counts, per ground truth the matched id, flags and similarity, per
+                person the matched ground truth and flags); `evaluator.collect(outputs)` feeds `evaluate()`. None changes nothing.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
                           (b * h * w * 3,), fixed_frames=True)
         if opts.oks:
             ent.oks.place(groundtruth)                              # ONE small host-to-device copy of the ground truth
+        if ent.track_eval is not None:                              # one more small copy: the identity indices
+            ent.track_eval.place(groundtruth, b, rows=False)
         if opts.jpeg and ent.encode_plan.quality != opts.jpeg[0]:   # the frames are fixed: only another quality needs new descriptors
             self._place_encode(ent, _encode_plan(*_batch_frames(b, h, w), opts.jpeg))
         stage = ent.stage.numpy()
@@ -477,12 +496,14 @@ class Detector:
         outs = self._run(ent, lambda: self._device_side_batch(ent, opts.thr))
         if ent.track is not None:
             ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
+        if ent.track_eval is not None:
+            ent.track_eval.commit()
         return self._finish(ent, outs, b, opts.return_heatmaps)
 
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms (checked last; may be
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval (checked last; may be
         absent: None). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
@@ -498,8 +519,38 @@ class Detector:
         if tta_key and not self._has_heatmaps():
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
         nms = self._check_pose_nms(given.get('pose_nms'))
+        evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], nms), shaped
+                        given['return_heatmaps'], evaluator, nms), shaped
+
+    def _check_track_eval(self, evaluator, track, groundtruth, b):
+        """The `track_eval` argument of the predict_* methods -> None or the TrackEvaluator. Before any device work (and
+        before the evaluator gives an identity a dense index)."""
+        if evaluator is None:
+            return None
+        from ..track_metrics import TrackEvaluator, groundtruth_track_ids
+        if not isinstance(evaluator, TrackEvaluator):
+            raise ValueError("track_eval must be None or a track_metrics.TrackEvaluator")
+        if track is None:
+            raise ValueError("track_eval= scores the tracker's identities: it needs track=, a tracking.PoseTracker")
+        if groundtruth is None:
+            raise ValueError("track_eval= needs groundtruth=, a list of dicts that carry 'track_ids'")
+        if self.assigner is None:
+            raise ValueError("track_eval= compares keypoints, which need the PRN (prn_path)")
+        for gt in groundtruth:
+            groundtruth_track_ids(gt, len(pose_metrics.groundtruth_arrays(gt)[0]))
+        if evaluator.streams != track.streams:
+            raise ValueError(f"track_eval=: the evaluator was made for {evaluator.streams} streams, the tracker for {track.streams}")
+        if evaluator.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"track_eval=: the evaluator was made for max_boxes = {evaluator.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if evaluator.max_gt != pose_metrics.MAX_GT:
+            raise ValueError(f"track_eval=: the Detector's ground-truth rows are {pose_metrics.MAX_GT} per image; make the "
+                             f"evaluator with max_gt = {pose_metrics.MAX_GT} (got {evaluator.max_gt})")
+        if torch.device(evaluator.device) != torch.device(self.net.device):
+            raise ValueError(f"track_eval=: the evaluator lives on {evaluator.device}, this Detector on {self.net.device}")
+        evaluator.out_bytes(b)
+        return evaluator
 
     def _check_pose_nms(self, nms):
         """The `pose_nms` argument of the predict_* methods -> None or the PoseNms. Before any device work."""
@@ -579,7 +630,7 @@ class Detector:
         if 'record' in outs:
             record = host['record'].numpy()
             persons = unpack_record(record, b, self.params['max_boxes'], self.assigner is not None)
-            _, oks_rows, track_rows, nms_info = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms)
+            _, oks_rows, track_rows, nms_info = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms)[:4]
             counts = record[4:4 + 4 * b].view(np.int32)
             if ent.oks is not None:                                 # the match rows lie behind the record: they came with it
                 for p, table in zip(persons, ent.oks.unpack(record[oks_rows], counts)):
@@ -590,6 +641,10 @@ class Detector:
             if ent.nms is not None:                                 # mpn_pose_nms's info block lies behind those: the same copy
                 for p, extra in zip(persons, ent.nms.unpack(record[nms_info], counts)):
                     p.update(extra)
+            if ent.track_eval is not None:                          # mpn_track_eval's rows lie behind everything: the same copy
+                eval_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval)[4]
+                for p, rows in zip(persons, ent.track_eval.unpack(record[eval_rows], counts)):
+                    p['track_eval'] = rows
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -643,6 +698,7 @@ class Detector:
         if opts.oks:
             ent.oks = pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, dev, opts.oks[1], opts.oks[2])
         ent.track = opts.track
+        ent.track_eval = opts.track_eval
         if opts.pose_nms is not None:
             ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
         if opts.style:
@@ -670,6 +726,9 @@ class Detector:
         ent.nms (a pose_nms.PoseNmsBuffers): the gather writes to its buffer, which stays on the device, and mpn_pose_nms writes
         the filtered record where the record lies otherwise: every launch above reads that one. Its info block lies behind the
         tracker's rows. Pure, like the tracker's launches.
+        ent.track_eval (a track_metrics.TrackEvaluator, with track and oks): mpn_track_eval follows the tracker's launches over the
+        record the tracker read, the tracker's rows and the ground truth ent.oks holds; its rows lie behind everything else.
+        Pure in the same way: the caller commits.
         ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -705,11 +764,12 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        in_record, oks_rows, track_rows, nms_info = record_layout(b, max_boxes, ent.oks, track, ent.nms)
+        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval)
+        in_record, oks_rows, track_rows, nms_info = layout[:4]
         nbytes = in_record.stop
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        whole = torch.empty(nms_info.stop, dtype=torch.uint8, device=net.device)
+        whole = torch.empty(layout[-1].stop, dtype=torch.uint8, device=net.device)
         filtered = whole[in_record]
         record = ent.nms.raw if ent.nms is not None else filtered    # what the gather writes
         if extent is None:
@@ -726,6 +786,9 @@ class Detector:
             ent.oks.launch(record, whole[oks_rows])
         if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
             track.launch_all(record, whole[track_rows], b)
+        if ent.track_eval is not None:                              # the record the tracker read, its rows, the ground truth in place
+            ent.track_eval.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[4]], b,
+                                  *ent.oks.device_groundtruth())
         dev['record'] = whole
         if annotate is not None and ent.style is not None:          # identities: mpn_draw_tracks on the rows just written
             style, table = ent.style
@@ -762,7 +825,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -790,6 +853,7 @@ class Detector:
                 source pixels, as they are returned.
             track_style: as for `predict_batch`; the identities are drawn on the SOURCE frames.
             pose_nms: as for `predict_batch`; the similarity is that of the keypoints in source pixels, as they are returned.
+            track_eval: as for `predict_batch`, with the ground truth in the pixels of the SOURCE images.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -802,7 +866,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -815,7 +879,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None):
+                      groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -832,7 +896,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales, track, track_style, pose_nms: as for `predict_images`.
+            flip, scales, track, track_style, pose_nms, track_eval: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -851,7 +915,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -881,9 +945,13 @@ class Detector:
             self._place_encode(ent, eplan)
         if opts.oks:
             ent.oks.place(groundtruth)
+        if ent.track_eval is not None:
+            ent.track_eval.place(groundtruth, len(groundtruth), rows=False)
         outs = self._run(ent, lambda: self._device_side_images(ent, opts.thr))
         if ent.track is not None:
             ent.track.commit()                                      # as in predict_batch: once per call, outside the graph
+        if ent.track_eval is not None:
+            ent.track_eval.commit()
         persons = self._finish(ent, outs, b, opts.return_heatmaps)
         if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):

@@ -184,6 +184,11 @@ class OksBuffers:
         pack_groundtruth(groundtruth, self._rows, self._counts)
         self.dev.copy_(self.stage, non_blocking=True)
 
+    def device_groundtruth(self):
+        """The device tensors `place` fills: (rows f64 [b, max_gt, 64] flat, counts int32 [b] as the words behind them) - what
+        mpn_track_eval reads beside mpn_oks_match."""
+        return self.dev[self._at[1]:], self.dev[self._at[2]:]
+
     def launch(self, record, out, oks_out=None):
         """record: the uint8 device tensor mpn_pose_gather wrote; out: uint8 device tensor of `out_bytes`; oks_out: float64
         device tensor [b * max_boxes, max_gt] or None."""

@@ -8,6 +8,7 @@
         [--motion [--velocity-gain 0.5] [--damping 1.0]]
         [--pose-nms [THRESHOLD]] [--pose-nms-min-keypoint-score X] [--pose-nms-score box|box*keypoints]
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
+        [--annotations JSON [--eval-threshold 0.5]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -26,7 +27,11 @@ pose. --pose-nms drops duplicate poses in front of the tracker (`pose_nms=`, an 
 inside the same graph; alone it uses the class's default threshold, which is not tuned). --frames-out DIR also writes every frame as
 DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in a colour per track (`inference.TrackStyle`;
 --draw-smoothed draws the smoothed keypoints, --hide-untracked leaves persons without an id out) - drawn and JPEG-encoded on
-the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. --annotations JSON (a
+COCO-style file whose annotations carry `track_id`, PoseTrack's layout; frames are found by the base name of `file_name`, a frame
+the file does not name has no annotated person) scores the identities while it tracks (`track_eval=`, a
+`track_metrics.TrackEvaluator`: one more launch in the same graph; a pair can correspond at OKS >= --eval-threshold) and adds
+MOTA, MOTP, IDF1 and the counts behind them to the summary as "track_eval". Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -85,6 +90,8 @@ def main(argv=None):
     ap.add_argument("--label-size", type=int, default=10, help="font size of the id labels (--frames-out)")
     ap.add_argument("--draw-smoothed", action="store_true", help="draw the smoothed keypoints (--frames-out, needs --smooth)")
     ap.add_argument("--hide-untracked", action="store_true", help="leave persons without an id out of the frames (--frames-out)")
+    ap.add_argument("--annotations", metavar="JSON", help="PoseTrack-style annotations: evaluate the tracks (MOTA, IDF1) while tracking")
+    ap.add_argument("--eval-threshold", type=float, default=0.5, help="OKS at which a person can correspond to an annotation (--annotations)")
     from . import pose_nms
     pose_nms.add_arguments(ap)
     args = ap.parse_args(argv)
@@ -134,6 +141,12 @@ def main(argv=None):
                           max_misses=args.max_misses, new_track_score=args.new_track_score, max_boxes=det.params['max_boxes'],
                           smooth=smooth, motion=motion, assignment=args.assignment)
     size = (args.size[1], args.size[0])
+    evaluator, annotated = None, {}
+    if args.annotations is not None:
+        from .track_metrics import TrackEvaluator, groundtruth_from_posetrack
+        annotated = {os.path.basename(name): gt for name, gt in groundtruth_from_posetrack(args.annotations)}
+        evaluator = TrackEvaluator(streams=1, threshold=args.eval_threshold, max_boxes=det.params['max_boxes'])
+    nobody = {'keypoints': np.zeros((0, 17, 3)), 'boxes': np.zeros((0, 4)), 'track_ids': np.zeros(0, np.int64)}
     frames = persons = 0
     with open(args.out, "w") as out:
         for at in range(0, len(names), args.batch):
@@ -142,12 +155,17 @@ def main(argv=None):
             for name in batch:
                 with open(os.path.join(args.images, name), "rb") as f:
                     files.append(f.read())
+            scored = {}
+            if evaluator is not None:
+                scored = dict(groundtruth=[annotated.get(name, nobody) for name in batch], track_eval=evaluator)
             if all(_is_jpeg(data) for data in files):
                 outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, pose_nms=nms,
-                                        **draw)
+                                        **draw, **scored)
             else:
                 outs = det.predict_images([_pixels(data) for data in files], size=size, score_threshold=args.score_threshold,
-                                          track=tracker, pose_nms=nms, **draw)
+                                          track=tracker, pose_nms=nms, **draw, **scored)
+            if evaluator is not None:
+                evaluator.collect(outs)
             for name, o in zip(batch, outs):
                 line = {"name": name, "ids": o["track_ids"].tolist(), "boxes": o["boxes"].tolist(),
                         "keypoints": o["keypoints"].tolist()}
@@ -174,6 +192,8 @@ def main(argv=None):
         summary["motion"] = {"velocity_gain": motion.velocity_gain, "damping": motion.damping}
     if nms is not None:
         summary["pose_nms"] = {"threshold": nms.threshold, "min_keypoint_score": nms.min_keypoint_score, "score": nms.score}
+    if evaluator is not None:
+        summary["track_eval"] = dict(evaluator.evaluate(), threshold=evaluator.threshold, annotations=args.annotations)
     print(json.dumps(summary))
     return state
 
