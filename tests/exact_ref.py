@@ -36,9 +36,9 @@ def int_affine(rs, C):
     return scale, shift
 
 
-def int_activations(rs, shape, scale):
-    """x in [-X_MAX, X_MAX], doubled on the channels whose scale is 0.5: x * scale + shift is an integer on every channel."""
-    x = int_tensor(rs, shape, -X_MAX, X_MAX)
+def int_activations(rs, shape, scale, x_max=X_MAX):
+    """x in [-x_max, x_max], doubled on the channels whose scale is 0.5: x * scale + shift is an integer on every channel."""
+    x = int_tensor(rs, shape, -x_max, x_max)
     return x * torch.where(scale == 0.5, 2.0, 1.0)
 
 
@@ -399,8 +399,14 @@ def gemm_case_data(M, N, K):
     return {"a": a, "b": b, "want": gemm_nt_ref(a, b), "headroom": exact_headroom(gemm_nt_ref, a, b)}
 
 
-BN_M = [777, 4096, 50000]
+BN_M = [777, 4096, 50000, 300001]     # 300 001 rows: mpn_bn_stats_num_parts is at its 2048 blocks, 147 rows per block (> 128)
 BN_C = [8, 24, 64, 1024]
+BN_MAX_ELEMENTS = 64 << 20           # 300 001 x 1024 would be 1.2 GB per f32 tensor (the 2048-block grid does not depend on C)
+BN_MC = [(M, C) for M in BN_M for C in BN_C if M * C <= BN_MAX_ELEMENTS]
+# |x| <= 8 (16 where the scale is 0.5) puts sum x^2 of a doubled channel at about 96 M = 28.8 M > 2^24 for M = 300 001. With
+# |x| <= 4 (8) for that M the generated data has sum x^2 <= 8.1 M and sum |g| |xhat| / 0.5 <= 13.3 M < 2^24 = 16.8 M
+# (tests/test_reduction_exact_host.py asserts it); x * scale + shift still spans [-7, 7]: 0.55 of it <= 0, 0.1 of it >= 6
+BN_X_MAX = {300001: 4}
 
 
 @lru_cache(maxsize=2)
@@ -408,7 +414,7 @@ def bn_case_data(M, C, act):
     """Integer mean in [-2, 2], invstd in {0.5, 1, 2}: xhat is a multiple of 0.5 and so is every product g * xhat."""
     rs = _rs("bn", M, C, act)
     scale, shift = int_affine(rs, C)
-    x = int_activations(rs, (M, C), scale)
+    x = int_activations(rs, (M, C), scale, BN_X_MAX.get(M, X_MAX))
     dA = int_tensor(rs, (M, C), -DY_MAX, DY_MAX)
     mean = int_tensor(rs, (C,), -2, 2)
     invstd = torch.from_numpy(rs.choice(np.array([0.5, 1.0, 2.0], np.float32), size=C))

@@ -194,6 +194,16 @@ def test_depthwise_table_has_single_and_multiple_slabs():
         assert all(n > 0 for n in counts) and min(counts) == 1 and max(counts) > 8, counts
 
 
+def test_batch_norm_table_reaches_blocks_of_more_than_128_rows():
+    """The largest row count is past the cap of the slab grid (2048 blocks of 128 rows): a block then walks more rows."""
+    lib = _lib.lib()
+    M = max(E.BN_M)
+    parts = lib.mpn_bn_stats_num_parts(M)
+    assert parts == 2048 and -(-M // parts) > 128
+    assert all(lib.mpn_bn_stats_num_parts(m) < 2048 for m in E.BN_M if m != M)
+    assert {C for m, C in E.BN_MC if m == M} == {8, 24, 64}          # 16-, 32-byte and odd (6 / 3 vectors) rows
+
+
 # --------------------------------------------------------------------------------------------------------------- headroom
 def test_headroom_below_2_pow_24_everywhere():
     worst = {}
@@ -217,9 +227,8 @@ def test_headroom_below_2_pow_24_everywhere():
         worst[("head", M)] = E.head_case_data(M, 64)["headroom"]
     for g in E.GEMM_CASES:
         worst[("gemm", g)] = E.gemm_case_data(*g)["headroom"]
-    for M in E.BN_M:
-        for C in E.BN_C:
-            worst[("bn", M, C)] = E.bn_case_data(M, C, 2)["headroom"]
+    for M, C in E.BN_MC:
+        worst[("bn", M, C)] = max(E.bn_case_data(M, C, act)["headroom"] for act in ((1, 2) if M in E.BN_X_MAX else (2,)))
     over = {k: v for k, v in worst.items() if not v < E.EXACT_LIMIT}
     assert not over, over
     assert max(worst.values()) > 2 ** 20        # ... and the largest cases are large: not far below the limit either

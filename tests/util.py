@@ -68,7 +68,8 @@ def assert_close(got, want, dtype, k=1, scale=None):
         scale = float(want.abs().max()) or 1.0
     err = (got - want).abs()
     bound = atol * scale + rtol * want.abs()
-    bad = err > bound
+    bad = ~(err <= bound)           # (not `err > bound`: a NaN - an element no thread wrote - is outside every tolerance)
+    err = torch.nan_to_num(err, nan=float("inf"))
     assert not bool(bad.any()), (
         f"max err {float(err.max()):.3e} (scale {scale:.3e}, {int(bad.sum())}/{bad.numel()} outside tol) "
         f"at {np.unravel_index(int(err.argmax()), tuple(err.shape))}")
