@@ -1384,6 +1384,81 @@ int mpn_draw_tracks(const uint8_t* sources, size_t sources_bytes, const void* de
                     size_t workspace_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Persons made unrecognisable: per KEPT person of mpn_pose_gather[_sized]'s record a region of its frame - the head, from the
+ * five face joints, or the box - is pixelated, blurred or filled. out_rgb = the packed RGB sources with those regions
+ * replaced; a pixel no region covers is a copy of the source. The definition is this project's own (NOT Pillow's reduce or
+ * GaussianBlur, which round differently); tests/anonymize_ref.py restates it as plain loops.
+ *
+ * All floating-point work is IEEE float64 on values widened from the record's float32, in the order written, no contraction;
+ * h, w are the descriptor's.
+ *   box      (by0, bx0, by1, bx1) = (box[0]*h, box[1]*w, box[2]*h, box[3]*w)
+ *   bounds   region 1 (box):  (fx0, fy0, fx1, fy1) = (bx0, by0, bx1, by1)
+ *            region 0 (head): F = the joints j in 0..4 (nose, eyes, ears) with with_keypoints != 0 and the row's
+ *                             keypoints[j][2] >= min_keypoint_score (float32 compare; a NaN score is not in F).
+ *                 F not empty: cx, cy = the sum of the x (y) of F in joint order, from 0.0, divided by |F|;
+ *                              e = 0.0, then per joint of F in order: d = |x_j - cx|, if d > e: e = d; the same with |y_j - cy|;
+ *                              s = e*scale; t = (by1 - by0)*min_size; if t > s: s = t;
+ *                              bounds cx - s, cy - s, cx + s, cy + s
+ *                 F empty:     bx0, by0, bx1, by0 + (by1 - by0)*fallback
+ *            A person with a non-finite bound has no region.
+ *   region   every bound clamped to +-2^20; x0 = floor(fx0), y0 = floor(fy0), x1 = ceil(fx1), y1 = ceil(fy1);
+ *            [x0, x1) x [y0, y1) half-open; a = x1 - x0, b = y1 - y0; a <= 0 or b <= 0: no region.
+ *   covered  frame pixel (x, y) lies in the rectangle and, for shape 0 (ellipse) with a, b <= 32768,
+ *            u*u*b*b + v*v*a*a <= a*a*b*b in int64, u = 2x + 1 - (x0 + x1), v = 2y + 1 - (y0 + y1) (62 bits). A larger
+ *            region is a rectangle.
+ *   colour   of a covered pixel: that of the LAST person of its image, in record order, that covers it; that person reads the
+ *            ORIGINAL sources, never another region's output.
+ *              mode 2 (fill)      color
+ *              mode 0 (pixelate)  c = ceil(max(a, b) / blocks); cell (i, j) = ((x - x0) / c, (y - y0) / c); per channel
+ *                                 (2*S + n) / (2*n) (integer division), S and n the sum and the count of the source pixels of
+ *                                 [x0 + i*c, x0 + (i+1)*c) x [y0 + j*c, y0 + (j+1)*c) inside the frame (clipped to the
+ *                                 frame, not to the region or the ellipse; n >= 1)
+ *              mode 1 (blur)      the frame after three passes, each a horizontal box mean then a vertical one of radius
+ *                                 `radius`, n = 2*radius + 1 samples, sample indices clamped to the frame (every pass
+ *                                 replicates its own edge), each 1-D mean (2*S + n) / (2*n) per channel, stored as uint8
+ *                                 before the next
+ *
+ *   sources, descs   as for mpn_draw_detections: src_offset (no alignment needed), h, w are read; out_offset is not
+ *   record      as for mpn_draw_detections (with mpn_pose_nms: the filtered one): the header's total and counts and the
+ *               rows' image_index, box and keypoints are read; a row whose image_index is not the image the header's counts
+ *               give it has no region
+ *   params      HOST, read at call time
+ *   out_rgb     out_bytes; image b's uint8 [h, w, 3] at byte src_offset, as in sources: every byte of every valid frame is
+ *               written. mpn_draw_detections / mpn_draw_tracks take it as their `sources` with the same descriptors.
+ *   workspace   mpn_anonymize_workspace_bytes(B, max_boxes) bytes (0 for arguments out of range), 16-byte aligned
+ * An image whose descriptor reaches outside sources_bytes / out_bytes, or has h, w outside what mpn_draw_detections accepts,
+ * is left unwritten: no descriptor makes a kernel read outside sources or write outside out_rgb.
+ * Launches: the regions (a thread per row), a streaming copy of the frames, for pixelate the cell means (a wave per region
+ * and cell), then a block per (row, tile of its region), which writes a covered pixel only where no later row of the image
+ * covers it: one writer per pixel behind the copy, no scatter, no atomics on global memory - the output is a function of
+ * (sources, descs, record, params), and launching twice gives the same bytes. Mosaic means and blur are computed only where a
+ * region lies. Grid and block sizes depend on (B, max_boxes, params) alone.
+ * Checked before any HIP call: null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535, 1 <= max_boxes <= MPN_DRAW_MAX_BOXES,
+ * B*max_boxes <= 4096 (MPN_ERR_BAD_SHAPE); descs, record, workspace 16-byte aligned (MPN_ERR_BAD_ALIGN); record_bytes,
+ * workspace_bytes, sources_bytes >= 3, out_bytes >= 3 (MPN_ERR_WORKSPACE); every parameter's range (MPN_ERR_BAD_ARG).
+ */
+#define MPN_ANONYMIZE_MAX_BLOCKS 32
+#define MPN_ANONYMIZE_MAX_RADIUS 12
+typedef struct mpn_anonymize_params {
+    int32_t region;                             /* 0 head, 1 box */
+    int32_t mode;                               /* 0 pixelate, 1 blur, 2 fill */
+    int32_t shape;                              /* 0 ellipse, 1 rectangle */
+    int32_t blocks;                             /* 2..MPN_ANONYMIZE_MAX_BLOCKS */
+    int32_t radius;                             /* 1..MPN_ANONYMIZE_MAX_RADIUS */
+    int32_t color;                              /* R | G << 8 | B << 16 */
+    float min_keypoint_score;                   /* finite */
+    int32_t reserved;
+    double scale;                               /* finite, > 0 */
+    double min_size;                            /* finite, >= 0 */
+    double fallback;                            /* in (0, 1] */
+} mpn_anonymize_params;
+size_t mpn_anonymize_params_bytes(void);
+size_t mpn_anonymize_workspace_bytes(int B, int max_boxes);
+int mpn_anonymize(const uint8_t* sources, size_t sources_bytes, const void* descs, const void* record, size_t record_bytes,
+                  int B, int max_boxes, int with_keypoints, const mpn_anonymize_params* params, uint8_t* out_rgb,
+                  size_t out_bytes, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Heatmap and mask overlays: `plot_maps` of the reference's inference/predict.ipynb (the cells under "Show heatmaps") for
  * a batch of B frames of one size, equal byte for byte to what Pillow and matplotlib make there. With h = H / 2, w = W / 2
  * (integer division), panel j of frame b is rows j*h .. j*h + h - 1 of out_rgba[b]: the frame resized to (w, h) with

@@ -178,6 +178,9 @@ SIGNATURES = {
     "mpn_draw_tracks_tables_bytes": (_Z, [_I, _I, _I]),
     "mpn_draw_tracks_workspace_bytes": (_Z, [_I, _I]),
     "mpn_draw_tracks": (_I, [_P, _Z, _P, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _Z, _P]),
+    "mpn_anonymize_params_bytes": (_Z, []),
+    "mpn_anonymize_workspace_bytes": (_Z, [_I, _I]),
+    "mpn_anonymize": (_I, [_P, _Z, _P, _P, _Z, _I, _I, _I, _P, _P, _Z, _P, _Z, _P]),
     "mpn_plot_maps_desc_bytes": (_Z, []),
     "mpn_plot_maps_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "mpn_plot_maps": (_I, [_P, _P, _P, _P, _P, _Z, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),

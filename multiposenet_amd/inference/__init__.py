@@ -1,6 +1,7 @@
 from .utils import get_keypoints, get_keypoints_batch, KeypointDecoder, draw_everything, draw_tracks  # noqa: F401
 from .detector import Detector  # noqa: F401
 from .draw import TrackStyle  # noqa: F401
+from .anonymize_stage import Anonymize, Anonymizer, anonymize  # noqa: F401
 from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401
 from .maps import MapPlotter, plot_maps  # noqa: F401
 from ..tracking import PoseTracker, OneEuro, ConstantVelocity  # noqa: F401

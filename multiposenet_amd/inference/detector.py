@@ -16,6 +16,7 @@ from .. import _lib
 from .. import pose_metrics
 from .. import pose_nms as pose_nms_stage
 from ..net import KeypointNet
+from . import anonymize_stage
 from . import draw, jpeg, maps, resample, tta
 
 # create_pb.py:31-36: the thresholds frozen into the graph
@@ -140,11 +141,12 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the TrackEvaluator of track_eval= or None; the PoseNms of pose_nms= or None (the last field, as ever)."""
+    return_heatmaps; the TrackEvaluator of track_eval= or None; the Anonymize of anonymize= or None; the PoseNms of pose_nms= or
+    None (the last field, as ever)."""
     __slots__ = ()
 
     @property
@@ -167,6 +169,8 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
             key += ('pose_nms', self.pose_nms)
         if self.track_eval is not None:
             key += ('track_eval', self.track_eval.serial)
+        if self.anonymize is not None:
+            key += ('anonymize', self.anonymize)
         return key
 
 
@@ -195,10 +199,11 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the mpn_anonymize stage of an
+    `anonymize=` entry (an anonymize_stage.Anonymizer: it holds the anonymised frames the drawing reads), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -395,7 +400,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None, track_eval=None):
+                      pose_nms=None, anonymize=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -469,13 +474,22 @@ class Detector:
                 evaluator's state; the call advances it once, beside the tracker's. Every dict gains 'track_eval'
                 (`TrackEvaluator.unpack`: the frame's counts, per ground truth the matched id, flags and similarity, per
                 person the matched ground truth and flags); `evaluator.collect(outputs)` feeds `evaluate()`. None changes nothing.
+            anonymize: None, or an inference.Anonymize (needs annotate=True or 'jpeg' and the detector; max_boxes <= 128): every
+                kept person is made unrecognisable in the frame `annotate` shows - its head, from the record's face joints, or
+                its box, pixelated, blurred or filled. One mpn_anonymize behind the gather (behind mpn_pose_nms: on the
+                survivors) inside the captured graph - a graph of its own per Anonymize - writes the anonymised frames to a
+                buffer of the entry; the drawing takes that buffer as its sources, so boxes, skeletons and identities lie over
+                the mosaic ('annotated', 'annotated_jpeg'). With overlay=False nothing is drawn: the anonymised frame alone,
+                alpha 255 (not with track_style). Without the PRN every person takes the fallback region. Every other key is
+                unchanged; `plot_maps` and the returned heatmaps still show the network's input, NOT the anonymised frame.
+                None changes nothing.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -503,8 +517,8 @@ class Detector:
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval (checked last; may be
-        absent: None). shape(): the method's own
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, anonymize (the
+        last three may be absent: None; anonymize is checked last). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
@@ -520,8 +534,23 @@ class Detector:
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
         nms = self._check_pose_nms(given.get('pose_nms'))
         evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
+        spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], evaluator, nms), shaped
+                        given['return_heatmaps'], evaluator, spec, nms), shaped
+
+    def _check_anonymize(self, spec, annotate, track_style):
+        """The `anonymize` argument of the predict_* methods -> None or the Anonymize. Before any device work."""
+        if spec is None:
+            return None
+        anonymize_stage.check_spec(spec)
+        if not annotate:
+            raise ValueError("anonymize= changes the frame annotate shows: it needs annotate=True or 'jpeg'")
+        if not spec.overlay and track_style is not None:
+            raise ValueError("anonymize: overlay=False draws nothing over the anonymised frame; track_style= says how to draw")
+        if self.retinanet is None:
+            raise ValueError("anonymize= needs the person detector (detector_path): without it no persons are detected")
+        anonymize_stage.check_max_boxes(self.params['max_boxes'])
+        return spec
 
     def _check_track_eval(self, evaluator, track, groundtruth, b):
         """The `track_eval` argument of the predict_* methods -> None or the TrackEvaluator. Before any device work (and
@@ -687,6 +716,10 @@ class Detector:
             ent.draw = draw.Buffers(b, self.params['max_boxes'], capacity[0], dev)
             if fixed_frames:
                 ent.draw.place(*_batch_frames(b, h, w))
+        if opts.anonymize is not None:                              # its output is a buffer like the sources
+            ent.anonymize = anonymize_stage.Anonymizer(b, self.params['max_boxes'], capacity[0], dev, opts.anonymize)
+            if fixed_frames:
+                ent.anonymize.place(*_batch_frames(b, h, w))
         if opts.jpeg:                                               # the frames lie where the drawing writes them
             plan = _encode_plan(*_batch_frames(b, h, w), opts.jpeg) if fixed_frames else None
             ent.encode = jpeg.JpegBatchEncoder(dev)
@@ -723,6 +756,9 @@ class Detector:
         with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
         ent.style ((TrackStyle, its table on the device), with draw and track): the drawing is mpn_draw_tracks, which reads
         those rows in place.
+        ent.anonymize (an anonymize_stage.Anonymizer whose descriptors are in place, with draw): mpn_anonymize follows everything that
+        writes rows, reads the record the drawing reads and `frames`, and writes its own buffer, which the drawing then takes as
+        its sources; with overlay=False the drawing gets the empty record. Pure: launching it twice gives the same bytes.
         ent.nms (a pose_nms.PoseNmsBuffers): the gather writes to its buffer, which stays on the device, and mpn_pose_nms writes
         the filtered record where the record lies otherwise: every launch above reads that one. Its info block lies behind the
         tracker's rows. Pure, like the tracker's launches.
@@ -790,6 +826,11 @@ class Detector:
             ent.track_eval.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[4]], b,
                                   *ent.oks.device_groundtruth())
         dev['record'] = whole
+        drawn = record
+        if ent.anonymize is not None:                               # the drawing reads the anonymised frames in place of the sources
+            frames = ent.anonymize.launch(frames, record, self.assigner is not None)
+            if not ent.anonymize.spec.overlay:
+                drawn = None                                        # (draw.Buffers.no_record: the frames with alpha 255)
         if annotate is not None and ent.style is not None:          # identities: mpn_draw_tracks on the rows just written
             style, table = ent.style
             rows = whole[track_rows]
@@ -797,7 +838,7 @@ class Detector:
             smoothed = rows[n:] if style.keypoints == 'smoothed' else None
             dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, table, self.assigner is not None)
         elif annotate is not None:
-            dev['annotated'] = annotate.launch(frames, record, self.assigner is not None)
+            dev['annotated'] = annotate.launch(frames, drawn, drawn is not None and self.assigner is not None)
         return self._encode_frames(dev, ent.encode)
 
     def _keypoint_pass(self, x):
@@ -825,7 +866,7 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, track_eval=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -854,6 +895,8 @@ class Detector:
             track_style: as for `predict_batch`; the identities are drawn on the SOURCE frames.
             pose_nms: as for `predict_batch`; the similarity is that of the keypoints in source pixels, as they are returned.
             track_eval: as for `predict_batch`, with the ground truth in the pixels of the SOURCE images.
+            anonymize: as for `predict_batch`; the SOURCE frames are anonymised at their own size. `plot_maps` and the heatmaps
+                still show the network's input.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -866,7 +909,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -879,7 +922,8 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames as JPEG bytes: on-device decode
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
-                      groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, track_eval=None):
+                      groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None,
+                      track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -896,7 +940,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales, track, track_style, pose_nms, track_eval: as for `predict_images`.
+            flip, scales, track, track_style, pose_nms, track_eval, anonymize: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -915,7 +959,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -941,6 +985,8 @@ class Detector:
         put_sources(ent)
         if opts.annotate:
             ent.draw.place(plan.sizes, plan.src_offsets)
+        if ent.anonymize is not None:
+            ent.anonymize.place(plan.sizes, plan.src_offsets)
         if eplan:
             self._place_encode(ent, eplan)
         if opts.oks:

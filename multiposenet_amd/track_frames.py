@@ -8,6 +8,8 @@
         [--motion [--velocity-gain 0.5] [--damping 1.0]]
         [--pose-nms [THRESHOLD]] [--pose-nms-min-keypoint-score X] [--pose-nms-score box|box*keypoints]
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
+        [--anonymize [head|box] [--anonymize-mode pixelate|blur|fill] [--anonymize-shape ellipse|rectangle] [--anonymize-blocks 8]
+        [--anonymize-radius 8] [--anonymize-no-overlay]]
         [--annotations JSON [--eval-threshold 0.5]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
@@ -27,7 +29,10 @@ pose. --pose-nms drops duplicate poses in front of the tracker (`pose_nms=`, an 
 inside the same graph; alone it uses the class's default threshold, which is not tuned). --frames-out DIR also writes every frame as
 DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in a colour per track (`inference.TrackStyle`;
 --draw-smoothed draws the smoothed keypoints, --hide-untracked leaves persons without an id out) - drawn and JPEG-encoded on
-the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. --annotations JSON (a
+the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. --anonymize (with
+--frames-out) makes every detected person unrecognisable in those frames first (`anonymize=`, an `inference.Anonymize`: one more
+stage in the same graph; the head by default, or the whole box; --anonymize-no-overlay writes the anonymised frames without
+boxes, skeletons and ids; the class's defaults are not tuned). --annotations JSON (a
 COCO-style file whose annotations carry `track_id`, PoseTrack's layout; frames are found by the base name of `file_name`, a frame
 the file does not name has no annotated person) scores the identities while it tracks (`track_eval=`, a
 `track_metrics.TrackEvaluator`: one more launch in the same graph; a pair can correspond at OKS >= --eval-threshold) and adds
@@ -93,11 +98,16 @@ def main(argv=None):
     ap.add_argument("--annotations", metavar="JSON", help="PoseTrack-style annotations: evaluate the tracks (MOTA, IDF1) while tracking")
     ap.add_argument("--eval-threshold", type=float, default=0.5, help="OKS at which a person can correspond to an annotation (--annotations)")
     from . import pose_nms
+    from .inference import anonymize_stage
     pose_nms.add_arguments(ap)
+    anonymize_stage.add_arguments(ap)
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
     nms = pose_nms.from_arguments(ap, args)
+    anon = anonymize_stage.from_arguments(ap, args)
+    if anon is not None and args.frames_out is None:
+        ap.error("--anonymize changes the frames --frames-out writes: it needs --frames-out DIR")
     motion = None
     if args.motion:
         from .tracking import ConstantVelocity
@@ -131,6 +141,10 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         draw = dict(annotate="jpeg", jpeg_quality=args.jpeg_quality, track_style=style)
+        if anon is not None:
+            draw["anonymize"] = anon
+            if not anon.overlay:
+                draw["track_style"] = None                          # nothing is drawn over the anonymised frames
         os.makedirs(args.frames_out, exist_ok=True)
     if args.detector is None or args.prn is None:
         print("[track_frames] no --detector / --prn file: seeded random weights, the tracks mean nothing")
