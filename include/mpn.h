@@ -1167,6 +1167,91 @@ int mpn_track_eval(const void* record, const void* track_rows, int B, int max_bo
                    const void* prev, void* next, size_t state_bytes, void* out, size_t out_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Zones and counting lines: which persons stand inside which polygon, who entered and who left (debounced), how long each stayed,
+ * and who crossed a line in which direction, per tracked identity, with cumulative counters. One block per stream.
+ * tests/zones_ref.py is this definition as plain loops.
+ *
+ *   mpn_zone_events   record: what mpn_pose_gather[_sized] or mpn_pose_nms wrote for (B, max_boxes), DEVICE, read in place
+ *                     exactly as mpn_pose_smooth reads it (the header's total and counts, clamped the same way; only rows
+ *                     0 .. total-1; of a row only its box (ymin, xmin, ymax, xmax, normalised), its score and
+ *                     keypoints[17][3] = (x, y, score) in pixels).
+ *                   track_rows: the `out` of mpn_pose_track* for the same record, DEVICE; of a row only int32 track_id is
+ *                     read. The tracker's slot is NOT used: the stage keeps its own table keyed by id, so that ids from any
+ *                     tracker serve.
+ *                   Streams: B = streams * F, stream s owns images s*F .. s*F+F-1 in time order, as in mpn_pose_track.
+ *                   PURE, as mpn_pose_smooth and for the same reason: the launch reads prev and writes the COMPLETE new state
+ *                     to next and the rows to out; it never writes prev, and running it twice in a row gives the same bytes.
+ *                     The caller advances the state by copying next over prev. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   table: mpn_zone_table_bytes() = 4712 bytes DEVICE, built by the host once: int32 num_zones (0..16),
+ *                     num_lines (0..16), min_frames (1..255), anchor (0 feet, 2 box_centre, anything else box_bottom); at byte
+ *                     16 f64 height, width, min_keypoint_score; at byte 40 int32 vertex_count[16] (3..16); at byte 104 f64
+ *                     vertices[16][16][2] as (x, y) in the pixels of the keypoints; at byte 4200 f64 lines[16][2][2], (P, Q) as
+ *                     (x, y). The launcher cannot read device memory: the kernel CLAMPS every count into its range, so a bad
+ *                     table gives wrong answers and indexes nothing out of range; range checks are the caller's.
+ *                   Every operation below is one IEEE f64 operation in the order written, without contraction; f32 inputs are
+ *                     widened first.
+ *                   Anchor C of a row. feet: the ankles are joints 15 and 16; one PASSES when score >= min_keypoint_score (a
+ *                     NaN never does). Both pass: ((x15 + x16) * 0.5, (y15 + y16) * 0.5); one passes: its (x, y); neither:
+ *                     box_bottom. box_bottom: ((xmin + xmax) * 0.5 * width, ymax * height). box_centre: ((xmin + xmax) * 0.5 *
+ *                     width, (ymin + ymax) * 0.5 * height). A row whose anchor has a non-finite coordinate HAS NO ANCHOR: its
+ *                     output row is zero but for flag bit 2, it takes no slot and touches no state.
+ *                   inside(z, C), the crossing number without a division: over the edges (x1, y1) -> (x2, y2) of zone z, the
+ *                     one from its last vertex to its first included: an edge counts only if (y1 > Cy) != (y2 > Cy); then
+ *                     t = (x2 - x1) * (Cy - y1) - (Cx - x1) * (y2 - y1), and the edge is crossed when y2 > y1 ? t > 0 : t < 0.
+ *                     C is inside when the number of crossed edges is odd. (Of an axis-aligned rectangle the sides with the smaller x and the smaller y
+ *                     belong to the zone, the other two do not: the rule decides, nothing is fuzzy.)
+ *                   crossed(l, A, C), line l from P to Q, movement from A to C: d(X) = (Qx - Px) * (Xy - Py) - (Qy - Py) *
+ *                     (Xx - Px), e(X) = (Cx - Ax) * (Xy - Ay) - (Cy - Ay) * (Xx - Ax). Crossed when (d(A) > 0) != (d(C) > 0)
+ *                     and (e(P) > 0) != (e(Q) > 0); POSITIVE when d(C) > 0, else NEGATIVE.
+ *                   State, prev and next, mpn_zone_state_bytes(streams) bytes DEVICE, per stream 1860 32-bit words: int32
+ *                     frames, three zero words; cumulative uint32 zone_entries[16], zone_exits[16], line_positive[16],
+ *                     line_negative[16]; then 64 slots (always 64: mpn_pose_track's largest table) of 28 words: int32 id (0 =
+ *                     never used), uint32 inside (the confirmed membership mask), int32 last (the stream's frame number of the
+ *                     last observation, 0 = none), one zero word, f64 ax, ay (the anchor of that observation), int32
+ *                     entered_frame[16], uint8 run[16]. An all-zero state is the valid empty state. Frame numbers count from 1
+ *                     and are NOT guarded against wrap, as in mpn_pose_smooth.
+ *                   Per frame j of the launch (0 <= j < F), now = prev.frames + j + 1:
+ *                     1. slots: the image's rows with track_id > 0 and an anchor, serially in row order (the one step whose
+ *                        order matters). The row takes the lowest slot with id == track_id; if an earlier row of this frame
+ *                        took that slot (two rows with one id), the row is handled as UNTRACKED. If no slot has the id, the row
+ *                        takes, among the slots no earlier row of this frame took, the one with the smallest `last` (as int32),
+ *                        the lowest index on a tie - a never-used slot has last = 0 and goes first - and resets it to {id =
+ *                        track_id, every other word 0}. 64 slots and at most 64 rows per frame: there is always one.
+ *                     2. zones, a row with a slot: for every zone z < num_zones, raw = inside(z, C). raw equal to the slot's
+ *                        confirmed bit: run[z] = 0. Otherwise run[z] + 1 >= min_frames flips the bit with run[z] = 0 - to
+ *                        inside: the row ENTERED, entered_frame[z] = now; to outside: the row EXITED, entered_frame[z] = 0 -
+ *                        and else run[z] += 1. dwell[z] = now - entered_frame[z] + 1 while the bit is set, else 0. Frames in
+ *                        which the person is not observed do not step run.
+ *                     3. lines, a row whose slot had last != 0 before this frame: crossed(l, A, C) for every l < num_lines with
+ *                        A the slot's stored anchor, however many frames ago. Lines are not debounced.
+ *                     4. the slot's anchor becomes C, last = now.
+ *                     5. every other row with an anchor (track_id <= 0, or the second of two rows with one id) is UNTRACKED:
+ *                        inside is its raw mask, it has no events, dwell 0; no state is touched.
+ *                     The counters take the frame's events as integer adds. Slots that no row names are copied from prev to next
+ *                     unchanged; next.frames = prev.frames + F. A frame without detections still counts.
+ *                   out: mpn_zone_out_bytes(B, max_boxes) bytes DEVICE. B * max_boxes person rows of 104 bytes aligned with the
+ *                     record's rows 0 .. total-1, every row behind total zero: uint32 inside, entered, exited,
+ *                     crossed_positive, crossed_negative (bit z or l), flags (bit 0 tracked: the row has a slot; bit 1 the
+ *                     anchor came from the ankles; bit 2 no anchor), f64 anchor[2] = (x, y), int32 dwell[16]. Behind them B
+ *                     image rows of uint32 [9][16]: occupancy (the image's rows whose inside bit is set, untracked ones
+ *                     included), entries, exits, positive, negative (this frame's events), total_entries, total_exits,
+ *                     total_positive, total_negative (cumulative, after this frame).
+ *                   Checked before any HIP call, the messages begin "zone_events:": null pointers, prev == next
+ *                     (MPN_ERR_BAD_ARG); streams >= 1, B % streams == 0, 1 <= max_boxes <= 64, B * max_boxes <= 4096
+ *                     (MPN_ERR_BAD_SHAPE); record 16-byte, track_rows / table / prev / next / out 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN). The grid depends on streams alone: a captured launch serves any later record, table
+ *                     contents and state.
+ *   mpn_zone_table_bytes   4712.
+ *   mpn_zone_state_bytes   streams * 7440; 0 for arguments out of range.
+ *   mpn_zone_out_bytes     B * max_boxes * 104 + B * 576; 0 for arguments out of range.
+ */
+size_t mpn_zone_table_bytes(void);
+size_t mpn_zone_state_bytes(int streams);
+size_t mpn_zone_out_bytes(int B, int max_boxes);
+int mpn_zone_events(const void* record, const void* track_rows, int B, int max_boxes, int streams, const void* table,
+                    const void* prev, void* next, void* out, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

@@ -163,6 +163,10 @@ SIGNATURES = {
     "mpn_track_eval_state_bytes": (_Z, [_I, _I]),
     "mpn_track_eval_out_bytes": (_Z, [_I, _I, _I]),
     "mpn_track_eval": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _D, _P, _P, _Z, _P, _Z, _P]),
+    "mpn_zone_table_bytes": (_Z, []),
+    "mpn_zone_state_bytes": (_Z, [_I]),
+    "mpn_zone_out_bytes": (_Z, [_I, _I]),
+    "mpn_zone_events": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mpn_coco_masks_image_desc_bytes": (_Z, []),
     "mpn_coco_masks_part_desc_bytes": (_Z, []),
     "mpn_coco_masks_plane_words": (_Z, [_I, _I]),

@@ -141,12 +141,12 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval anonymize pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval zones anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the TrackEvaluator of track_eval= or None; the Anonymize of anonymize= or None; the PoseNms of pose_nms= or
-    None (the last field, as ever)."""
+    return_heatmaps; the TrackEvaluator of track_eval= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
+    None; the PoseNms of pose_nms= or None (the last field, as ever)."""
     __slots__ = ()
 
     @property
@@ -169,28 +169,35 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
             key += ('pose_nms', self.pose_nms)
         if self.track_eval is not None:
             key += ('track_eval', self.track_eval.serial)
+        if self.zones is not None:
+            key += ('zones', self.zones.serial)
         if self.anonymize is not None:
             key += ('anonymize', self.anonymize)
         return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None):
+def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None):
     """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
     filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
     pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
     rows: `row_offsets`); behind that, at the next multiple of 16 bytes, mpn_pose_nms's info block (nms: the entry's
     pose_nms.PoseNmsBuffers). A part that is not there is empty; a record of 0 bytes: more slots than mpn_pose_gather packs.
     track_eval (the entry's track_metrics.TrackEvaluator): a fifth slice, mpn_track_eval's rows behind everything else at the
-    next multiple of 16 bytes; without it the four slices are returned, as ever."""
+    next multiple of 16 bytes; without it the four slices are returned, as ever. zones (the entry's zones.ZoneCounter): one
+    more slice at the end of the tuple, mpn_zone_events' rows behind everything else at the next multiple of 16 bytes; without
+    it the function returns what it returns without the argument."""
     record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
     rows = record + (oks.out_bytes if oks is not None else 0)
     end = rows + (track.out_bytes(b) if track is not None else 0)
     info = slice((end + 15) // 16 * 16, (end + 15) // 16 * 16 + nms.info_bytes) if nms is not None else slice(end, end)
     parts = slice(0, record), slice(record, rows), slice(rows, end), info
-    if track_eval is None:
-        return parts
-    at = (info.stop + 15) // 16 * 16
-    return parts + (slice(at, at + track_eval.out_bytes(b)),)
+    if track_eval is not None:
+        at = (info.stop + 15) // 16 * 16
+        parts += (slice(at, at + track_eval.out_bytes(b)),)
+    if zones is not None:
+        at = (parts[-1].stop + 15) // 16 * 16
+        parts += (slice(at, at + zones.out_bytes(b)),)
+    return parts
 
 
 class _Entry:
@@ -199,11 +206,11 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the mpn_anonymize stage of an
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the mpn_anonymize stage of an
     `anonymize=` entry (an anonymize_stage.Anonymizer: it holds the anonymised frames the drawing reads), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -400,7 +407,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None, anonymize=None, track_eval=None):
+                      pose_nms=None, anonymize=None, zones=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -474,6 +481,15 @@ class Detector:
                 evaluator's state; the call advances it once, beside the tracker's. Every dict gains 'track_eval'
                 (`TrackEvaluator.unpack`: the frame's counts, per ground truth the matched id, flags and similarity, per
                 person the matched ground truth and flags); `evaluator.collect(outputs)` feeds `evaluate()`. None changes nothing.
+            zones: None, or a zones.ZoneCounter (needs track=; the counter's streams and max_boxes are the tracker's, its
+                frame_size the size of the frames): one mpn_zone_events launch behind the tracker's inside the captured graph - a
+                graph of its own per counter - tests every kept person's anchor (the feet; without the PRN the box) against the
+                counter's polygons and lines over the record the tracker read (the filtered one with pose_nms=). The rows lie
+                behind every other part of the result buffer and arrive in the record's one copy. The launch only reads the
+                counter's state; the call advances it once, beside the tracker's. Every dict gains 'zones'
+                (`ZoneCounter.unpack`: per person the zones it is inside, its entries, exits, line crossings, anchor and dwell
+                times; per frame the occupancy, the events and the running totals). Persons below score_threshold and coasting
+                tracks are not counted. Every other key is unchanged. None changes nothing.
             anonymize: None, or an inference.Anonymize (needs annotate=True or 'jpeg' and the detector; max_boxes <= 128): every
                 kept person is made unrecognisable in the frame `annotate` shows - its head, from the record's face joints, or
                 its box, pixelated, blurred or filled. One mpn_anonymize behind the gather (behind mpn_pose_nms: on the
@@ -489,7 +505,7 @@ class Detector:
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -512,13 +528,15 @@ class Detector:
             ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
         if ent.track_eval is not None:
             ent.track_eval.commit()
+        if ent.zones is not None:
+            ent.zones.commit()
         return self._finish(ent, outs, b, opts.return_heatmaps)
 
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, anonymize (the
-        last three may be absent: None; anonymize is checked last). shape(): the method's own
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, zones, anonymize (the
+        last four may be absent: None; anonymize is checked last, zones before it). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
@@ -534,9 +552,31 @@ class Detector:
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
         nms = self._check_pose_nms(given.get('pose_nms'))
         evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
+        counter = self._check_zones(given.get('zones'), given['track'], b, shaped[4].sizes if len(shaped) > 4 else [(h, w)])
         spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], evaluator, spec, nms), shaped
+                        given['return_heatmaps'], evaluator, counter, spec, nms), shaped
+
+    def _check_zones(self, counter, track, b, sizes):
+        """The `zones` argument of the predict_* methods -> None or the ZoneCounter. sizes: (height, width) of the call's frames,
+        in whose pixels the record's keypoints are. Before any device work."""
+        if counter is None:
+            return None
+        from ..zones import ZoneCounter
+        if not isinstance(counter, ZoneCounter):
+            raise ValueError("zones must be None or a zones.ZoneCounter")
+        if track is None:
+            raise ValueError("zones= counts the tracker's identities: it needs track=, a tracking.PoseTracker")
+        if counter.streams != track.streams:
+            raise ValueError(f"zones=: the counter was made for {counter.streams} streams, the tracker for {track.streams}")
+        if counter.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"zones=: the counter was made for max_boxes = {counter.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if torch.device(counter.device) != torch.device(self.net.device):
+            raise ValueError(f"zones=: the counter lives on {counter.device}, this Detector on {self.net.device}")
+        counter.check_frame_sizes(sizes)
+        counter.out_bytes(b)
+        return counter
 
     def _check_anonymize(self, spec, annotate, track_style):
         """The `anonymize` argument of the predict_* methods -> None or the Anonymize. Before any device work."""
@@ -674,6 +714,10 @@ class Detector:
                 eval_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval)[4]
                 for p, rows in zip(persons, ent.track_eval.unpack(record[eval_rows], counts)):
                     p['track_eval'] = rows
+            if ent.zones is not None:                               # mpn_zone_events' rows lie behind those: the same copy
+                zone_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones)[-1]
+                for p, rows in zip(persons, ent.zones.unpack(record[zone_rows], counts)):
+                    p['zones'] = rows
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -732,6 +776,7 @@ class Detector:
             ent.oks = pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, dev, opts.oks[1], opts.oks[2])
         ent.track = opts.track
         ent.track_eval = opts.track_eval
+        ent.zones = opts.zones
         if opts.pose_nms is not None:
             ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
         if opts.style:
@@ -765,6 +810,8 @@ class Detector:
         ent.track_eval (a track_metrics.TrackEvaluator, with track and oks): mpn_track_eval follows the tracker's launches over the
         record the tracker read, the tracker's rows and the ground truth ent.oks holds; its rows lie behind everything else.
         Pure in the same way: the caller commits.
+        ent.zones (a zones.ZoneCounter, with track): mpn_zone_events follows the tracker's launches (and mpn_track_eval) over the record
+        the tracker read and the tracker's rows; its rows lie behind everything else. Pure in the same way: the caller commits.
         ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -800,7 +847,7 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval)
+        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones)
         in_record, oks_rows, track_rows, nms_info = layout[:4]
         nbytes = in_record.stop
         if nbytes == 0:
@@ -825,6 +872,8 @@ class Detector:
         if ent.track_eval is not None:                              # the record the tracker read, its rows, the ground truth in place
             ent.track_eval.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[4]], b,
                                   *ent.oks.device_groundtruth())
+        if ent.zones is not None:                                   # the record the tracker read and its rows; without the PRN: boxes
+            ent.zones.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]], b, self.assigner is not None)
         dev['record'] = whole
         drawn = record
         if ent.anonymize is not None:                               # the drawing reads the anonymised frames in place of the sources
@@ -866,7 +915,8 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, track_eval=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, zones=None,
+                       track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -895,6 +945,7 @@ class Detector:
             track_style: as for `predict_batch`; the identities are drawn on the SOURCE frames.
             pose_nms: as for `predict_batch`; the similarity is that of the keypoints in source pixels, as they are returned.
             track_eval: as for `predict_batch`, with the ground truth in the pixels of the SOURCE images.
+            zones: as for `predict_batch`, in the pixels of the SOURCE images, which must all have the counter's frame_size.
             anonymize: as for `predict_batch`; the SOURCE frames are anonymised at their own size. `plot_maps` and the heatmaps
                 still show the network's input.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
@@ -909,7 +960,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -923,7 +974,7 @@ class Detector:
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
                       groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None,
-                      track_eval=None):
+                      zones=None, track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -940,7 +991,7 @@ class Detector:
             size, keep_aspect_ratio, score_threshold, return_heatmaps, annotate, jpeg_quality, jpeg_subsampling, plot_maps: as
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
-            flip, scales, track, track_style, pose_nms, track_eval, anonymize: as for `predict_images`.
+            flip, scales, track, track_style, pose_nms, track_eval, zones, anonymize: as for `predict_images`.
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -959,7 +1010,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -998,6 +1049,8 @@ class Detector:
             ent.track.commit()                                      # as in predict_batch: once per call, outside the graph
         if ent.track_eval is not None:
             ent.track_eval.commit()
+        if ent.zones is not None:
+            ent.zones.commit()
         persons = self._finish(ent, outs, b, opts.return_heatmaps)
         if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):

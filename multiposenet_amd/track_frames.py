@@ -11,6 +11,7 @@
         [--anonymize [head|box] [--anonymize-mode pixelate|blur|fill] [--anonymize-shape ellipse|rectangle] [--anonymize-blocks 8]
         [--anonymize-radius 8] [--anonymize-no-overlay]]
         [--annotations JSON [--eval-threshold 0.5]]
+        [--zones FILE.json]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -36,7 +37,13 @@ boxes, skeletons and ids; the class's defaults are not tuned). --annotations JSO
 COCO-style file whose annotations carry `track_id`, PoseTrack's layout; frames are found by the base name of `file_name`, a frame
 the file does not name has no annotated person) scores the identities while it tracks (`track_eval=`, a
 `track_metrics.TrackEvaluator`: one more launch in the same graph; a pair can correspond at OKS >= --eval-threshold) and adds
-MOTA, MOTP, IDF1 and the counts behind them to the summary as "track_eval". Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+MOTA, MOTP, IDF1 and the counts behind them to the summary as "track_eval". --zones FILE.json counts the tracked persons in
+polygons and across lines while it tracks (`zones=`, a `zones.ZoneCounter`: one more launch in the same graph). The file holds
+"frame_size" [height, width], named "zones" {name: [[x, y], ...]} and "lines" {name: [[x, y], [x, y]]} in the frames' pixels and,
+optionally, "anchor", "min_frames" and "min_keypoint_score". Every line gains "zones": per person the names of the zones it is
+inside ("inside") and its events ("entered", "exited", "crossed_positive", "crossed_negative"), and for the frame "occupancy",
+"entries", "exits", "line_positive" and "line_negative" by name; the summary gains the totals by name as "zones". A frame of
+another size than frame_size ends the run with a ValueError. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -97,6 +104,9 @@ def main(argv=None):
     ap.add_argument("--hide-untracked", action="store_true", help="leave persons without an id out of the frames (--frames-out)")
     ap.add_argument("--annotations", metavar="JSON", help="PoseTrack-style annotations: evaluate the tracks (MOTA, IDF1) while tracking")
     ap.add_argument("--eval-threshold", type=float, default=0.5, help="OKS at which a person can correspond to an annotation (--annotations)")
+    ap.add_argument("--zones", metavar="FILE.json",
+                    help="count the tracked persons in polygons and across lines: frame_size, named zones and lines, "
+                         "optionally anchor, min_frames, min_keypoint_score")
     from . import pose_nms
     from .inference import anonymize_stage
     pose_nms.add_arguments(ap)
@@ -160,6 +170,19 @@ def main(argv=None):
         from .track_metrics import TrackEvaluator, groundtruth_from_posetrack
         annotated = {os.path.basename(name): gt for name, gt in groundtruth_from_posetrack(args.annotations)}
         evaluator = TrackEvaluator(streams=1, threshold=args.eval_threshold, max_boxes=det.params['max_boxes'])
+    counter = None
+    if args.zones is not None:
+        from .zones import ZoneCounter
+        with open(args.zones) as f:
+            spec = json.load(f)
+        unknown = sorted(set(spec) - {"frame_size", "zones", "lines", "anchor", "min_frames", "min_keypoint_score"})
+        if unknown or "frame_size" not in spec:
+            ap.error(f"--zones: {args.zones} must hold frame_size, zones and / or lines, and optionally anchor, min_frames, "
+                     f"min_keypoint_score (unknown: {unknown})")
+        try:
+            counter = ZoneCounter(streams=1, max_boxes=det.params['max_boxes'], **spec)
+        except ValueError as e:
+            ap.error(str(e))
     nobody = {'keypoints': np.zeros((0, 17, 3)), 'boxes': np.zeros((0, 4)), 'track_ids': np.zeros(0, np.int64)}
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -172,6 +195,8 @@ def main(argv=None):
             scored = {}
             if evaluator is not None:
                 scored = dict(groundtruth=[annotated.get(name, nobody) for name in batch], track_eval=evaluator)
+            if counter is not None:
+                scored["zones"] = counter
             if all(_is_jpeg(data) for data in files):
                 outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, pose_nms=nms,
                                         **draw, **scored)
@@ -190,6 +215,16 @@ def main(argv=None):
                     line["coasting_ids"] = o["coasting_ids"].tolist()
                     line["coasting_boxes"] = o["coasting_boxes"].tolist()
                     line["coasting_keypoints"] = o["coasting_keypoints"].tolist()
+                if counter is not None:
+                    z = o["zones"]
+                    line["zones"] = {k: [[name for name, hit in zip(names_of, row) if hit] for row in z[k]]
+                                     for k, names_of in (("inside", counter.zone_names), ("entered", counter.zone_names),
+                                                         ("exited", counter.zone_names), ("crossed_positive", counter.line_names),
+                                                         ("crossed_negative", counter.line_names))}
+                    line["zones"].update({k: dict(zip(names_of, z[k].tolist()))
+                                          for k, names_of in (("occupancy", counter.zone_names), ("entries", counter.zone_names),
+                                                              ("exits", counter.zone_names), ("line_positive", counter.line_names),
+                                                              ("line_negative", counter.line_names))})
                 out.write(json.dumps(line) + "\n")
                 if draw:
                     with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
@@ -208,6 +243,8 @@ def main(argv=None):
         summary["pose_nms"] = {"threshold": nms.threshold, "min_keypoint_score": nms.min_keypoint_score, "score": nms.score}
     if evaluator is not None:
         summary["track_eval"] = dict(evaluator.evaluate(), threshold=evaluator.threshold, annotations=args.annotations)
+    if counter is not None:
+        summary["zones"] = dict(counter.totals(0), file=args.zones)
     print(json.dumps(summary))
     return state
 
