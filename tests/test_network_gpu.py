@@ -46,17 +46,25 @@ def test_forward_inference_config1_f32(cuda):
     np.testing.assert_allclose(seg.cpu().numpy(), heat[..., 17].numpy(), atol=1e-3, rtol=1e-3)
 
 
-def test_training_forward_every_layer_f32(cuda):
-    """Raw output of every conv in TRAINING mode (batch statistics) vs the f64 oracle, layer by layer."""
+SQUARE = (2, 128, 128)
+# the smallest shapes off the square (image sides are multiples of net.DIVISOR = 128): width > height (levels 2..5 = 32x64 .. 4x8), and
+# height > width at batch 1 (64x32 .. 8x4). An h / w transposition in a buffer shape, a job table or a launch geometry, a row pitch from
+# the wrong axis and a per-image stride that only matters when B != 2 are all invisible at 2 x 128 x 128.
+OFF_SQUARE = [pytest.param((2, 128, 256), id="2x128x256"), pytest.param((1, 256, 128), id="1x256x128")]
+
+
+def _training_forward_every_layer(shape=SQUARE):
     from multiposenet_amd.net import KeypointNet
     rs = np.random.RandomState(11)
-    B, H, W = 2, 128, 128
+    B, H, W = shape
     params = _params(3)
     img = rs.rand(B, H, W, 3).astype(np.float32)
     taps = {}
     with torch.no_grad():
-        heat, _ = onet.forward(torch.tensor(img, dtype=torch.float64),
-                               {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}, True, taps=taps)
+        heat, enr = onet.forward(torch.tensor(img, dtype=torch.float64),
+                                 {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}, True, taps=taps)
+    for l in (2, 3, 4, 5):      # (the raw FPN outputs, which the oracle returns NHWC instead of tapping them: 41 + 4 = 45 tensors)
+        taps[f"p{l}"] = enr[f"p{l}"].permute(0, 3, 1, 2)
     net = KeypointNet(values=params, dtype=torch.float32)
     logits, _ = net.forward(torch.tensor(img).cuda(), True)
     b = net._last[0]
@@ -68,16 +76,36 @@ def test_training_forward_every_layer_f32(cuda):
         got[f"x{l}"] = b["x"][l]
         got[f"phi_subnet_{l}/y1"] = b["y1"][l]
         got[f"phi_subnet_{l}/y2"] = b["y2"][l]
-    bad = []
+        got[f"p{l}"] = b["p"][l]
+    assert len(got) == 45 and tuple(logits.shape) == (B, H // 4, W // 4, 18)
+    bad, errs = [], []
     for k, t in got.items():
         want = taps[k].permute(0, 2, 3, 1).numpy()
+        assert tuple(t.shape) == want.shape, (k, t.shape, want.shape)
         if k == "concat":   # channels 0..127 hold level 2 RAW (= phi_subnet_2/y2, checked under that name): compare the rest
             t, want = t[..., 128:], want[..., 128:]
         err = np.abs(t.cpu().numpy().astype(np.float64) - want).max() / (np.abs(want).max() + 1e-30)
+        errs.append((float(err), k))
         if err > 2e-4:
             bad.append((k, float(err)))
+    print(f"\n[training forward {B}x{H}x{W}] worst max-error / max of 45 taps: {max(errs)[0]:.1e} ({max(errs)[1]}), median "
+          f"{float(np.median([e for e, _ in errs])):.1e}; logits max abs error {float(np.abs(logits.cpu().numpy() - heat.numpy()).max()):.1e}")
     assert not bad, bad
     np.testing.assert_allclose(logits.cpu().numpy(), heat.numpy(), atol=1e-3, rtol=1e-3)
+
+
+def test_training_forward_every_layer_f32(cuda):
+    """Raw output of every conv in TRAINING mode (batch statistics) vs the f64 oracle, layer by layer."""
+    _training_forward_every_layer()
+
+
+@pytest.mark.parametrize("shape", OFF_SQUARE)
+def test_training_forward_every_layer_off_the_square_f32(cuda, shape):
+    """test_training_forward_every_layer_f32 off the square: the raw output of all 45 taps within 2e-4 of each tensor's maximum of the
+    f64 oracle, the logits to 1e-3 - the square test's bounds (the f32 oracle's own distance from the f64 one is no larger here than on
+    the square: 2.8e-6 / 3.4e-6 against 3.2e-6). Measured on the MI355X: worst tap 2.9e-5 / 4.5e-5 (concat), median 9.1e-6 /
+    9.1e-6, logits 5.1e-5 / 4.7e-5 absolute (the square: 2.7e-5, 8.4e-6, 4.9e-5)."""
+    _training_forward_every_layer(shape)
 
 
 def _params_smooth(seed):
@@ -94,10 +122,10 @@ def _params_smooth(seed):
     return p
 
 
-def _layer_gradient_errors(seed, smooth=False):
+def _layer_gradient_errors(seed, smooth=False, shape=SQUARE):
     from multiposenet_amd.net import KeypointNet
     rs = np.random.RandomState(seed)
-    B, H, W = 2, 128, 128
+    B, H, W = shape
     params = _params_smooth(seed) if smooth else _params(seed)
     img = rs.rand(B, H, W, 3).astype(np.float32)
     lab = _labels(rs, B, H // 4, W // 4)
@@ -125,6 +153,7 @@ def _layer_gradient_errors(seed, smooth=False):
     rep = []
     for k, t in got.items():
         want = taps[k].grad.permute(0, 2, 3, 1).numpy()
+        assert tuple(t.shape) == want.shape, (k, t.shape, want.shape)
         if k == "concat":   # (its first 128 channels were turned into the gradient w.r.t. the raw level-2 output in place)
             t, want = t[..., 128:], want[..., 128:]
         a = t.cpu().numpy().astype(np.float64)
@@ -143,6 +172,21 @@ def test_backward_every_layer_smooth_network_f32(cuda):
     assert float(np.median([e for _, e in rep])) < 1e-4
 
 
+@pytest.mark.parametrize("shape", OFF_SQUARE)
+def test_backward_every_layer_smooth_network_off_the_square_f32(cuda, shape):
+    """test_backward_every_layer_smooth_network_f32 off the square: the activation gradient of every tap against autograd through the
+    f64 oracle with all activation masks pinned open, the square test's bounds (worst tensor below 1e-3 relative L2, median below
+    1e-4; the f32 oracle's own worst is 4.6e-6 / 4.4e-6 here against 6.5e-6 on the square, and the deepest batch-norms see 64 and 32
+    samples against 32). Measured on the MI355X: worst 6.2e-5 (Conv2d_12_pointwise) / 1.5e-4 (Conv2d_12_depthwise),
+    median 7.8e-6 / 8.3e-6."""
+    rep = _layer_gradient_errors(21, smooth=True, shape=shape)
+    assert len(rep) == 41
+    print(f"\n[smooth backward {shape}] worst per-layer activation-gradient errors (rel L2):", [(k, f"{e:.1e}") for k, e in rep[:4]],
+          f"median {float(np.median([e for _, e in rep])):.1e}")
+    assert rep[0][1] < 1e-3, rep[:6]
+    assert float(np.median([e for _, e in rep])) < 1e-4
+
+
 def test_backward_every_layer_f32(cuda):
     """d(total loss)/d(raw conv output) of EVERY layer vs autograd through the f64 oracle, two seeds.
     f32 and f64 forward values differ by ~1e-6..1e-5 relative, so out of ~3M ReLU/ReLU6 inputs about ten per run
@@ -158,11 +202,11 @@ def test_backward_every_layer_f32(cuda):
     assert best_final < 1e-4, best_final
 
 
-def test_train_step_f32_matches_oracle(cuda):
+def _train_step_f32_matches_oracle(shape=SQUARE, data_seed=3):
     from multiposenet_amd.net import KeypointNet
     from multiposenet_amd.train import Trainer
-    rs = np.random.RandomState(3)
-    B, H, W = 2, 128, 128
+    rs = np.random.RandomState(data_seed)
+    B, H, W = shape
     params = _params(1)
     img = rs.rand(B, H, W, 3).astype(np.float32)
     lab = _labels(rs, B, H // 4, W // 4)
@@ -196,11 +240,16 @@ def test_train_step_f32_matches_oracle(cuda):
     report = sorted(ours.items(), key=lambda kv: -kv[1])
     print("worst relative-L2 gradient errors:", [(k, f"{e:.1e}", f"oracle-f32 {yard[k]:.1e}") for k, e in report[:6]])
     print("median ours / oracle-f32:", float(np.median(list(ours.values()))), float(np.median(list(yard.values()))))
-    assert float(np.median(list(ours.values()))) < max(2e-3, 2 * float(np.median(list(yard.values()))))
-    assert report[0][1] < max(2e-2, 2 * max(yard.values())), report[:5]
+    cosines = {}
     for k, g in grads.items():   # direction of every gradient tensor
         got = net.grads[k].cpu().numpy().astype(np.float64).ravel()
-        cos = float(got @ g.ravel() / (np.linalg.norm(got) * np.linalg.norm(g) + 1e-30))
+        cosines[k] = float(got @ g.ravel() / (np.linalg.norm(got) * np.linalg.norm(g) + 1e-30))
+    want7 = np.array(list(losses.values()) + [total])
+    print(f"[train step {B}x{H}x{W}] worst ours / worst oracle-f32: {report[0][1]:.1e} / {max(yard.values()):.1e}; lowest cosine "
+          f"{min(cosines.values()):.6f}; worst relative loss error {float(np.abs(out[:7] / want7 - 1).max()):.1e}")
+    assert float(np.median(list(ours.values()))) < max(2e-3, 2 * float(np.median(list(yard.values()))))
+    assert report[0][1] < max(2e-2, 2 * max(yard.values())), report[:5]
+    for k, cos in cosines.items():
         assert cos > 0.99, (k, cos)
     # variables after the Adam step and the moving statistics
     sd = net.state_dict()
@@ -212,6 +261,35 @@ def test_train_step_f32_matches_oracle(cuda):
         else:
             np.testing.assert_allclose(sd[k], ref[k], atol=1e-4, rtol=1e-4, err_msg=k)
     assert int(net.global_step.item()) == 1
+
+
+def test_train_step_f32_matches_oracle(cuda):
+    _train_step_f32_matches_oracle()
+
+
+# The data seed of each off-square train step is chosen on the host from the ORACLE alone (tools/train_step_conditioning.py search,
+# profiles/train_step_conditioning.txt): the first seed from 3 upward at which the f32 oracle meets every assertion of the test in all
+# of 13 roundings of the same step (its input as it is, and moved by one ulp twelve times). At the square test's seed 3 it does so in 1
+# of 7 (2 x 128 x 256) and 4 of 7 (1 x 256 x 128): a case the yardstick itself does not pass cannot tell a wrong kernel from rounding.
+TRAIN_STEP_OFF_SQUARE = [pytest.param((2, 128, 256), 14, id="2x128x256"), pytest.param((1, 256, 128), 35, id="1x256x128")]
+
+
+@pytest.mark.parametrize("shape,data_seed", TRAIN_STEP_OFF_SQUARE)
+def test_train_step_off_the_square_f32_matches_oracle(cuda, shape, data_seed):
+    """test_train_step_f32_matches_oracle off the square: one step against onet.train_step in f64 with the f32 oracle as yardstick -
+    the losses to 2e-4, the gradients' relative L2 (median below max(2e-3, 2 x yardstick), worst below max(2e-2, 2 x yardstick)),
+    cosine above 0.99 for every gradient tensor, the variables after the Adam step, the moving statistics, global_step == 1.
+    Why the data seed is not the square's 3: a pre-activation within f32 rounding of 0 or 6 lands on either side, one flipped mask in
+    a deep layer moves every gradient below it by 1e-3 .. 1e-2 (test_backward_every_layer_f32), and the yardstick is ONE draw of that
+    scatter. At seed 3 and 2 x 128 x 256 the build read a median of 1.17e-2 against the yardstick's 1.59e-3 with a forward pass as close
+    to the f64 oracle as the f32 oracle's on every layer (8.0e-6 / 8.7e-6 at Conv2d_11_pointwise): three of that layer's 131072
+    pre-activations lie within 4e-7 of a ReLU6 threshold, and the activation gradient's error steps from 1.7e-3 above that layer to
+    1.4e-2 below it - and the f32 oracle itself, its input moved by one ulp, read medians of 4.3e-3 .. 1.2e-2. So the case is taken
+    where the bound is one that every rounding of the oracle keeps (see TRAIN_STEP_OFF_SQUARE), and the bounds stay as the square
+    test states them. Measured on the MI355X: median 1.04e-3 against the yardstick's 2.23e-3 (bound 4.5e-3) and worst 2.3e-3
+    (bound 2e-2) at 2 x 128 x 256, median 6.3e-3 against 6.1e-3 (bound 1.2e-2) and worst 2.1e-2 against 1.6e-2 (bound 3.2e-2) at
+    1 x 256 x 128; lowest cosine 0.999997 / 0.99978, losses within 2.7e-6 / 4.1e-6."""
+    _train_step_f32_matches_oracle(shape, data_seed)
 
 
 def test_graph_replay_equals_eager_and_bf16_tracks_f32(cuda):
@@ -296,6 +374,111 @@ def test_weight_decay_term_matches_oracle(cuda):
     np.testing.assert_allclose(ev[6] - ev[:6].sum(), wd * sum(
         0.5 * float((p.astype(np.float64) ** 2).sum()) for k, p in net.state_dict().items()
         if ("weights" in k or "kernel" in k) and "depthwise_weights" not in k), rtol=1e-3)
+
+
+@pytest.mark.parametrize("shape", OFF_SQUARE)
+def test_eval_step_matches_oracle_off_the_square(cuda, shape):
+    """Trainer.eval_step (VERDICT "What's missing" 8: only its weight-decay term had been checked) against the f64 oracle under MOVING
+    statistics (randomize_bn: not the trivial 0 / 1): onet.forward(..., False), onet.losses_fn and onet.per_pixel_reg_loss. All eight
+    entries of ops.LOSS_NAMES to rtol 2e-4 (the project's bound for the training losses), once without weight decay and once with
+    weight_decay = 1e-2, where the total carries the regularisation term as test_weight_decay_term_matches_oracle computes it.
+    Measured on the MI355X: the worst of the eight is 6.6e-7 / 7.5e-7 (segmentation_loss_at_level_3), every other
+    entry below 4e-7, with and without the decay term."""
+    from multiposenet_amd import ops
+    from multiposenet_amd.net import KeypointNet
+    from multiposenet_amd.train import Trainer
+    rs = np.random.RandomState(17)
+    B, H, W = shape
+    params = _params(9)
+    assert float(np.abs(params["final_bn/moving_mean"]).max()) > 0 and float(np.abs(params["final_bn/moving_variance"] - 1).max()) > 0
+    img = rs.rand(B, H, W, 3).astype(np.float32)
+    lab = _labels(rs, B, H // 4, W // 4)
+    with torch.no_grad():
+        heat, enr = onet.forward(torch.tensor(img, dtype=torch.float64),
+                                 {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}, False)
+        tl = {k: torch.tensor(v) if k == "num_boxes" else torch.tensor(v, dtype=torch.float64) for k, v in lab.items()}
+        total, losses = onet.losses_fn(heat, enr, tl)
+        ppr = float(onet.per_pixel_reg_loss(heat, tl))
+    six = [float(v) for v in losses.values()]
+    assert ops.LOSS_NAMES == list(losses) + ["total_loss", "per_pixel_reg_loss"]
+    wd = 1e-2
+    reg = wd * sum(0.5 * float((p.astype(np.float64) ** 2).sum()) for k, p in params.items()
+                   if ("weights" in k or "kernel" in k) and "depthwise_weights" not in k)
+    assert reg > 1e-3 * float(total)        # the term is visible at this wd
+    feats = {"images": torch.tensor(img).cuda()}
+    dlab = {k: torch.tensor(val).cuda() for k, val in lab.items()}
+    for decay, extra in ((0.0, 0.0), (wd, reg)):
+        hp = {"initial_learning_rate": 3e-4, "num_steps": 200000, "weight_decay": decay, "depth_multiplier": 1.0}
+        net = KeypointNet(values=params, dtype=torch.float32)
+        ev = Trainer(net, hp, use_graph=False).eval_step(feats, dlab).cpu().numpy().astype(np.float64)
+        want = np.array(six + [float(total) + extra, ppr])
+        print(f"\n[eval step {B}x{H}x{W}, weight_decay {decay}] relative errors of {ops.LOSS_NAMES}: "
+              f"{[f'{e:.1e}' for e in np.abs(ev / want - 1)]}")
+        assert ev.shape == (8,)
+        np.testing.assert_allclose(ev, want, rtol=2e-4, atol=1e-9)
+        assert int(net.global_step.item()) == 0
+        sd = net.state_dict()                # an EVAL step moves nothing
+        for k in params:
+            np.testing.assert_array_equal(sd[k], params[k], err_msg=k)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_graph_replay_equals_eager_off_the_square(cuda, dtype):
+    """Capture and replay at 2 x 128 x 256: three eager steps and three replayed steps are bit-identical in losses and state, for the
+    f32 build and for the bf16 build (each against itself: the bf16 build runs other kernels - the MFMA 3x3, the pointwise GEMM, the
+    bf16 weight gradients - and is the benchmarked one)."""
+    from multiposenet_amd.net import KeypointNet
+    from multiposenet_amd.train import Trainer
+    rs = np.random.RandomState(4)
+    B, H, W = 2, 128, 256
+    params = _params(2)
+    img = torch.tensor(rs.rand(B, H, W, 3).astype(np.float32)).cuda()
+    dlab = {k: torch.tensor(val).cuda() for k, val in _labels(rs, B, H // 4, W // 4).items()}
+    hp = {"initial_learning_rate": 3e-4, "num_steps": 200000, "weight_decay": 0.0, "depth_multiplier": 1.0}
+    res = {}
+    for graph in (False, True):
+        net = KeypointNet(values=params, dtype=torch.float32 if dtype == "f32" else torch.bfloat16)
+        tr = Trainer(net, hp, use_graph=graph)
+        ls = [tr.step({"images": img}, dlab).cpu().numpy().copy() for _ in range(3)]
+        res[graph] = (ls, net.state_dict(), int(net.global_step.item()))
+    assert res[False][2] == res[True][2] == 3
+    for a, b in zip(res[False][0], res[True][0]):
+        assert np.isfinite(a).all() and a[6] > 0
+        np.testing.assert_array_equal(a, b)
+    assert not np.array_equal(res[False][0][0], res[False][0][2])      # the steps do move the losses
+    for k in res[False][1]:
+        np.testing.assert_array_equal(res[False][1][k], res[True][1][k], err_msg=k)
+
+
+def test_buffer_sets_of_transposed_shapes_do_not_mix(cuda):
+    """One net, inference forward at 2 x 128 x 256, then at 2 x 256 x 128 (the same element counts in every buffer, so a buffer set
+    keyed or sized by the count alone would be shared), then the first input again: the third result equals the first bit for bit,
+    and the second matches the f64 oracle at its own shape to 1e-3. Measured on the MI355X: 3.6e-6 absolute on logits up to 5.2."""
+    from multiposenet_amd.net import KeypointNet
+    params = _params(4)
+    rs = np.random.RandomState(19)
+    wide = rs.rand(2, 128, 256, 3).astype(np.float32)
+    tall = rs.rand(2, 256, 128, 3).astype(np.float32)
+    net = KeypointNet(values=params, dtype=torch.float32)
+
+    def fwd(x):
+        logits, enriched = net.forward(torch.tensor(x).cuda(), False)
+        return logits.cpu().numpy().copy(), {l: enriched[f"p{l}"].float().cpu().numpy().copy() for l in (2, 3, 4, 5)}
+
+    first, second, third = fwd(wide), fwd(tall), fwd(wide)
+    assert first[0].shape == (2, 32, 64, 18) and second[0].shape == (2, 64, 32, 18)
+    np.testing.assert_array_equal(third[0], first[0])
+    for l in (2, 3, 4, 5):
+        np.testing.assert_array_equal(third[1][l], first[1][l])
+    with torch.no_grad():
+        heat, enr = onet.forward(torch.tensor(tall, dtype=torch.float64),
+                                 {k: torch.tensor(v, dtype=torch.float64) for k, v in params.items()}, False)
+    print(f"\n[2x256x128 after 2x128x256 on one net] logits max abs error {float(np.abs(second[0] - heat.numpy()).max()):.1e} "
+          f"(max |logit| {float(heat.abs().max()):.2f})")
+    np.testing.assert_allclose(second[0], heat.numpy(), atol=1e-3, rtol=1e-3)
+    for l in (2, 3, 4, 5):
+        assert second[1][l].shape == (2, 256 >> l, 128 >> l, enr[f"p{l}"].shape[3])
+        np.testing.assert_allclose(second[1][l], enr[f"p{l}"].numpy(), atol=1e-3, rtol=1e-3)
 
 
 def test_model_fn_contract(cuda):
@@ -513,6 +696,34 @@ def test_depth_multiplier_train_step(cuda, dm, c0, c0_internal):
     np.testing.assert_allclose(out[torch.bfloat16][6], out[torch.float32][6], rtol=3e-2)
 
 
+def _teacher_forced_backward_against_the_oracle(dtype, B=4, H=128, W=128):
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import bf16_teacher_forced as tf
+    out = tf.run(steps=60, B=B, size=128, H=H, W=W, dtype=torch.bfloat16 if dtype == "bf16" else torch.float32, verbose=False)
+    rows = {r[0]: r for r in out["rows"]}
+    tol_rel, tol_cos = (0.10, 0.99) if dtype == "bf16" else (2e-3, 0.99999)
+    np.testing.assert_allclose(out["loss"], out["oracle_loss"], rtol=1e-5 if dtype == "bf16" else 1e-6)
+    bad, excepted = [], []
+    for k, (_, size, norm, rel, cos) in rows.items():
+        if rel <= tol_rel and cos >= tol_cos:
+            continue
+        if k.endswith("/gamma") and k[:-6] + "/beta" in rows:
+            nb = rows[k[:-6] + "/beta"][2]
+            if norm <= 0.1 * nb and rel * norm <= (0.05 if dtype == "bf16" else 1e-3) * nb:      # |error| against the layer's |dbeta|
+                excepted.append((k, round(rel, 3), norm / nb))
+                continue
+        bad.append((k, rel, cos))
+    outside = {k: r for k, r in rows.items() if k not in dict((e[0], 0) for e in excepted)}
+    worst = max(outside.values(), key=lambda r: r[3])
+    print(f"\n[{dtype} backward, teacher-forced, {B}x{H}x{W}] all {len(rows)} gradient tensors together: rel-L2 {out['all_rel']:.3g}, cosine "
+          f"{out['all_cos']:.6f}; worst rel-L2 outside the exceptions {worst[3]:.3g} ({worst[0]}), median {float(np.median([r[3] for r in rows.values()])):.3g}; "
+          f"{len(excepted)} nearly scale-invariant gammas held to their layer's |dbeta|: {excepted[:3]} ...")
+    assert not bad, bad
+    assert out["all_rel"] <= (0.03 if dtype == "bf16" else 5e-4) and len(excepted) <= 16
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
 def test_backward_pass_teacher_forced_against_the_oracle(cuda, dtype):
     """an ABSOLUTE bound on the benchmarked (bf16) build's step gradients. A plain comparison cannot carry one:
@@ -528,26 +739,16 @@ def test_backward_pass_teacher_forced_against_the_oracle(cuda, dtype):
     arithmetic, not tolerance: the gammas of batch-norms that feed a depthwise conv + batch-norm are nearly scale-invariant
     directions (|dgamma| ~ 1e-2 of |dbeta|, a residue of cancelling sums): held to 5 % of that layer's |dbeta| instead.
     The f32 build through the same machinery: 1e-4."""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import bf16_teacher_forced as tf
-    out = tf.run(steps=60, B=4, size=128, dtype=torch.bfloat16 if dtype == "bf16" else torch.float32, verbose=False)
-    rows = {r[0]: r for r in out["rows"]}
-    tol_rel, tol_cos = (0.10, 0.99) if dtype == "bf16" else (2e-3, 0.99999)
-    np.testing.assert_allclose(out["loss"], out["oracle_loss"], rtol=1e-5 if dtype == "bf16" else 1e-6)
-    bad, excepted = [], []
-    for k, (_, size, norm, rel, cos) in rows.items():
-        if rel <= tol_rel and cos >= tol_cos:
-            continue
-        if k.endswith("/gamma") and k[:-6] + "/beta" in rows:
-            nb = rows[k[:-6] + "/beta"][2]
-            if norm <= 0.1 * nb and rel * norm <= (0.05 if dtype == "bf16" else 1e-3) * nb:      # |error| against the layer's |dbeta|
-                excepted.append((k, round(rel, 3), norm / nb))
-                continue
-        bad.append((k, rel, cos))
-    print(f"\n[{dtype} backward, teacher-forced] all {len(rows)} gradient tensors together: rel-L2 {out['all_rel']:.5f}, cosine "
-          f"{out['all_cos']:.6f}; worst rel-L2 outside the exceptions {max(r[3] for k, r in rows.items() if k not in dict((e[0], 0) for e in excepted)):.4f}; "
-          f"{len(excepted)} nearly scale-invariant gammas held to their layer's |dbeta|: {excepted[:3]} ...")
-    assert not bad, bad
-    assert out["all_rel"] <= (0.03 if dtype == "bf16" else 5e-4) and len(excepted) <= 16
+    _teacher_forced_backward_against_the_oracle(dtype)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f32"])
+def test_backward_pass_teacher_forced_against_the_oracle_off_the_square(cuda, dtype):
+    """test_backward_pass_teacher_forced_against_the_oracle at 2 @ 128 x 256 (the pixel count of 4 @ 128^2, so the same cost): the
+    bf16 build's backward chain - the MFMA 3x3 kernel, the pointwise GEMM, the bf16 weight gradients - at the emulating oracle's
+    forward state on a map that is wider than high, after the same 60 steps, under the same bounds (every tensor within 10 % and cosine
+    0.99, all together 3 %; f32: 2e-3 / 0.99999 / 5e-4) and the same rule for nearly scale-invariant gammas, at most 16 of them.
+    Measured on the MI355X, bf16: all 126 tensors together 1.48 % (the square: 1.47 %), worst outside the exceptions 6.2 %
+    (Conv2d_5_pointwise/BatchNorm/gamma; the square: 5.8 %, the same tensor), median 0.85 %, 11 gammas under the rule (the square: 11).
+    f32: together 1.5e-6, worst 4.8e-5 (Conv2d_0/BatchNorm/gamma), median 1.2e-6, no gamma under the rule."""
+    _teacher_forced_backward_against_the_oracle(dtype, B=2, H=128, W=256)

@@ -6,7 +6,7 @@ perturbation is taken out: the bf16 build runs its forward pass (sizing every bu
 raw conv outputs, FPN sums, concat slices, logits, and the batch statistics / affines of all 40 batch-norm layers - is OVERWRITTEN with
 the emulating oracle's (exactly representable) values, and the build's loss gradient + backward pass run from there. What remains
 is the arithmetic of the backward kernels themselves: bf16 gradient storage, f32 accumulation order, the fused reductions.
-python tools/bf16_teacher_forced.py [train steps] [batch] [size]"""
+python tools/bf16_teacher_forced.py [train steps] [batch] [size] [height] [width]   (height and width default to size)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -28,17 +28,18 @@ def labels_np(rs, B, h, w):
             "segmentation_masks": (rs.rand(B, h, w) < 0.3).astype(np.float32), "num_boxes": rs.randint(1, 4, B).astype(np.int32)}
 
 
-def trained_variables(steps, B, size, seed=5, pool=3, lr=1e-3):
+def trained_variables(steps, B, size, seed=5, pool=3, lr=1e-3, H=None, W=None):
     """the f32 build, `steps` steps over a small pool of batches: variables, batch-norm parameters and moving statistics of a network
-    that has left its initialisation (nothing here depends on HOW well it is trained)"""
+    that has left its initialisation (nothing here depends on HOW well it is trained). Batches of B @ H x W; both default to size."""
+    H, W = H or size, W or size
     hp = {"initial_learning_rate": lr, "num_steps": 200000, "weight_decay": 0.0, "depth_multiplier": 1.0}
     net = KeypointNet(dtype=torch.float32, seed=seed)
     tr = Trainer(net, hp, use_graph=False)
     rs = np.random.RandomState(seed)
     batches = []
     for _ in range(pool):
-        img = torch.tensor(rs.rand(B, size, size, 3).astype(np.float32)).cuda()
-        lab = {k: torch.tensor(v).cuda() for k, v in labels_np(rs, B, size // 4, size // 4).items()}
+        img = torch.tensor(rs.rand(B, H, W, 3).astype(np.float32)).cuda()
+        lab = {k: torch.tensor(v).cuda() for k, v in labels_np(rs, B, H // 4, W // 4).items()}
         batches.append((img, lab))
     first = last = None
     for i in range(steps):
@@ -48,11 +49,12 @@ def trained_variables(steps, B, size, seed=5, pool=3, lr=1e-3):
     return net.state_dict(), first, last
 
 
-def run(steps=60, B=4, size=128, seed=9, dtype=torch.bfloat16, verbose=True):
-    values, first, last = trained_variables(steps, B, size)
+def run(steps=60, B=4, size=128, seed=9, dtype=torch.bfloat16, verbose=True, H=None, W=None):
+    H, W = H or size, W or size
+    values, first, last = trained_variables(steps, B, size, H=H, W=W)
     rs = np.random.RandomState(seed)
-    img = rs.rand(B, size, size, 3).astype(np.float32)                 # a batch the variables have not seen
-    lab = labels_np(rs, B, size // 4, size // 4)
+    img = rs.rand(B, H, W, 3).astype(np.float32)                       # a batch the variables have not seen
+    lab = labels_np(rs, B, H // 4, W // 4)
     # ---- the emulating oracle: forward with every stored tensor tapped, backward
     em = torch.bfloat16 if dtype == torch.bfloat16 else None
     p64 = {k: torch.tensor(v, dtype=torch.float64, requires_grad=onet.is_trainable(k)) for k, v in values.items()}
@@ -114,7 +116,7 @@ def run(steps=60, B=4, size=128, seed=9, dtype=torch.bfloat16, verbose=True):
     out = {"rows": rows, "all_rel": rel(cat(got), cat(want)), "all_cos": cos(cat(got), cat(want)), "loss": float(losses[6]),
            "oracle_loss": float(total.detach()), "train_first": first, "train_last": last}
     if verbose:
-        print(f"variables after {steps} steps (total loss {first} -> {last}); batch of {B} @ {size}^2; teacher-forced backward of the "
+        print(f"variables after {steps} steps (total loss {first} -> {last}); batch of {B} @ {H}x{W}; teacher-forced backward of the "
               f"{'bf16' if dtype == torch.bfloat16 else 'f32'} build vs the {'emulating ' if em else ''}oracle: total loss {out['loss']:.5f} vs "
               f"{out['oracle_loss']:.5f}; ALL gradients rel-L2 {out['all_rel']:.4f}, cosine {out['all_cos']:.6f}")
         print("%-62s %9s %10s %8s %9s" % ("tensor", "size", "|g|", "rel-L2", "cosine"))
@@ -126,5 +128,5 @@ def run(steps=60, B=4, size=128, seed=9, dtype=torch.bfloat16, verbose=True):
 
 
 if __name__ == "__main__":
-    a = [int(x) for x in sys.argv[1:4]]
-    run(*a)
+    a = [int(x) for x in sys.argv[1:6]]
+    run(*a[:3], **dict(zip(("H", "W"), a[3:])))

@@ -56,11 +56,18 @@ def trained_variables(steps, B, H, W, seed=5, pool=3):
     return bb, head, first, last
 
 
-def run(steps=40, B=2, H=256, W=384, seed=9, dtype=torch.bfloat16, verbose=True):
+def run(steps=40, B=2, H=256, W=384, seed=9, dtype=torch.bfloat16, verbose=True, boxes=None, num=None):
+    """boxes ([B, N, 4] normalised (ymin, xmin, ymax, xmax)) and num ([B]): the held-out batch's boxes instead of random ones, to
+    choose which levels get a matched anchor; the training pool keeps its random boxes."""
     bb, hp, first, last = trained_variables(steps, B, H, W)
     rs = np.random.RandomState(seed)
     img = rs.rand(B, H, W, 3).astype(np.float32)                       # a batch the variables have not seen
-    boxes, num = groundtruth(rs, B)
+    assert (boxes is None) == (num is None)
+    if boxes is None:
+        boxes, num = groundtruth(rs, B)
+    else:
+        boxes, num = np.asarray(boxes, np.float32), np.asarray(num, np.int32)
+        assert boxes.shape[0] == B and boxes.shape[2] == 4 and num.shape == (B,) and int(num.max()) <= boxes.shape[1]
     anchors, _ = generate_anchors(H, W)
     tg = np.zeros((B, anchors.shape[0], 4), np.float32); mt = np.zeros((B, anchors.shape[0]), np.int32)
     for b in range(B):
