@@ -1252,6 +1252,114 @@ int mpn_zone_events(const void* record, const void* track_rows, int B, int max_b
                     const void* prev, void* next, void* out, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Motion trails: where each tracked identity has been - a ring of its last K anchors in device state - returned per person as
+ * a polyline, newest point first, and drawn into the annotated frames. tests/trails_ref.py is this definition as plain loops.
+ *
+ *   mpn_track_trails  record, track_rows, streams: as for mpn_zone_events (the header's total and counts, clamped the same way;
+ *                     only rows 0 .. total-1; of a row its box and keypoints; of a track row only int32 track_id at byte 0 of a
+ *                     24-byte row). B = streams * F, stream s owns images s*F .. s*F+F-1 in time order.
+ *                   PURE, as mpn_zone_events: the launch reads prev and writes the COMPLETE new state to next and the rows to
+ *                     out; it never writes prev, and running it twice in a row gives the same bytes. The caller advances the
+ *                     state by copying next over prev. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   By value: length K (1..64), the points a trail keeps; every (1..255), a point is kept once per `every`
+ *                     frames; max_gap (0 = never restart, else 1..65535), an identity not observed for more than max_gap frames
+ *                     starts a new trail; anchor (0 feet, 2 box_centre, anything else box_bottom); min_keypoint_score; height,
+ *                     width of the frames in the pixels of the keypoints; with_keypoints (0: the record has no keypoints, feet
+ *                     reads box_bottom).
+ *                   Anchor C of a row: exactly mpn_zone_events' rule - every operation one IEEE f64 operation in the order
+ *                     written there, without contraction, f32 inputs widened first; the ankles are joints 15 and 16 and one
+ *                     PASSES when score >= min_keypoint_score (a NaN never does); both pass: ((x15 + x16) * 0.5, (y15 + y16) *
+ *                     0.5); one passes: its (x, y); neither: box_bottom ((xmin + xmax) * 0.5 * width, ymax * height);
+ *                     box_centre ((xmin + xmax) * 0.5 * width, (ymin + ymax) * 0.5 * height). Each coordinate is then rounded
+ *                     ONCE to f32. A coordinate that is not finite before or after that rounding means NO ANCHOR: the output row
+ *                     is zero but for flag bit 2, the row takes no slot and touches no state.
+ *                   State, prev and next, mpn_track_trails_state_bytes(streams, K) bytes DEVICE, per stream 16 + 64 * (32 + 8*K)
+ *                     bytes: int32 frames, three zero words; then 64 slots (always 64, as in mpn_zone_events), each int32 id (0 =
+ *                     never used), last (the stream's frame number of the last observation, 0 = none), last_append (that of the
+ *                     last point kept), count (points in the ring, 0..K), head (the index of the newest), three zero words, then
+ *                     f32 ring[K][2] as (x, y). An all-zero state is the valid empty state. Frame numbers count from 1 and are
+ *                     NOT guarded against wrap. count and head of a state this launch did not write are clamped into range.
+ *                   Per frame j of the launch (0 <= j < F), now = prev.frames + j + 1:
+ *                     1. slots: mpn_zone_events' rule word for word. The image's rows with track_id > 0 and an anchor, serially
+ *                        in row order: the row takes the lowest slot with id == track_id; if an earlier row of this frame took
+ *                        that slot (two rows with one id), the row is handled as UNTRACKED. If no slot has the id, the row takes,
+ *                        among the slots no earlier row of this frame took, the one with the smallest `last` (as int32), the
+ *                        lowest index on a tie, and resets it to {id = track_id, every other word 0, the ring included}.
+ *                     2. restart: count > 0, max_gap > 0 and now - last > max_gap: every word of the slot but id becomes 0, the
+ *                        ring included; the row is RESTARTED (flag bit 4).
+ *                     3. append: count == 0 or now - last_append >= every: head = (count == 0) ? 0 : (head + 1) % K; ring[head] =
+ *                        C; count = min(count + 1, K); last_append = now; the row is APPENDED (flag bit 3).
+ *                     4. last = now.
+ *                     5. the row's points, newest first. Appended: ring[(head - i + K) % K] for i < count, n = count.
+ *                        Otherwise C, then those: n = count + 1 <= K + 1.
+ *                     6. every other row with an anchor (track_id <= 0, or the second of two rows with one id) is UNTRACKED:
+ *                        n = 1, points[0] = C, flag bit 0 clear; no state is touched.
+ *                     Slots that no row names are copied from prev to next unchanged; next.frames = prev.frames + F. A frame
+ *                     without detections still counts.
+ *                   out: mpn_track_trails_out_bytes(B, max_boxes, K) bytes DEVICE: B * max_boxes rows of 8 * (K + 2) bytes
+ *                     aligned with the record's rows 0 .. total-1, every row behind total zero: int32 n, uint32 flags (bit 0
+ *                     tracked: the row has a slot; bit 1 the anchor came from the ankles; bit 2 no anchor; bit 3 appended; bit 4
+ *                     restarted), f32 points[K + 1][2] as (x, y), zero behind n.
+ *                   Checked before any HIP call, the messages begin "track_trails:": null pointers, prev == next, length, every,
+ *                     max_gap outside their ranges, a non-finite height, width or min_keypoint_score (MPN_ERR_BAD_ARG);
+ *                     streams >= 1, B % streams == 0, 1 <= max_boxes <= 64, B * max_boxes <= 4096 (MPN_ERR_BAD_SHAPE); record
+ *                     16-byte, track_rows / prev / next / out 8-byte aligned (MPN_ERR_BAD_ALIGN). One block per stream: the
+ *                     grid depends on streams alone.
+ *   mpn_track_trails_state_bytes   streams * (16 + 64 * (32 + 8 * length)); 0 for arguments out of range.
+ *   mpn_track_trails_out_bytes     B * max_boxes * 8 * (length + 2); 0 for arguments out of range.
+ *
+ *   mpn_draw_trails   the rows of mpn_track_trails as polylines over the RGBA frames mpn_draw_detections / mpn_draw_tracks
+ *                     wrote, IN PLACE. descs: the same [B] mpn_draw_desc array; out_offset, h, w are read. record: the header's
+ *                     total and counts say which rows belong to which image (clamped to the record's capacity). track_rows: as
+ *                     above. trail_rows: mpn_track_trails' out for the same record and length; n is clamped to 0 .. length + 1.
+ *                   Draw order: per image, in record row order, every row with flag bit 0, n >= 2 and track_id > 0 is a
+ *                     polyline. Its segment s (0 <= s <= n-2) runs from points[s+1] to points[s]; segments are drawn OLDEST
+ *                     first: s = n-2, ..., 0. End points: each f32 coordinate clamped to +-2^29 (a NaN becomes -2^29), then
+ *                     truncated toward zero. The pixel set of a segment is exactly the `line` rule of mpn_draw_detections, from
+ *                     the first (older) point: end point included, a zero-length segment is one pixel, clipped to the frame per
+ *                     pixel.
+ *                   Ink: palette[(track_id - 1) % P] with alpha a_s = 255 without the fade flag, else
+ *                     a_s = 255 - (s * (255 - min_alpha)) / max(K - 1, 1) in integer division: the newest segment is opaque. A
+ *                     pixel of a segment becomes, per colour channel, BLEND8(a_s, pixel, ink): t = a_s*ink + (255 - a_s)*pixel +
+ *                     128; ((t >> 8) + t) >> 8; its alpha byte becomes 255. Segments are applied IN ORDER: a pixel that two
+ *                     segments cover is blended twice - the joint pixel every two neighbours share included. That is what
+ *                     Pillow draws with ImageDraw.Draw(rgb, 'RGBA').line([older, newer], fill=(r, g, b, a_s), width=1) once per
+ *                     segment (tests/test_trails_host.py holds the restatement against Pillow).
+ *                   tables: DEVICE, 4-byte aligned, tables_bytes >= MPN_DRAW_TRAILS_TABLE_HEADER_BYTES; int32 words: 0 flags
+ *                     (bit 0 fade), 1 min_alpha (clamped to 0..255), 2 K of the fade formula (clamped to 1..64), 3 P, the
+ *                     palette's size, 1..MPN_DRAW_TRACKS_MAX_PALETTE, 4 .. 3 + P the palette, one colour per word as
+ *                     mpn_draw_tracks packs it (R | G<<8 | B<<16). mpn_draw_trails_tables_bytes(P): 16 + 4*P rounded up to 16; 0
+ *                     out of range. The table is DATA: a palette that does not lie inside tables_bytes leaves every trail
+ *                     undrawn.
+ *                   In place: a pixel is read and written by exactly one thread, with 4-byte accesses - no scatter, no atomics on
+ *                     global memory; pixels no segment covers are neither read nor written. The launch is therefore NOT
+ *                     IDEMPOTENT with the fade flag (or wherever a_s < 255): run twice over the same frame it blends twice. In
+ *                     the Detector's graph it always follows a draw launch that rewrote the whole frame, so replaying the graph's
+ *                     device side is still harmless. An image whose descriptor reaches outside out_bytes, or has h, w outside
+ *                     what mpn_draw_detections accepts, is left alone.
+ *                   workspace: mpn_draw_trails_workspace_bytes(B, max_boxes, length) bytes (B * max_boxes * (48 * length + 32);
+ *                     0 out of range), 16-byte aligned. Two launches whose grids depend on (B, max_boxes, length) alone: build
+ *                     (a thread per row and segment: end points, bounding box, ink, alpha; and a bounding box per trail), then
+ *                     the raster, which culls per wave by the trail's box, then by the segment's.
+ *                   Checked before any HIP call, with mpn_draw_tracks' codes, the messages begin "draw_trails:": null pointers
+ *                     (MPN_ERR_BAD_ARG); 1 <= B <= 65535, 1 <= max_boxes <= MPN_DRAW_MAX_BOXES, B * max_boxes <= 4096,
+ *                     1 <= length <= 64 (MPN_ERR_BAD_SHAPE); descs, record, out_rgba, workspace 16-byte, track_rows, trail_rows,
+ *                     tables 4-byte aligned (MPN_ERR_BAD_ALIGN); record_bytes, workspace_bytes, out_bytes >= 16, tables_bytes >=
+ *                     the header (MPN_ERR_WORKSPACE).
+ */
+#define MPN_DRAW_TRAILS_TABLE_HEADER_BYTES 16
+size_t mpn_track_trails_state_bytes(int streams, int length);
+size_t mpn_track_trails_out_bytes(int B, int max_boxes, int length);
+int mpn_track_trails(const void* record, const void* track_rows, int B, int max_boxes, int streams, int length, int every,
+                     int max_gap, int anchor, double min_keypoint_score, double height, double width, int with_keypoints,
+                     const void* prev, void* next, void* out, mpn_stream_t stream);
+size_t mpn_draw_trails_tables_bytes(int palette_size);
+size_t mpn_draw_trails_workspace_bytes(int B, int max_boxes, int length);
+int mpn_draw_trails(const void* descs, const void* record, size_t record_bytes, const void* track_rows, const void* trail_rows,
+                    const void* tables, size_t tables_bytes, int B, int max_boxes, int length, uint8_t* out_rgba, size_t out_bytes,
+                    void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

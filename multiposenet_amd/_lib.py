@@ -167,6 +167,12 @@ SIGNATURES = {
     "mpn_zone_state_bytes": (_Z, [_I]),
     "mpn_zone_out_bytes": (_Z, [_I, _I]),
     "mpn_zone_events": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mpn_track_trails_state_bytes": (_Z, [_I, _I]),
+    "mpn_track_trails_out_bytes": (_Z, [_I, _I, _I]),
+    "mpn_track_trails": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _D, _D, _I, _P, _P, _P, _P]),
+    "mpn_draw_trails_tables_bytes": (_Z, [_I]),
+    "mpn_draw_trails_workspace_bytes": (_Z, [_I, _I, _I]),
+    "mpn_draw_trails": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _Z, _P]),
     "mpn_coco_masks_image_desc_bytes": (_Z, []),
     "mpn_coco_masks_part_desc_bytes": (_Z, []),
     "mpn_coco_masks_plane_words": (_Z, [_I, _I]),

@@ -141,11 +141,11 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval zones anonymize pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval trails zones anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the TrackEvaluator of track_eval= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
+    return_heatmaps; the TrackEvaluator of track_eval= or None; the TrackTrails of trails= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
     None; the PoseNms of pose_nms= or None (the last field, as ever)."""
     __slots__ = ()
 
@@ -171,12 +171,14 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
             key += ('track_eval', self.track_eval.serial)
         if self.zones is not None:
             key += ('zones', self.zones.serial)
+        if self.trails is not None:
+            key += ('trails', self.trails.serial)
         if self.anonymize is not None:
             key += ('anonymize', self.anonymize)
         return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None):
+def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None, trails=None):
     """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
     filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
     pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
@@ -185,7 +187,8 @@ def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None,
     track_eval (the entry's track_metrics.TrackEvaluator): a fifth slice, mpn_track_eval's rows behind everything else at the
     next multiple of 16 bytes; without it the four slices are returned, as ever. zones (the entry's zones.ZoneCounter): one
     more slice at the end of the tuple, mpn_zone_events' rows behind everything else at the next multiple of 16 bytes; without
-    it the function returns what it returns without the argument."""
+    it the function returns what it returns without the argument. trails (the entry's trails.TrackTrails): one more slice at
+    the very end, behind zones' slice, mpn_track_trails' rows at the next multiple of 16 bytes; likewise."""
     record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
     rows = record + (oks.out_bytes if oks is not None else 0)
     end = rows + (track.out_bytes(b) if track is not None else 0)
@@ -197,6 +200,9 @@ def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None,
     if zones is not None:
         at = (parts[-1].stop + 15) // 16 * 16
         parts += (slice(at, at + zones.out_bytes(b)),)
+    if trails is not None:
+        at = (parts[-1].stop + 15) // 16 * 16
+        parts += (slice(at, at + trails.out_bytes(b)),)
     return parts
 
 
@@ -206,11 +212,11 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the mpn_anonymize stage of an
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the trails of a `trails=` entry (a trails.TrackTrails, kept alive like the tracker), the mpn_anonymize stage of an
     `anonymize=` entry (an anonymize_stage.Anonymizer: it holds the anonymised frames the drawing reads), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones', 'trails')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -407,7 +413,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None, anonymize=None, zones=None, track_eval=None):
+                      pose_nms=None, anonymize=None, trails=None, zones=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -481,6 +487,14 @@ class Detector:
                 evaluator's state; the call advances it once, beside the tracker's. Every dict gains 'track_eval'
                 (`TrackEvaluator.unpack`: the frame's counts, per ground truth the matched id, flags and similarity, per
                 person the matched ground truth and flags); `evaluator.collect(outputs)` feeds `evaluate()`. None changes nothing.
+            trails: None, or a trails.TrackTrails (needs track=; its streams and max_boxes are the tracker's, its frame_size the
+                size of the frames): one mpn_track_trails launch behind the tracker's (and mpn_zone_events) inside the captured
+                graph - a graph of its own per TrackTrails - keeps every identity's last anchors over the record the tracker
+                read. The rows lie at the very end of the result buffer and arrive in the record's one copy; the launch only
+                reads the state, the call advances it once, beside the tracker's. Every dict gains 'trails'
+                (`TrackTrails.unpack`: per person its points, newest first, their count and flags). With annotate and
+                `trails.draw`, mpn_draw_trails blends the polylines into the annotated frame before it is encoded (not with
+                anonymize's overlay=False, which draws nothing). Coasting tracks add no points. None changes nothing.
             zones: None, or a zones.ZoneCounter (needs track=; the counter's streams and max_boxes are the tracker's, its
                 frame_size the size of the frames): one mpn_zone_events launch behind the tracker's inside the captured graph - a
                 graph of its own per counter - tests every kept person's anchor (the feet; without the PRN the box) against the
@@ -505,7 +519,7 @@ class Detector:
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -530,13 +544,15 @@ class Detector:
             ent.track_eval.commit()
         if ent.zones is not None:
             ent.zones.commit()
+        if ent.trails is not None:
+            ent.trails.commit()
         return self._finish(ent, outs, b, opts.return_heatmaps)
 
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, zones, anonymize (the
-        last four may be absent: None; anonymize is checked last, zones before it). shape(): the method's own
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, trails, zones, anonymize (the
+        last five may be absent: None; anonymize is checked last, zones before it, trails before zones). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
@@ -552,10 +568,12 @@ class Detector:
             raise ValueError("flip / scales average the keypoint subnet's heatmap outputs; this Detector has none")
         nms = self._check_pose_nms(given.get('pose_nms'))
         evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
-        counter = self._check_zones(given.get('zones'), given['track'], b, shaped[4].sizes if len(shaped) > 4 else [(h, w)])
+        sizes = shaped[4].sizes if len(shaped) > 4 else [(h, w)]
+        trails = self._check_trails(given.get('trails'), given['track'], b, sizes)
+        counter = self._check_zones(given.get('zones'), given['track'], b, sizes)
         spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], evaluator, counter, spec, nms), shaped
+                        given['return_heatmaps'], evaluator, trails, counter, spec, nms), shaped
 
     def _check_zones(self, counter, track, b, sizes):
         """The `zones` argument of the predict_* methods -> None or the ZoneCounter. sizes: (height, width) of the call's frames,
@@ -577,6 +595,27 @@ class Detector:
         counter.check_frame_sizes(sizes)
         counter.out_bytes(b)
         return counter
+
+    def _check_trails(self, trails, track, b, sizes):
+        """The `trails` argument of the predict_* methods -> None or the TrackTrails. sizes: (height, width) of the call's frames,
+        in whose pixels the record's keypoints are. Before any device work."""
+        if trails is None:
+            return None
+        from ..trails import TrackTrails
+        if not isinstance(trails, TrackTrails):
+            raise ValueError("trails must be None or a trails.TrackTrails")
+        if track is None:
+            raise ValueError("trails= follows the tracker's identities: it needs track=, a tracking.PoseTracker")
+        if trails.streams != track.streams:
+            raise ValueError(f"trails=: the trails were made for {trails.streams} streams, the tracker for {track.streams}")
+        if trails.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"trails=: the trails were made for max_boxes = {trails.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if torch.device(trails.device) != torch.device(self.net.device):
+            raise ValueError(f"trails=: the trails live on {trails.device}, this Detector on {self.net.device}")
+        trails.check_frame_sizes(sizes)
+        trails.out_bytes(b)
+        return trails
 
     def _check_anonymize(self, spec, annotate, track_style):
         """The `anonymize` argument of the predict_* methods -> None or the Anonymize. Before any device work."""
@@ -718,6 +757,11 @@ class Detector:
                 zone_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones)[-1]
                 for p, rows in zip(persons, ent.zones.unpack(record[zone_rows], counts)):
                     p['zones'] = rows
+            if ent.trails is not None:                              # mpn_track_trails' rows lie behind those: the same copy
+                trail_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones,
+                                           ent.trails)[-1]
+                for p, rows in zip(persons, ent.trails.unpack(record[trail_rows], counts)):
+                    p['trails'] = rows
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -777,6 +821,7 @@ class Detector:
         ent.track = opts.track
         ent.track_eval = opts.track_eval
         ent.zones = opts.zones
+        ent.trails = opts.trails
         if opts.pose_nms is not None:
             ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
         if opts.style:
@@ -812,6 +857,9 @@ class Detector:
         Pure in the same way: the caller commits.
         ent.zones (a zones.ZoneCounter, with track): mpn_zone_events follows the tracker's launches (and mpn_track_eval) over the record
         the tracker read and the tracker's rows; its rows lie behind everything else. Pure in the same way: the caller commits.
+        ent.trails (a trails.TrackTrails, with track): mpn_track_trails follows mpn_zone_events over the same record and rows; its
+        rows lie behind zones'. Pure in the same way: the caller commits. With draw and `trails.draw`, mpn_draw_trails follows
+        the drawing and blends the rows' polylines into its frames in place (not with anonymize's overlay=False).
         ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
         mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
         launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
@@ -847,7 +895,8 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones)
+        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones, ent.trails)
+        zone_rows = layout[-2] if ent.trails is not None else layout[-1]
         in_record, oks_rows, track_rows, nms_info = layout[:4]
         nbytes = in_record.stop
         if nbytes == 0:
@@ -873,7 +922,9 @@ class Detector:
             ent.track_eval.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[4]], b,
                                   *ent.oks.device_groundtruth())
         if ent.zones is not None:                                   # the record the tracker read and its rows; without the PRN: boxes
-            ent.zones.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]], b, self.assigner is not None)
+            ent.zones.launch(record, whole[track_rows][:track.track_bytes(b)], whole[zone_rows], b, self.assigner is not None)
+        if ent.trails is not None:                                  # likewise; its rows are the last part of the copy
+            ent.trails.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]], b, self.assigner is not None)
         dev['record'] = whole
         drawn = record
         if ent.anonymize is not None:                               # the drawing reads the anonymised frames in place of the sources
@@ -888,6 +939,10 @@ class Detector:
             dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, table, self.assigner is not None)
         elif annotate is not None:
             dev['annotated'] = annotate.launch(frames, drawn, drawn is not None and self.assigner is not None)
+        if annotate is not None and ent.trails is not None and ent.trails.draw and drawn is not None:
+            # the polylines over the frames just written, in place, before they are encoded
+            ent.trails.launch_draw(annotate.desc, record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]],
+                                   dev['annotated'], b)
         return self._encode_frames(dev, ent.encode)
 
     def _keypoint_pass(self, x):
@@ -915,8 +970,8 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, zones=None,
-                       track_eval=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, trails=None,
+                       zones=None, track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -960,7 +1015,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -974,7 +1029,7 @@ class Detector:
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
                       groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None,
-                      zones=None, track_eval=None):
+                      trails=None, zones=None, track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -1010,7 +1065,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -1051,6 +1106,8 @@ class Detector:
             ent.track_eval.commit()
         if ent.zones is not None:
             ent.zones.commit()
+        if ent.trails is not None:
+            ent.trails.commit()
         persons = self._finish(ent, outs, b, opts.return_heatmaps)
         if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):

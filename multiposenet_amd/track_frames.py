@@ -12,6 +12,8 @@
         [--anonymize-radius 8] [--anonymize-no-overlay]]
         [--annotations JSON [--eval-threshold 0.5]]
         [--zones FILE.json]
+        [--trails [LENGTH] [--trail-every N] [--trail-max-gap N] [--trail-anchor feet|box_bottom|box_centre] [--no-trail-fade]
+        [--no-trail-draw]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -43,7 +45,13 @@ polygons and across lines while it tracks (`zones=`, a `zones.ZoneCounter`: one 
 optionally, "anchor", "min_frames" and "min_keypoint_score". Every line gains "zones": per person the names of the zones it is
 inside ("inside") and its events ("entered", "exited", "crossed_positive", "crossed_negative"), and for the frame "occupancy",
 "entries", "exits", "line_positive" and "line_negative" by name; the summary gains the totals by name as "zones". A frame of
-another size than frame_size ends the run with a ValueError. Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+another size than frame_size ends the run with a ValueError. --trails [LENGTH] keeps the last LENGTH anchors of every tracked
+person on the device while it tracks (`trails=`, a `trails.TrackTrails`: one more launch in the same graph; alone it uses the
+class's default length, which is not tuned; the frames' size is that of the first frame, and a frame of another size ends the run
+with a ValueError). Every line gains "trail": per person its points (x, y), newest first, empty for a person without an id.
+With --frames-out the trails are drawn into the written frames in the persons' colours (`mpn_draw_trails`, two more launches),
+fading towards their old end unless --no-trail-fade; --no-trail-draw keeps them out of the frames. --trail-every N keeps one
+point per N frames, --trail-max-gap N starts a new trail for a person not seen for more than N frames (0: never). Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -107,6 +115,15 @@ def main(argv=None):
     ap.add_argument("--zones", metavar="FILE.json",
                     help="count the tracked persons in polygons and across lines: frame_size, named zones and lines, "
                          "optionally anchor, min_frames, min_keypoint_score")
+    ap.add_argument("--trails", metavar="LENGTH", type=int, nargs="?", const=-1, default=None,
+                    help="keep the last LENGTH anchors of every tracked person (alone: the class's default) and write them as \"trail\"")
+    ap.add_argument("--trail-every", metavar="N", type=int, default=None, help="keep one point per N frames (--trails)")
+    ap.add_argument("--trail-max-gap", metavar="N", type=int, default=None,
+                    help="a person not seen for more than N frames starts a new trail; 0: never (--trails)")
+    ap.add_argument("--trail-anchor", choices=("feet", "box_bottom", "box_centre"), default=None,
+                    help="the point that stands for a person (--trails)")
+    ap.add_argument("--no-trail-fade", action="store_true", help="draw every segment of a trail opaque (--trails, --frames-out)")
+    ap.add_argument("--no-trail-draw", action="store_true", help="keep the trails out of the written frames (--trails, --frames-out)")
     from . import pose_nms
     from .inference import anonymize_stage
     pose_nms.add_arguments(ap)
@@ -118,6 +135,17 @@ def main(argv=None):
     anon = anonymize_stage.from_arguments(ap, args)
     if anon is not None and args.frames_out is None:
         ap.error("--anonymize changes the frames --frames-out writes: it needs --frames-out DIR")
+    trail_options = None
+    if args.trails is None:
+        if args.trail_every is not None or args.trail_max_gap is not None or args.trail_anchor is not None or args.no_trail_fade \
+                or args.no_trail_draw:
+            ap.error("--trail-every, --trail-max-gap, --trail-anchor, --no-trail-fade and --no-trail-draw need --trails")
+    else:
+        trail_options = dict(fade=not args.no_trail_fade, draw=not args.no_trail_draw, min_keypoint_score=args.min_keypoint_score)
+        for key, value in (("length", None if args.trails == -1 else args.trails), ("every", args.trail_every), ("max_gap", args.trail_max_gap),
+                           ("anchor", args.trail_anchor)):
+            if value is not None:
+                trail_options[key] = value
     motion = None
     if args.motion:
         from .tracking import ConstantVelocity
@@ -183,6 +211,7 @@ def main(argv=None):
             counter = ZoneCounter(streams=1, max_boxes=det.params['max_boxes'], **spec)
         except ValueError as e:
             ap.error(str(e))
+    trails = None
     nobody = {'keypoints': np.zeros((0, 17, 3)), 'boxes': np.zeros((0, 4)), 'track_ids': np.zeros(0, np.int64)}
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -197,6 +226,20 @@ def main(argv=None):
                 scored = dict(groundtruth=[annotated.get(name, nobody) for name in batch], track_eval=evaluator)
             if counter is not None:
                 scored["zones"] = counter
+            if trail_options is not None and trails is None:       # the first frame says in whose pixels the trails are
+                from .trails import TrackTrails
+                if _is_jpeg(files[0]):
+                    from .inference.jpeg import jpeg_info
+                    info = jpeg_info(files[0])
+                    first_size = (info['height'], info['width'])
+                else:
+                    first_size = _pixels(files[0]).shape[:2]
+                try:
+                    trails = TrackTrails(streams=1, frame_size=first_size, max_boxes=det.params['max_boxes'], **trail_options)
+                except ValueError as e:
+                    ap.error(str(e))
+            if trails is not None:
+                scored["trails"] = trails
             if all(_is_jpeg(data) for data in files):
                 outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, pose_nms=nms,
                                         **draw, **scored)
@@ -225,6 +268,10 @@ def main(argv=None):
                                           for k, names_of in (("occupancy", counter.zone_names), ("entries", counter.zone_names),
                                                               ("exits", counter.zone_names), ("line_positive", counter.line_names),
                                                               ("line_negative", counter.line_names))})
+                if trails is not None:
+                    t = o["trails"]
+                    line["trail"] = [pts[:n].tolist() if tracked else []
+                                     for pts, n, tracked in zip(t["points"], t["count"], t["tracked"])]
                 out.write(json.dumps(line) + "\n")
                 if draw:
                     with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
@@ -245,6 +292,9 @@ def main(argv=None):
         summary["track_eval"] = dict(evaluator.evaluate(), threshold=evaluator.threshold, annotations=args.annotations)
     if counter is not None:
         summary["zones"] = dict(counter.totals(0), file=args.zones)
+    if trails is not None:
+        summary["trails"] = {"length": trails.length, "every": trails.every, "max_gap": trails.max_gap, "anchor": trails.anchor,
+                             "fade": trails.fade, "draw": trails.draw}
     print(json.dumps(summary))
     return state
 
