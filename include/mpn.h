@@ -1360,6 +1360,123 @@ int mpn_draw_trails(const void* descs, const void* record, size_t record_bytes, 
                     void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Density maps: where in the picture persons stand, and how much - two planes of counters over a grid of square cells in device
+ * state, dwell (person-frames per cell) and visits (arrivals of an identity in a cell) - returned per person as the cell it
+ * stands in and laid over the annotated frames as a colour wash. tests/density_ref.py is this definition as plain loops.
+ *
+ *   mpn_density_map   record, streams: as for mpn_track_trails (the header's total and counts, clamped the same way; only rows
+ *                     0 .. total-1; of a row its box and keypoints). track_rows: mpn_pose_track's rows for the record (of a row
+ *                     only int32 track_id at byte 0 of a 24-byte row), or NULL: no identities - every row is untracked, step 2
+ *                     is skipped and the visits plane only ages. B = streams * F, stream s owns images s*F .. s*F+F-1 in time
+ *                     order.
+ *                   PURE, as mpn_track_trails: the launch reads prev and writes the COMPLETE new state to next, the rows to out
+ *                     and the snapshots; it never writes prev, and running it twice in a row gives the same bytes. The caller
+ *                     advances the state by copying next over prev. prev == next is refused (MPN_ERR_BAD_ARG).
+ *                   By value: height, width of the frames in pixels (1..8192 each); cell, the side of a cell in pixels (4..256):
+ *                     the grid is gh = ceil(height / cell) rows of gw = ceil(width / cell) cells, G = gh * gw <= 16384, cell
+ *                     (r, c) has index r * gw + c; the last row and column may be ragged. footprint (0 anchor, 1 box); anchor
+ *                     (0 feet, 2 box_centre, anything else box_bottom); min_keypoint_score; with_keypoints (0: the record has
+ *                     no keypoints, feet reads box_bottom); half_life (0 = never, else 1..65535 frames); show (0 dwell, 1
+ *                     visits: the plane the snapshots copy; 1 needs track_rows).
+ *                   Anchor C of a row: exactly mpn_zone_events' rule, in f64, NOT rounded to f32 (csrc/person_anchor.h holds
+ *                     the rule for all three stages). A coordinate that is not finite means NO ANCHOR: the output row is
+ *                     {-1, -1, flag bit 2, 0}, the row takes no slot and adds nothing.
+ *                   The anchor's cell: the row is INSIDE when 0 <= Cx < width and 0 <= Cy < height (f64 comparisons); then
+ *                     col = (int)Cx / cell, row = (int)Cy / cell - truncation, then integer division - and k = row * gw + col.
+ *                     A row with an anchor that is not INSIDE is OUTSIDE (flag bit 3; row = col = -1).
+ *                   State, prev and next, mpn_density_state_bytes(streams, gh, gw) bytes DEVICE, per stream 32 + 64 * 16 + 8 * G
+ *                     bytes: int32 frames; uint32 max_dwell, max_visits; five zero words; then 64 slots (always 64, as in
+ *                     mpn_zone_events), each int32 id (0 = never used), last (the stream's frame number of the last observation,
+ *                     0 = none), cell1 (1 + the cell the identity was last seen INSIDE, 0 = none or OUTSIDE), one zero word; then
+ *                     uint32 dwell[G], then uint32 visits[G]. An all-zero state is the valid empty state. Frame numbers count
+ *                     from 1 and are NOT guarded against wrap.
+ *                   Per frame j of the launch (0 <= j < F), now = prev.frames + j + 1, in this order:
+ *                     1. halving: half_life > 0 and now % half_life == 0: every cell of both planes, max_dwell and max_visits
+ *                        become v >> 1. Stepwise, not exponential: between two halvings nothing ages.
+ *                     2. slots (not without track_rows): mpn_zone_events' rule word for word. The image's rows with
+ *                        track_id > 0 and an anchor, serially in row order: the row takes the lowest slot with id == track_id;
+ *                        if an earlier row of this frame took that slot (two rows with one id), the row is handled as
+ *                        UNTRACKED. If no slot has the id, the row takes, among the slots no earlier row of this frame took, the
+ *                        one with the smallest `last` (as int32), the lowest index on a tie, and resets it to {id = track_id,
+ *                        every other word 0}.
+ *                     3. a row with a slot (flag bit 0). INSIDE: when slot.cell1 != k + 1 the row is a VISIT (flag bit 4) and
+ *                        visits[k] takes a saturating + 1; then cell1 = k + 1. OUTSIDE: cell1 = 0 - coming back to the old cell
+ *                        is a visit again. In both cases last = now.
+ *                     4. dwell: every row with an anchor, tracked or not, adds a saturating + 1 to the cells of its footprint.
+ *                        anchor: INSIDE rows, cell k. box: every cell (r, c) with x0 <= (2*c + 1) * cell * 0.5 < x1 and
+ *                        y0 <= (2*r + 1) * cell * 0.5 < y1 - the cells whose centre the box covers - where x0 = xmin * width,
+ *                        x1 = xmax * width, y0 = ymin * height, y1 = ymax * height in f64 (f32 inputs widened first); a bound
+ *                        that is not finite adds nothing. Saturation is at 2^32 - 1; saturating adds commute, so the order of
+ *                        the rows does not matter.
+ *                     5. maxima: max_dwell = max(max_dwell, the new value of every cell step 4 added to); max_visits likewise
+ *                        over step 3. (For a state this launch wrote from the empty one they are the planes' maxima: max(v >> 1)
+ *                        == max(v) >> 1.)
+ *                     6. snapshot: with snapshots, the `show` plane as it now stands is copied to snapshots[image].
+ *                     Slots that no row names are copied from prev to next unchanged; next.frames = prev.frames + F. A frame
+ *                     without detections still counts.
+ *                   out: mpn_density_out_bytes(B, max_boxes) = B * max_boxes * 16 + B * 16 bytes DEVICE, 16-byte aligned:
+ *                     B * max_boxes person rows aligned with the record's rows 0 .. total-1, every row behind total zero: int32
+ *                     row, col (the anchor's cell, -1, -1 when it has none); uint32 flags (bit 0 tracked: the row has a slot;
+ *                     bit 1 the anchor came from the ankles; bit 2 no anchor; bit 3 outside; bit 4 visit); uint32 cells, the
+ *                     cells step 4 added to for this row. Behind them, per image: uint32 max_dwell, max_visits (after the
+ *                     frame), counted (the frame's rows with cells > 0), visits (the frame's VISIT rows).
+ *                   snapshots: NULL or mpn_density_snapshot_bytes(B, gh, gw) = B * G * 4 bytes DEVICE: uint32 [B][G].
+ *                   Checked before any HIP call, the messages begin "density_map:": null pointers other than track_rows and
+ *                     snapshots, prev == next, cell outside 4..256, height or width outside 1..8192, G > 16384, footprint not 0
+ *                     or 1, half_life outside 0..65535, show not 0 or 1, show == 1 without track_rows, a non-finite
+ *                     min_keypoint_score (MPN_ERR_BAD_ARG); streams >= 1, B % streams == 0, 1 <= max_boxes <= 64, B * max_boxes
+ *                     <= 4096 (MPN_ERR_BAD_SHAPE); record and out 16-byte, track_rows / prev / next / snapshots 8-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN). One block per stream: the grid depends on streams alone.
+ *   mpn_density_state_bytes      streams * (32 + 64 * 16 + 8 * gh * gw); 0 for arguments out of range (gh * gw > 16384).
+ *   mpn_density_out_bytes        B * max_boxes * 16 + B * 16; 0 for arguments out of range.
+ *   mpn_density_snapshot_bytes   B * gh * gw * 4; 0 for arguments out of range.
+ *
+ *   mpn_draw_density  the snapshots as a colour wash over the RGBA frames mpn_draw_detections / mpn_draw_tracks (and
+ *                     mpn_draw_trails) wrote, IN PLACE. descs: the same [B] mpn_draw_desc array; out_offset, h, w are read.
+ *                     snapshots, rows: mpn_density_map's snapshots and out for the same B, max_boxes, height, width and cell; of
+ *                     rows only the image rows are read.
+ *                   An image is LEFT ALONE when its descriptor has (h, w) != (height, width), reaches outside out_bytes (or is
+ *                     one mpn_draw_detections would not write), or when its M (below) is 0.
+ *                   tables: DEVICE, 4-byte aligned, tables_bytes >= MPN_DRAW_DENSITY_TABLE_BYTES = 32 + 1024; 32-bit words:
+ *                     0 int32 flags (bit 0 smooth; bit 1 the snapshots show visits: M is read from max_visits), 1 uint32
+ *                     full_scale, 2..7 zero, 8..263 the colours of levels 0..255 as R | G<<8 | B<<16 | A<<24. The host fills
+ *                     A[l] = (opacity * l + 127) / 255 and A[0] = 0. The table is DATA: the kernel clamps what it indexes with.
+ *                   Cell level: M = full_scale, or with full_scale == 0 the image row's maximum of the shown plane;
+ *                     L(cell) = min(255, (255 * v + M / 2) / M) in 64-bit integers.
+ *                   Pixel level without smooth: L(y / cell, x / cell). With smooth, bilinear between the cells' centres in
+ *                     integers, s = cell: u = 2*x + 1 - s; c0 = floor(u / (2*s)); fx = u - c0 * 2*s; c1 = c0 + 1; c0 and c1
+ *                     clamped to 0..gw-1; rows likewise from y: r0, r1, fy;
+ *                     level = (L00*(2s-fx)*(2s-fy) + L01*fx*(2s-fy) + L10*(2s-fx)*fy + L11*fx*fy + 2*s*s) / (4*s*s), Lrc the
+ *                     level of cell (r, c) named by r0/r1 and c0/c1. (Below 2^31 in 32-bit integers.)
+ *                   Blend: where A[level] > 0 every colour channel becomes BLEND8(A[level], pixel, ink[level]) as mpn_draw_trails
+ *                     defines it and the alpha byte becomes 255; other pixels keep their bytes. That is Pillow's
+ *                     frame.paste(colour_image, (0, 0), mask=alpha_image) on an RGB frame (tests/test_density_host.py holds the
+ *                     restatement against Pillow).
+ *                   In place: every pixel is read and written by exactly one thread, four pixels per 16-byte access; no scatter,
+ *                     no atomics. NOT IDEMPOTENT: run twice over the same frame it blends twice. In the Detector's graph it
+ *                     always follows a draw launch that rewrote the whole frame.
+ *                   workspace: mpn_draw_density_workspace_bytes(B, gh, gw) bytes (B * G rounded up to 16; 0 out of range),
+ *                     16-byte aligned: the levels as bytes [B][G]. Two launches whose grids depend on (B, height, width, gh, gw)
+ *                     alone: the levels (a thread per image and cell), then the raster.
+ *                   Checked before any HIP call, the messages begin "draw_density:": null pointers (MPN_ERR_BAD_ARG); 1 <= B <=
+ *                     65535, 1 <= max_boxes <= 64, B * max_boxes <= 4096, height, width, cell and G as above
+ *                     (MPN_ERR_BAD_SHAPE); descs, rows, out_rgba, workspace 16-byte, snapshots, tables 4-byte aligned
+ *                     (MPN_ERR_BAD_ALIGN); workspace_bytes, out_bytes >= 16, tables_bytes (MPN_ERR_WORKSPACE).
+ */
+#define MPN_DRAW_DENSITY_TABLE_BYTES 1056
+size_t mpn_density_state_bytes(int streams, int gh, int gw);
+size_t mpn_density_out_bytes(int B, int max_boxes);
+size_t mpn_density_snapshot_bytes(int B, int gh, int gw);
+int mpn_density_map(const void* record, const void* track_rows, int B, int max_boxes, int streams, int height, int width, int cell,
+                    int footprint, int anchor, double min_keypoint_score, int with_keypoints, int half_life, int show,
+                    const void* prev, void* next, void* out, void* snapshots, mpn_stream_t stream);
+size_t mpn_draw_density_tables_bytes(void);
+size_t mpn_draw_density_workspace_bytes(int B, int gh, int gw);
+int mpn_draw_density(const void* descs, const void* snapshots, const void* rows, const void* tables, size_t tables_bytes, int B,
+                     int max_boxes, int height, int width, int cell, uint8_t* out_rgba, size_t out_bytes, void* workspace,
+                     size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * The `masks` feature of a COCO keypoint record (the pixel work of the reference's data/create_tfrecords.py): the persons'
  * segmentations of a RAGGED batch of images -> per image the loss mask and the segmentation mask at full resolution ->
  * Lanczos4 to quarter size -> `> 0` -> packed bits. Three launches whatever the batch holds (zero, parts, finish); no

@@ -173,6 +173,13 @@ SIGNATURES = {
     "mpn_draw_trails_tables_bytes": (_Z, [_I]),
     "mpn_draw_trails_workspace_bytes": (_Z, [_I, _I, _I]),
     "mpn_draw_trails": (_I, [_P, _P, _Z, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P, _Z, _P]),
+    "mpn_density_state_bytes": (_Z, [_I, _I, _I]),
+    "mpn_density_out_bytes": (_Z, [_I, _I]),
+    "mpn_density_snapshot_bytes": (_Z, [_I, _I, _I]),
+    "mpn_density_map": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mpn_draw_density_tables_bytes": (_Z, []),
+    "mpn_draw_density_workspace_bytes": (_Z, [_I, _I, _I]),
+    "mpn_draw_density": (_I, [_P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P, _Z, _P, _Z, _P]),
     "mpn_coco_masks_image_desc_bytes": (_Z, []),
     "mpn_coco_masks_part_desc_bytes": (_Z, []),
     "mpn_coco_masks_plane_words": (_Z, [_I, _I]),

@@ -25,6 +25,7 @@
 //                                              nor written.
 //                      The Bresenham membership test is draw.hip's `line` rule, restated here on the same closed form.
 #include "common.h"
+#include "person_anchor.h"
 
 #pragma clang fp contract(off)
 
@@ -36,14 +37,13 @@ constexpr int kMaxRows = 4096;          // mpn_pose_gather's own limit on B * ma
 constexpr int kSlots = 64;              // always, as in mpn_zone_events: one lane of wave 0 per slot
 constexpr int kMaxLength = 64;          // K: ring entries per slot; one lane per segment in the raster
 constexpr int kTrailMaxBoxes = 64;      // mpn_track_trails: one lane of wave 0 per record row
-constexpr int kRowWords = 108, kOffBox = 1, kOffKeypoints = 57, kTrackRowBytes = 24, kTrackRowWords = 6;
-constexpr int kLeftAnkle = 15, kRightAnkle = 16;
+constexpr int kRowWords = 108, kTrackRowBytes = 24, kTrackRowWords = 6;
 // the state of one stream, in 32-bit words: {frames, 0, 0, 0}, then 64 slots of 8 + 2K words
 constexpr int kStateHeaderWords = 4, kSlotHeaderWords = 8;
 constexpr int kSlotId = 0, kSlotLast = 1, kSlotLastAppend = 2, kSlotCount = 3, kSlotHead = 4;
 constexpr int slot_words(int K) { return kSlotHeaderWords + 2 * K; }
 constexpr int stream_words(int K) { return kStateHeaderWords + kSlots * slot_words(K); }
-constexpr unsigned kFlagTracked = 1u, kFlagAnkles = 2u, kFlagNoAnchor = 4u, kFlagAppended = 8u, kFlagRestarted = 16u;
+constexpr unsigned kFlagTracked = 1u, kFlagNoAnchor = mpn_anchor::kFlagNoAnchor, kFlagAppended = 8u, kFlagRestarted = 16u;
 constexpr int trail_row_words(int K) { return 2 * (K + 2); }
 
 inline size_t header_words(int B) { return ((size_t)(2 * B + 2) + 3) / 4 * 4; }
@@ -59,7 +59,6 @@ struct TrailArgs {
     double min_score, height, width;
 };
 
-__device__ __forceinline__ bool finite64(double v) { return v - v == 0.0; }      // (inf - inf and nan - nan are nan)
 __device__ __forceinline__ bool finite32(float v) { return v - v == 0.0f; }
 
 __global__ __launch_bounds__(kThreads) void track_trails_kernel(TrailArgs a) {
@@ -105,28 +104,11 @@ __global__ __launch_bounds__(kThreads) void track_trails_kernel(TrailArgs a) {
             float fx = 0.0f, fy = 0.0f;
             int id = 0;
             if (lane < n) {
-                const float* row = a.rows + (size_t)(first + lane) * kRowWords;
-                const double ymin = (double)row[kOffBox], xmin = (double)row[kOffBox + 1];
-                const double ymax = (double)row[kOffBox + 2], xmax = (double)row[kOffBox + 3];
-                const float* la = row + kOffKeypoints + 3 * kLeftAnkle;
-                const float* ra = row + kOffKeypoints + 3 * kRightAnkle;
-                const bool left = a.anchor_mode == 0 && (double)la[2] >= a.min_score;
-                const bool right = a.anchor_mode == 0 && (double)ra[2] >= a.min_score;
                 double cx, cy;
-                if (left && right) {
-                    cx = ((double)la[0] + (double)ra[0]) * 0.5;
-                    cy = ((double)la[1] + (double)ra[1]) * 0.5;
-                } else if (left) {
-                    cx = (double)la[0]; cy = (double)la[1];
-                } else if (right) {
-                    cx = (double)ra[0]; cy = (double)ra[1];
-                } else {
-                    cx = (xmin + xmax) * 0.5 * a.width;
-                    cy = a.anchor_mode == 2 ? (ymin + ymax) * 0.5 * a.height : ymax * a.height;
-                }
-                flags = (left || right) ? kFlagAnkles : 0u;
+                flags = mpn_anchor::person_anchor(a.rows + (size_t)(first + lane) * kRowWords, a.anchor_mode, a.min_score, a.height,
+                                                  a.width, cx, cy);
                 fx = (float)cx; fy = (float)cy;                   // the one rounding to f32
-                if (!finite64(cx) || !finite64(cy) || !finite32(fx) || !finite32(fy)) { flags = kFlagNoAnchor; fx = 0.0f; fy = 0.0f; }
+                if ((flags & kFlagNoAnchor) || !finite32(fx) || !finite32(fy)) { flags = kFlagNoAnchor; fx = 0.0f; fy = 0.0f; }
                 id = *(const int*)(a.track_rows + (size_t)(first + lane) * kTrackRowBytes);
                 if (id < 0 || (flags & kFlagNoAnchor)) id = 0;
             }

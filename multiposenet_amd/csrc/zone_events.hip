@@ -13,6 +13,7 @@
 //            person rows; a ballot per zone and line for the image row and the cumulative counters
 // Latency-bound glue like mpn_pose_smooth (microseconds behind a network pass of milliseconds): not tuned beyond that.
 #include "common.h"
+#include "person_anchor.h"
 
 #pragma clang fp contract(off)
 
@@ -24,8 +25,7 @@ constexpr int kMaxRows = 4096;          // mpn_pose_gather's own limit on B * ma
 constexpr int kSlots = 64;              // always: mpn_pose_track's largest table; one lane of wave 0 per slot
 constexpr int kMaxZones = 16, kMaxLines = 16, kMaxVertices = 16;
 // the record's row (pose_gather.hip), in 32-bit words; a row of mpn_pose_track's out in bytes (track_id first)
-constexpr int kRowWords = 108, kOffBox = 1, kOffKeypoints = 57, kTrackRowBytes = 24;
-constexpr int kLeftAnkle = 15, kRightAnkle = 16;
+constexpr int kRowWords = 108, kTrackRowBytes = 24;
 // the table, in bytes
 constexpr int kTabHeight = 16, kTabCounts = 40, kTabVertices = 104, kTabLines = kTabVertices + kMaxZones * kMaxVertices * 16;
 constexpr int kTableBytes = kTabLines + kMaxLines * 32;                                  // 4712
@@ -37,7 +37,7 @@ constexpr int kStreamWords = kOffSlots + kSlots * kSlotWords;                   
 static_assert(kStreamWords % 2 == 0 && kOffSlots % 2 == 0 && kSlotWords % 2 == 0, "the anchors are aligned doubles");
 // the output rows, in bytes: a person row {inside, entered, exited, positive, negative, flags; f64 anchor[2]; int32 dwell[16]}
 constexpr int kPersonBytes = 104, kPersonWords = kPersonBytes / 4, kImageWords = 9 * 16, kImageBytes = kImageWords * 4;
-constexpr unsigned kFlagTracked = 1u, kFlagAnkles = 2u, kFlagNoAnchor = 4u;
+constexpr unsigned kFlagTracked = 1u, kFlagNoAnchor = mpn_anchor::kFlagNoAnchor;     // (bit 1: the anchor came from the ankles)
 
 inline size_t header_words(int B) { return ((size_t)(2 * B + 2) + 3) / 4 * 4; }
 
@@ -51,8 +51,6 @@ struct ZoneArgs {
     unsigned char* out;
     int B, max_boxes, streams;
 };
-
-__device__ __forceinline__ bool finite64(double v) { return v - v == 0.0; }      // (inf - inf and nan - nan are nan)
 
 __global__ __launch_bounds__(kThreads) void zone_events_kernel(ZoneArgs a) {
     __shared__ double state64[kStreamWords / 2];                  // the stream's state, addressed in words below
@@ -123,26 +121,8 @@ __global__ __launch_bounds__(kThreads) void zone_events_kernel(ZoneArgs a) {
         if (wave == 0) {
             int id = 0;
             if (lane < n) {
-                const float* row = a.rows + (size_t)(first + lane) * kRowWords;
-                const double ymin = (double)row[kOffBox], xmin = (double)row[kOffBox + 1];
-                const double ymax = (double)row[kOffBox + 2], xmax = (double)row[kOffBox + 3];
-                const float* la = row + kOffKeypoints + 3 * kLeftAnkle;
-                const float* ra = row + kOffKeypoints + 3 * kRightAnkle;
-                const bool left = anchor_mode == 0 && (double)la[2] >= min_score;
-                const bool right = anchor_mode == 0 && (double)ra[2] >= min_score;
-                if (left && right) {
-                    cx = ((double)la[0] + (double)ra[0]) * 0.5;
-                    cy = ((double)la[1] + (double)ra[1]) * 0.5;
-                } else if (left) {
-                    cx = (double)la[0]; cy = (double)la[1];
-                } else if (right) {
-                    cx = (double)ra[0]; cy = (double)ra[1];
-                } else {
-                    cx = (xmin + xmax) * 0.5 * width;
-                    cy = anchor_mode == 2 ? (ymin + ymax) * 0.5 * height : ymax * height;
-                }
-                flags = (left || right) ? kFlagAnkles : 0u;
-                if (!finite64(cx) || !finite64(cy)) { flags = kFlagNoAnchor; cx = 0.0; cy = 0.0; }
+                flags = mpn_anchor::person_anchor(a.rows + (size_t)(first + lane) * kRowWords, anchor_mode, min_score, height, width,
+                                                  cx, cy);
                 id = *(const int*)(a.track_rows + (size_t)(first + lane) * kTrackRowBytes);
                 if (id < 0 || (flags & kFlagNoAnchor)) id = 0;
             }

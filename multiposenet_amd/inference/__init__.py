@@ -9,3 +9,4 @@ from ..pose_nms import PoseNms, PoseSuppressor, pose_nms  # noqa: F401
 from ..track_metrics import TrackEvaluator, groundtruth_from_posetrack  # noqa: F401
 from ..zones import ZoneCounter  # noqa: F401
 from ..trails import TrackTrails, draw_trails  # noqa: F401
+from ..density import DensityMap, draw_density  # noqa: F401

@@ -141,11 +141,11 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval trails zones anonymize pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval density trails zones anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
     (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the TrackEvaluator of track_eval= or None; the TrackTrails of trails= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
+    return_heatmaps; the TrackEvaluator of track_eval= or None; the DensityMap of density= or None; the TrackTrails of trails= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
     None; the PoseNms of pose_nms= or None (the last field, as ever)."""
     __slots__ = ()
 
@@ -173,12 +173,14 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
             key += ('zones', self.zones.serial)
         if self.trails is not None:
             key += ('trails', self.trails.serial)
+        if self.density is not None:
+            key += ('density', self.density.serial)
         if self.anonymize is not None:
             key += ('anonymize', self.anonymize)
         return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None, trails=None):
+def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None, trails=None, density=None):
     """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
     filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
     pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
@@ -188,7 +190,8 @@ def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None,
     next multiple of 16 bytes; without it the four slices are returned, as ever. zones (the entry's zones.ZoneCounter): one
     more slice at the end of the tuple, mpn_zone_events' rows behind everything else at the next multiple of 16 bytes; without
     it the function returns what it returns without the argument. trails (the entry's trails.TrackTrails): one more slice at
-    the very end, behind zones' slice, mpn_track_trails' rows at the next multiple of 16 bytes; likewise."""
+    the very end, behind zones' slice, mpn_track_trails' rows at the next multiple of 16 bytes; likewise. density (the entry's density.DensityMap): one more
+    slice at the very end, behind the trails' slice, mpn_density_map's rows at the next multiple of 16 bytes; likewise."""
     record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
     rows = record + (oks.out_bytes if oks is not None else 0)
     end = rows + (track.out_bytes(b) if track is not None else 0)
@@ -203,6 +206,9 @@ def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None,
     if trails is not None:
         at = (parts[-1].stop + 15) // 16 * 16
         parts += (slice(at, at + trails.out_bytes(b)),)
+    if density is not None:
+        at = (parts[-1].stop + 15) // 16 * 16
+        parts += (slice(at, at + density.out_bytes(b)),)
     return parts
 
 
@@ -212,11 +218,11 @@ class _Entry:
     it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
     ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
     entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the trails of a `trails=` entry (a trails.TrackTrails, kept alive like the tracker), the mpn_anonymize stage of an
+    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the trails of a `trails=` entry (a trails.TrackTrails, kept alive like the tracker), the map of a `density=` entry (a density.DensityMap, kept alive like the tracker), the mpn_anonymize stage of an
     `anonymize=` entry (an anonymize_stage.Anonymizer: it holds the anonymised frames the drawing reads), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
     stays None."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones', 'trails')
+                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones', 'trails', 'density')
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -413,7 +419,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None, anonymize=None, trails=None, zones=None, track_eval=None):
+                      pose_nms=None, anonymize=None, density=None, trails=None, zones=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -495,6 +501,15 @@ class Detector:
                 (`TrackTrails.unpack`: per person its points, newest first, their count and flags). With annotate and
                 `trails.draw`, mpn_draw_trails blends the polylines into the annotated frame before it is encoded (not with
                 anonymize's overlay=False, which draws nothing). Coasting tracks add no points. None changes nothing.
+            density: None, or a density.DensityMap (track= is optional; with it the map's streams are the tracker's; its
+                max_boxes is the Detector's, its frame_size the size of the frames): one mpn_density_map launch behind the tracker's
+                (and mpn_track_trails) inside the captured graph - a graph of its own per DensityMap - adds every kept person to
+                the cell it stands in: the dwell plane, and with track= the visits plane. The rows lie at the very end of the
+                result buffer and arrive in the record's one copy; the launch only reads the state, the call advances it once,
+                beside the tracker's. Every dict gains 'density' (`DensityMap.unpack`: per person its cell and flags, per frame the
+                maxima and counts); `density.grid()` reads a plane. With annotate and `density.draw`, mpn_draw_density blends
+                the map over the annotated frame before it is encoded (not with anonymize's overlay=False, which draws nothing).
+                Persons below score_threshold and coasting tracks are not counted. None changes nothing.
             zones: None, or a zones.ZoneCounter (needs track=; the counter's streams and max_boxes are the tracker's, its
                 frame_size the size of the frames): one mpn_zone_events launch behind the tracker's inside the captured graph - a
                 graph of its own per counter - tests every kept person's anchor (the feet; without the PRN the box) against the
@@ -519,7 +534,7 @@ class Detector:
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -546,13 +561,15 @@ class Detector:
             ent.zones.commit()
         if ent.trails is not None:
             ent.trails.commit()
+        if ent.density is not None:
+            ent.density.commit()
         return self._finish(ent, outs, b, opts.return_heatmaps)
 
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
         returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, trails, zones, anonymize (the
-        last five may be absent: None; anonymize is checked last, zones before it, trails before zones). shape(): the method's own
+        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, density, trails, zones, anonymize (the
+        last six may be absent: None; anonymize is checked last, zones before it, trails before zones, density before trails). shape(): the method's own
         checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
         (b, height, width) of the network input."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
@@ -569,11 +586,12 @@ class Detector:
         nms = self._check_pose_nms(given.get('pose_nms'))
         evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
         sizes = shaped[4].sizes if len(shaped) > 4 else [(h, w)]
+        density = self._check_density(given.get('density'), given['track'], b, sizes)
         trails = self._check_trails(given.get('trails'), given['track'], b, sizes)
         counter = self._check_zones(given.get('zones'), given['track'], b, sizes)
         spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], evaluator, trails, counter, spec, nms), shaped
+                        given['return_heatmaps'], evaluator, density, trails, counter, spec, nms), shaped
 
     def _check_zones(self, counter, track, b, sizes):
         """The `zones` argument of the predict_* methods -> None or the ZoneCounter. sizes: (height, width) of the call's frames,
@@ -616,6 +634,29 @@ class Detector:
         trails.check_frame_sizes(sizes)
         trails.out_bytes(b)
         return trails
+
+    def _check_density(self, density, track, b, sizes):
+        """The `density` argument of the predict_* methods -> None or the DensityMap. sizes: (height, width) of the call's frames,
+        in whose pixels the record's keypoints are. Before any device work."""
+        if density is None:
+            return None
+        from ..density import DensityMap
+        if not isinstance(density, DensityMap):
+            raise ValueError("density must be None or a density.DensityMap")
+        if self.retinanet is None:
+            raise ValueError("density= counts the persons of the record: this Detector has no person detector")
+        if track is None and density.show == 'visits':
+            raise ValueError("density=: show='visits' counts the arrivals of identities: it needs track=, a tracking.PoseTracker")
+        if track is not None and density.streams != track.streams:
+            raise ValueError(f"density=: the map was made for {density.streams} streams, the tracker for {track.streams}")
+        if density.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"density=: the map was made for max_boxes = {density.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if torch.device(density.device) != torch.device(self.net.device):
+            raise ValueError(f"density=: the map lives on {density.device}, this Detector on {self.net.device}")
+        density.check_frame_sizes(sizes)
+        density.out_bytes(b)
+        return density
 
     def _check_anonymize(self, spec, annotate, track_style):
         """The `anonymize` argument of the predict_* methods -> None or the Anonymize. Before any device work."""
@@ -762,6 +803,11 @@ class Detector:
                                            ent.trails)[-1]
                 for p, rows in zip(persons, ent.trails.unpack(record[trail_rows], counts)):
                     p['trails'] = rows
+            if ent.density is not None:                             # mpn_density_map's rows lie behind those: the same copy
+                density_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones,
+                                             ent.trails, ent.density)[-1]
+                for p, rows in zip(persons, ent.density.unpack(record[density_rows], counts)):
+                    p['density'] = rows
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -822,6 +868,7 @@ class Detector:
         ent.track_eval = opts.track_eval
         ent.zones = opts.zones
         ent.trails = opts.trails
+        ent.density = opts.density
         if opts.pose_nms is not None:
             ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
         if opts.style:
@@ -857,6 +904,10 @@ class Detector:
         Pure in the same way: the caller commits.
         ent.zones (a zones.ZoneCounter, with track): mpn_zone_events follows the tracker's launches (and mpn_track_eval) over the record
         the tracker read and the tracker's rows; its rows lie behind everything else. Pure in the same way: the caller commits.
+        ent.density (a density.DensityMap, with or without track): mpn_density_map follows mpn_track_trails over the same record
+        (and, with track, the tracker's rows); its rows lie behind the trails'. Pure in the same way: the caller commits. With draw
+        and `density.draw`, mpn_draw_density follows mpn_draw_trails and blends the map into the frames in place (not with
+        anonymize's overlay=False).
         ent.trails (a trails.TrackTrails, with track): mpn_track_trails follows mpn_zone_events over the same record and rows; its
         rows lie behind zones'. Pure in the same way: the caller commits. With draw and `trails.draw`, mpn_draw_trails follows
         the drawing and blends the rows' polylines into its frames in place (not with anonymize's overlay=False).
@@ -895,13 +946,16 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones, ent.trails)
+        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones, ent.trails, ent.density)
+        density_rows = layout[-1]                                   # (the end of the copy either way)
+        if ent.density is not None:                                 # the slices in front of the map's are what they are without it
+            layout = layout[:-1]
         zone_rows = layout[-2] if ent.trails is not None else layout[-1]
         in_record, oks_rows, track_rows, nms_info = layout[:4]
         nbytes = in_record.stop
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        whole = torch.empty(layout[-1].stop, dtype=torch.uint8, device=net.device)
+        whole = torch.empty(density_rows.stop, dtype=torch.uint8, device=net.device)
         filtered = whole[in_record]
         record = ent.nms.raw if ent.nms is not None else filtered    # what the gather writes
         if extent is None:
@@ -925,6 +979,11 @@ class Detector:
             ent.zones.launch(record, whole[track_rows][:track.track_bytes(b)], whole[zone_rows], b, self.assigner is not None)
         if ent.trails is not None:                                  # likewise; its rows are the last part of the copy
             ent.trails.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]], b, self.assigner is not None)
+        density_drawn = (ent.density is not None and annotate is not None and ent.density.draw and
+                         (ent.anonymize is None or ent.anonymize.spec.overlay))
+        if ent.density is not None:                                 # the same record; identities where there is a tracker
+            ent.density.launch(record, whole[track_rows][:track.track_bytes(b)] if track is not None else None, whole[density_rows],
+                               b, self.assigner is not None, ent.density.snapshots(b) if density_drawn else None)
         dev['record'] = whole
         drawn = record
         if ent.anonymize is not None:                               # the drawing reads the anonymised frames in place of the sources
@@ -943,6 +1002,8 @@ class Detector:
             # the polylines over the frames just written, in place, before they are encoded
             ent.trails.launch_draw(annotate.desc, record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]],
                                    dev['annotated'], b)
+        if density_drawn:                                           # the map over everything drawn so far, in place
+            ent.density.launch_draw(annotate.desc, ent.density.snapshots(b), whole[density_rows], dev['annotated'], b)
         return self._encode_frames(dev, ent.encode)
 
     def _keypoint_pass(self, x):
@@ -970,8 +1031,8 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, trails=None,
-                       zones=None, track_eval=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, density=None,
+                       trails=None, zones=None, track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -1015,7 +1076,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -1029,7 +1090,7 @@ class Detector:
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
                       groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None,
-                      trails=None, zones=None, track_eval=None):
+                      density=None, trails=None, zones=None, track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -1065,7 +1126,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -1108,6 +1169,8 @@ class Detector:
             ent.zones.commit()
         if ent.trails is not None:
             ent.trails.commit()
+        if ent.density is not None:
+            ent.density.commit()
         persons = self._finish(ent, outs, b, opts.return_heatmaps)
         if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):

@@ -14,6 +14,8 @@
         [--zones FILE.json]
         [--trails [LENGTH] [--trail-every N] [--trail-max-gap N] [--trail-anchor feet|box_bottom|box_centre] [--no-trail-fade]
         [--no-trail-draw]]
+        [--density [CELL] [--density-footprint anchor|box] [--density-half-life N] [--density-show dwell|visits]
+        [--density-full-scale N] [--density-opacity A] [--no-density-smooth] [--no-density-draw] [--density-out FILE.npz]]
 
 The image files of DIR, in sorted name order, are the frames of ONE stream. They go through the Detector in batches of
 --batch consecutive frames with `track=` a `tracking.PoseTracker`: the matching runs inside the captured graph and the track
@@ -51,7 +53,15 @@ class's default length, which is not tuned; the frames' size is that of the firs
 with a ValueError). Every line gains "trail": per person its points (x, y), newest first, empty for a person without an id.
 With --frames-out the trails are drawn into the written frames in the persons' colours (`mpn_draw_trails`, two more launches),
 fading towards their old end unless --no-trail-fade; --no-trail-draw keeps them out of the frames. --trail-every N keeps one
-point per N frames, --trail-max-gap N starts a new trail for a person not seen for more than N frames (0: never). Without model files the weights are seeded random ones: the output then only shows that the path runs."""
+point per N frames, --trail-max-gap N starts a new trail for a person not seen for more than N frames (0: never). --density [CELL] accumulates where the persons stand over a grid of CELL x CELL pixel cells on the device while
+it tracks (`density=`, a `density.DensityMap`: one more launch in the same graph; alone it uses the class's default cell, which is
+not tuned; the frames' size is that of the first frame, and a frame of another size ends the run with a ValueError). Every line
+gains "density": per person its "cell" (row, col; -1, -1 outside the frame) and the frame's "counted", "visits", "max_dwell" and
+"max_visits". With --frames-out the map is laid over the written frames (`mpn_draw_density`, two more launches) unless
+--no-density-draw: --density-show says which plane, --density-full-scale N the count at which the colour saturates (0: each
+frame's own maximum), --density-opacity A the alpha of the highest level, --no-density-smooth draws whole cells.
+--density-footprint box adds a person to every cell whose centre its box covers, --density-half-life N halves every counter
+once per N frames (0: never). --density-out FILE.npz writes the final "dwell" and "visits" planes and "cell". Without model files the weights are seeded random ones: the output then only shows that the path runs."""
 import argparse
 import json
 import os
@@ -124,6 +134,22 @@ def main(argv=None):
                     help="the point that stands for a person (--trails)")
     ap.add_argument("--no-trail-fade", action="store_true", help="draw every segment of a trail opaque (--trails, --frames-out)")
     ap.add_argument("--no-trail-draw", action="store_true", help="keep the trails out of the written frames (--trails, --frames-out)")
+    ap.add_argument("--density", metavar="CELL", type=int, nargs="?", const=-1, default=None,
+                    help="accumulate where the persons stand over cells of CELL x CELL pixels (alone: the class's default) and "
+                         "write each person's cell as \"density\"")
+    ap.add_argument("--density-footprint", choices=("anchor", "box"), default=None,
+                    help="a person adds to its anchor's cell, or to every cell whose centre its box covers (--density)")
+    ap.add_argument("--density-half-life", metavar="N", type=int, default=None,
+                    help="halve every counter once per N frames; 0: never (--density)")
+    ap.add_argument("--density-show", choices=("dwell", "visits"), default=None, help="the plane the frames show (--density)")
+    ap.add_argument("--density-full-scale", metavar="N", type=int, default=None,
+                    help="the count at which the colour saturates; 0: each frame's own maximum (--density, --frames-out)")
+    ap.add_argument("--density-opacity", metavar="A", type=int, default=None,
+                    help="the alpha of the highest level, 0..255 (--density, --frames-out)")
+    ap.add_argument("--no-density-smooth", action="store_true", help="draw whole cells (--density, --frames-out)")
+    ap.add_argument("--no-density-draw", action="store_true", help="keep the map out of the written frames (--density, --frames-out)")
+    ap.add_argument("--density-out", metavar="FILE.npz", default=None,
+                    help="write the final dwell and visits planes and the cell size (--density)")
     from . import pose_nms
     from .inference import anonymize_stage
     pose_nms.add_arguments(ap)
@@ -146,6 +172,21 @@ def main(argv=None):
                            ("anchor", args.trail_anchor)):
             if value is not None:
                 trail_options[key] = value
+    density_options = None
+    if args.density is None:
+        if args.density_footprint is not None or args.density_half_life is not None or args.density_show is not None or \
+                args.density_full_scale is not None or args.density_opacity is not None or args.no_density_smooth or \
+                args.no_density_draw or args.density_out is not None:
+            ap.error("--density-footprint, --density-half-life, --density-show, --density-full-scale, --density-opacity, "
+                     "--no-density-smooth, --no-density-draw and --density-out need --density")
+    else:
+        density_options = dict(smooth=not args.no_density_smooth, draw=not args.no_density_draw,
+                               min_keypoint_score=args.min_keypoint_score)
+        for key, value in (("cell", None if args.density == -1 else args.density), ("footprint", args.density_footprint),
+                           ("half_life", args.density_half_life), ("show", args.density_show), ("full_scale", args.density_full_scale),
+                           ("opacity", args.density_opacity)):
+            if value is not None:
+                density_options[key] = value
     motion = None
     if args.motion:
         from .tracking import ConstantVelocity
@@ -211,7 +252,7 @@ def main(argv=None):
             counter = ZoneCounter(streams=1, max_boxes=det.params['max_boxes'], **spec)
         except ValueError as e:
             ap.error(str(e))
-    trails = None
+    trails = density = None
     nobody = {'keypoints': np.zeros((0, 17, 3)), 'boxes': np.zeros((0, 4)), 'track_ids': np.zeros(0, np.int64)}
     frames = persons = 0
     with open(args.out, "w") as out:
@@ -226,14 +267,24 @@ def main(argv=None):
                 scored = dict(groundtruth=[annotated.get(name, nobody) for name in batch], track_eval=evaluator)
             if counter is not None:
                 scored["zones"] = counter
-            if trail_options is not None and trails is None:       # the first frame says in whose pixels the trails are
-                from .trails import TrackTrails
-                if _is_jpeg(files[0]):
+            if (trail_options is not None and trails is None) or (density_options is not None and density is None):
+                if _is_jpeg(files[0]):                              # the first frame says in whose pixels trails and map are
                     from .inference.jpeg import jpeg_info
                     info = jpeg_info(files[0])
                     first_size = (info['height'], info['width'])
                 else:
                     first_size = _pixels(files[0]).shape[:2]
+            if density_options is not None and density is None:
+                from .density import DensityMap
+                try:
+                    density = DensityMap(streams=1, frame_size=tuple(int(v) for v in first_size), max_boxes=det.params['max_boxes'],
+                                         **density_options)
+                except ValueError as e:
+                    ap.error(str(e))
+            if density is not None:
+                scored["density"] = density
+            if trail_options is not None and trails is None:
+                from .trails import TrackTrails
                 try:
                     trails = TrackTrails(streams=1, frame_size=first_size, max_boxes=det.params['max_boxes'], **trail_options)
                 except ValueError as e:
@@ -272,6 +323,10 @@ def main(argv=None):
                     t = o["trails"]
                     line["trail"] = [pts[:n].tolist() if tracked else []
                                      for pts, n, tracked in zip(t["points"], t["count"], t["tracked"])]
+                if density is not None:
+                    d = o["density"]
+                    line["density"] = {"cell": d["cell"].tolist(), "counted": d["counted"], "visits": d["visits"],
+                                       "max_dwell": d["max_dwell"], "max_visits": d["max_visits"]}
                 out.write(json.dumps(line) + "\n")
                 if draw:
                     with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
@@ -295,6 +350,13 @@ def main(argv=None):
     if trails is not None:
         summary["trails"] = {"length": trails.length, "every": trails.every, "max_gap": trails.max_gap, "anchor": trails.anchor,
                              "fade": trails.fade, "draw": trails.draw}
+    if density is not None:
+        summary["density"] = {"cell": density.cell, "grid": [density.gh, density.gw], "footprint": density.footprint,
+                              "half_life": density.half_life, "show": density.show, "draw": density.draw,
+                              "max_dwell": int(density.state(0)["max_dwell"]), "max_visits": int(density.state(0)["max_visits"])}
+        if args.density_out is not None:
+            np.savez(args.density_out, dwell=density.grid(0, "dwell"), visits=density.grid(0, "visits"), cell=np.int32(density.cell))
+            summary["density"]["out"] = args.density_out
     print(json.dumps(summary))
     return state
 
