@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _lib
 from .pose_metrics import fill_record
+from .stream_state import StreamState, choice, flag, integer
 from .zones import ANCHORS, MAX_BOXES, SLOTS, track_rows_of
 
 MIN_CELL, MAX_CELL, MAX_SIDE, MAX_CELLS, MAX_HALF_LIFE, MAX_FULL_SCALE = 4, 256, 8192, 16384, 65535, 2 ** 31 - 1
@@ -38,31 +39,11 @@ SLOT = np.dtype([('id', np.int32), ('last', np.int32), ('cell1', np.int32), ('pa
 ROW = np.dtype([('row', np.int32), ('col', np.int32), ('flags', np.uint32), ('cells', np.uint32)])
 IMAGE = np.dtype([('max_dwell', np.uint32), ('max_visits', np.uint32), ('counted', np.uint32), ('visits', np.uint32)])
 
-_serials = itertools.count(1)
-
 
 def state_dtype(gh, gw):
     """The state of one stream (include/mpn.h) for a grid of gh x gw cells."""
     return np.dtype([('frames', np.int32), ('max_dwell', np.uint32), ('max_visits', np.uint32), ('pad', np.int32, (5,)),
                      ('slots', SLOT, (SLOTS,)), ('dwell', np.uint32, (gh, gw)), ('visits', np.uint32, (gh, gw))])
-
-
-def _integer(name, value, lo, hi):
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
-        raise ValueError(f"DensityMap: {name} must be an integer in {lo}..{hi} (got {value!r})")
-    return int(value)
-
-
-def _flag(name, value):
-    if not isinstance(value, (bool, np.bool_)):
-        raise ValueError(f"DensityMap: {name} must be False or True (got {value!r})")
-    return bool(value)
-
-
-def _choice(name, value, choices):
-    if not isinstance(value, str) or value not in choices:
-        raise ValueError(f"DensityMap: {name} must be one of {list(choices)} (got {value!r})")
-    return value
 
 
 def draw_table(colormap, opacity, smooth, full_scale, show):
@@ -79,7 +60,7 @@ def draw_table(colormap, opacity, smooth, full_scale, show):
     return table
 
 
-class DensityMap:
+class DensityMap(StreamState):
     """Where persons stand, accumulated per cell of a grid over the frame, for `streams` independent cameras, on the device
     (`mpn_density_map`), and how `annotate` draws it (`mpn_draw_density`).
 
@@ -98,12 +79,13 @@ class DensityMap:
     as `tracking.PoseTracker` does. The object owns the drawing's table on the device and the state - per stream 64 identities
     with the cell each was last seen in, and the two planes - as a prev / next pair. `launch` is pure; `commit()` advances the
     state. No default is tuned on video."""
+    keyword, _serials = 'density', itertools.count(1)
 
     def __init__(self, streams=1, frame_size=None, cell=16, footprint='anchor', anchor='feet', min_keypoint_score=0.0, half_life=0,
                  show='dwell', draw=True, smooth=True, full_scale=0, opacity=160, colormap=None, max_boxes=25, device=None):
         if isinstance(streams, (bool, np.bool_)) or not isinstance(streams, (int, np.integer)) or streams < 1:
             raise ValueError(f"DensityMap: streams must be an integer >= 1 (got {streams!r})")
-        self.max_boxes = _integer('max_boxes', max_boxes, 1, MAX_BOXES)
+        self.max_boxes = integer('DensityMap', 'max_boxes', max_boxes, 1, MAX_BOXES)
         try:
             height, width = frame_size
         except (TypeError, ValueError):
@@ -111,24 +93,24 @@ class DensityMap:
         for v in (height, width):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= v <= MAX_SIDE:
                 raise ValueError(f"DensityMap: frame_size must be two integers (height, width) in 1..{MAX_SIDE} (got {frame_size!r})")
-        self.cell = _integer('cell', cell, MIN_CELL, MAX_CELL)
+        self.cell = integer('DensityMap', 'cell', cell, MIN_CELL, MAX_CELL)
         self.gh, self.gw = -(-int(height) // self.cell), -(-int(width) // self.cell)
         if self.gh * self.gw > MAX_CELLS:
             raise ValueError(f"DensityMap: a grid of {self.gh} x {self.gw} cells has more than {MAX_CELLS}; take a larger cell "
                              f"(got {cell!r})")
-        self.footprint = _choice('footprint', footprint, FOOTPRINTS)
-        self.anchor = _choice('anchor', anchor, ANCHORS)
+        self.footprint = choice('DensityMap', 'footprint', footprint, FOOTPRINTS)
+        self.anchor = choice('DensityMap', 'anchor', anchor, ANCHORS)
         try:
             mks = float(min_keypoint_score)
         except (TypeError, ValueError):
             raise ValueError(f"DensityMap: min_keypoint_score must be a number (got {min_keypoint_score!r})") from None
         if not math.isfinite(mks):
             raise ValueError(f"DensityMap: min_keypoint_score must be finite (got {min_keypoint_score!r})")
-        self.half_life = _integer('half_life', half_life, 0, MAX_HALF_LIFE)
-        self.show = _choice('show', show, PLANES)
-        self.draw, self.smooth = _flag('draw', draw), _flag('smooth', smooth)
-        self.full_scale = _integer('full_scale', full_scale, 0, MAX_FULL_SCALE)
-        self.opacity = _integer('opacity', opacity, 0, 255)
+        self.half_life = integer('DensityMap', 'half_life', half_life, 0, MAX_HALF_LIFE)
+        self.show = choice('DensityMap', 'show', show, PLANES)
+        self.draw, self.smooth = flag('DensityMap', 'draw', draw), flag('DensityMap', 'smooth', smooth)
+        self.full_scale = integer('DensityMap', 'full_scale', full_scale, 0, MAX_FULL_SCALE)
+        self.opacity = integer('DensityMap', 'opacity', opacity, 0, 255)
         if colormap is None:
             from .inference.maps import colour_table
             colormap = colour_table()[:, :3]
@@ -142,26 +124,17 @@ class DensityMap:
         self.state_row = state_dtype(self.gh, self.gw)
         lib = _lib.lib()
         self.state_bytes = lib.mpn_density_state_bytes(self.streams, self.gh, self.gw)
-        self.stream_bytes = self.state_row.itemsize
-        if self.state_bytes != self.streams * self.stream_bytes:
+        if self.state_bytes != self.streams * self.state_row.itemsize:
             raise ValueError(f"DensityMap: streams = {streams!r} are more than mpn_density_map takes")
         self.host_table = draw_table(self.colormap, self.opacity, self.smooth, self.full_scale, self.show)
         import torch
         self.device = torch.device(device) if device is not None else _lib.current_device()
         self.table = torch.from_numpy(self.host_table.copy()).to(self.device)
-        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
+        self._make_state(self.state_row.itemsize)
         self._update, self._work, self._snapshots = {}, {}, {}
         self.last_out = None
 
     # ---------------------------------------------------------------- the device side
-    def check_batch(self, b):
-        """The number of images of a call -> frames per stream."""
-        if b < 1 or b % self.streams != 0:
-            raise ValueError(f"density=: {b} images are not a whole number of frames for each of {self.streams} streams")
-        return b // self.streams
-
     def check_frame_sizes(self, sizes):
         """Raises unless every (height, width) of `sizes` is the object's frame_size."""
         for h, w in sizes:
@@ -218,24 +191,9 @@ class DensityMap:
                   _lib.ptr(work), work.numel(), _lib.stream_ptr())
         return out_rgba
 
-    def commit(self):
-        """The last launch's state becomes the current one: one device copy on the current stream."""
-        self.prev.copy_(self.next, non_blocking=True)
-
-    def reset(self, stream=None):
-        """Forget everything and set the frame count to zero: of all streams, or of one."""
-        if stream is not None and not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        part = slice(None) if stream is None else slice(int(stream) * self.stream_bytes, (int(stream) + 1) * self.stream_bytes)
-        self.prev[part].zero_()
-        self.next[part].zero_()
-
     def state(self, stream=0):
         """A host copy of one stream's current state, as a `state_dtype(gh, gw)` record."""
-        if not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        raw = self.prev[int(stream) * self.stream_bytes:(int(stream) + 1) * self.stream_bytes].cpu().numpy()
-        return raw.view(self.state_row)[0]
+        return self._raw_state(stream).view(self.state_row)[0]
 
     def grid(self, stream=0, plane='dwell'):
         """A host copy of one stream's current plane, 'dwell' or 'visits': uint32 [gh, gw]."""

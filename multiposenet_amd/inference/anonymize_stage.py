@@ -13,6 +13,7 @@ import math
 import numpy as np
 
 from .. import _lib
+from ..stream_state import choice, integer
 from . import draw
 
 REGIONS = {'head': 0, 'box': 1}
@@ -29,18 +30,6 @@ class Params(ctypes.Structure):
                 ('radius', ctypes.c_int32), ('color', ctypes.c_int32), ('min_keypoint_score', ctypes.c_float),
                 ('reserved', ctypes.c_int32), ('scale', ctypes.c_double), ('min_size', ctypes.c_double),
                 ('fallback', ctypes.c_double)]
-
-
-def _choice(name, value, table):
-    if not isinstance(value, str) or value not in table:
-        raise ValueError(f"Anonymize: {name} must be one of {list(table)} (got {value!r})")
-    return value
-
-
-def _integer(name, value, lo, hi):
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
-        raise ValueError(f"Anonymize: {name} must be an integer in {lo}..{hi} (got {value!r})")
-    return int(value)
 
 
 def _number(name, value, rule, ok):
@@ -89,9 +78,9 @@ class Anonymize:
             mks32 = float(np.float32(mks))                          # what the launch compares against
         if not math.isfinite(mks32):
             raise ValueError(f"Anonymize: min_keypoint_score must be finite (got {min_keypoint_score!r})")
-        values = dict(region=_choice('region', region, REGIONS), mode=_choice('mode', mode, MODES),
-                      shape=_choice('shape', shape, SHAPES), blocks=_integer('blocks', blocks, 2, MAX_BLOCKS),
-                      radius=_integer('radius', radius, 1, MAX_RADIUS), color=tuple(int(v) for v in rgb),
+        values = dict(region=choice('Anonymize', 'region', region, REGIONS), mode=choice('Anonymize', 'mode', mode, MODES),
+                      shape=choice('Anonymize', 'shape', shape, SHAPES), blocks=integer('Anonymize', 'blocks', blocks, 2, MAX_BLOCKS),
+                      radius=integer('Anonymize', 'radius', radius, 1, MAX_RADIUS), color=tuple(int(v) for v in rgb),
                       scale=_number('scale', scale, "> 0", lambda v: v > 0),
                       min_size=_number('min_size', min_size, ">= 0", lambda v: v >= 0),
                       fallback=_number('fallback', fallback, "in (0, 1]", lambda v: 0 < v <= 1),

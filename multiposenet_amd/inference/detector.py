@@ -8,6 +8,7 @@ and returns the seven outputs of OUTPUT_NAMES (create_pb.py:22-26) with the scor
 The reference freezes three checkpoints into one `.pb` (create_pb.py:170-185); here the three variable sets are three `.npz`
 files keyed by the reference's variable names (multiposenet_amd.checkpoint)."""
 import collections
+import importlib
 
 import numpy as np
 import torch
@@ -18,6 +19,9 @@ from .. import pose_nms as pose_nms_stage
 from ..net import KeypointNet
 from . import anonymize_stage
 from . import draw, jpeg, maps, resample, tta
+from .record import NUM_KEYPOINTS, _ROW, RecordLayout, _no_persons, unpack_record  # noqa: F401 (found here by tests and tools)
+
+record_layout = RecordLayout            # the layout's earlier name, when it was a tuple of slices: modules that import it still load
 
 # create_pb.py:31-36: the thresholds frozen into the graph
 PARAMS = {'depth_multiplier': 1.0, 'score_threshold': 0.3, 'iou_threshold': 0.6, 'max_boxes': 25}
@@ -29,13 +33,6 @@ def _load(path):
         return path
     with np.load(path) as z:
         return {k: z[k] for k in z.files}
-
-
-NUM_KEYPOINTS = 17
-# a row of mpn_pose_gather's record (include/mpn.h names the fields in this order; offsets and stride come from the library)
-_ROW = np.dtype([('image_index', np.int32), ('box', np.float32, (4,)), ('score', np.float32),
-                 ('keypoint_scores', np.float32, (NUM_KEYPOINTS,)), ('keypoint_positions', np.float32, (NUM_KEYPOINTS, 2)),
-                 ('keypoints', np.float32, (NUM_KEYPOINTS, 3))])
 
 
 def check_batch(images):
@@ -141,12 +138,35 @@ def _batch_frames(b, h, w):
     return [(h, w)] * b, [i * h * w * 3 for i in range(b)]
 
 
+# The stages that write rows behind the record, in the order of their parts in the `RecordLayout` - which is also the order
+# in which `_finish` unpacks them and the call commits them. part: the name of the part and of the _Entry attribute; option:
+# the _Options field, and the word in an entry's key; result: the key of the result dicts the unpacked rows go to (None: they
+# update the dict); tail: how the option is spelled behind its word in the key - by its 'serial', as the 'value' itself, or
+# None where `_Options.tail` spells it out; stateful: the caller's own object with a prev / next state: the entry holds it
+# as it is and the call commits it. The launches, which take different arguments, are written out in `_device_side_batch`.
+_Stage = collections.namedtuple('_Stage', 'part option result tail stateful')
+_STAGES = (_Stage('oks', 'oks', 'oks', None, False),
+           _Stage('track', 'track', None, None, True),
+           _Stage('nms', 'pose_nms', None, 'value', False),
+           _Stage('track_eval', 'track_eval', 'track_eval', 'serial', True),
+           _Stage('zones', 'zones', 'zones', 'serial', True),
+           _Stage('trails', 'trails', 'trails', 'serial', True),
+           _Stage('density', 'density', 'density', 'serial', True))
+
+
+# The stages that ride on the tracker, by keyword: (module, class, what the messages call the stage, why it needs track= - None:
+# it does not, `Detector._check_density` has the rule)
+_RIDERS = {'track_eval': ('track_metrics', 'TrackEvaluator', 'the evaluator', "scores the tracker's identities"),
+           'zones': ('zones', 'ZoneCounter', 'the counter', "counts the tracker's identities"),
+           'trails': ('trails', 'TrackTrails', 'the trails', "follows the tracker's identities"),
+           'density': ('density', 'DensityMap', 'the map', None)}
+
+
 class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval density trails zones anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
-    'jpeg''s (quality, sampling); plot_maps; the key parts of groundtruth= (`_check_groundtruth`), of flip / scales
-    (`check_tta`) and of track_style= (`check_track_style`), () where the option is off; the tracker or None;
-    return_heatmaps; the TrackEvaluator of track_eval= or None; the DensityMap of density= or None; the TrackTrails of trails= or None; the ZoneCounter of zones= or None; the Anonymize of anonymize= or
-    None; the PoseNms of pose_nms= or None (the last field, as ever)."""
+    'jpeg''s (quality, sampling); plot_maps; oks, tta and style as the parts of the key that `_check_groundtruth`, `check_tta`
+    and `check_track_style` return, () where the option is off; return_heatmaps; every other field the object of its keyword,
+    or None."""
     __slots__ = ()
 
     @property
@@ -165,64 +185,27 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
         if self.track is not None:
             key += ('track', self.track.serial, b)
         key += self.style
-        if self.pose_nms is not None:
-            key += ('pose_nms', self.pose_nms)
-        if self.track_eval is not None:
-            key += ('track_eval', self.track_eval.serial)
-        if self.zones is not None:
-            key += ('zones', self.zones.serial)
-        if self.trails is not None:
-            key += ('trails', self.trails.serial)
-        if self.density is not None:
-            key += ('density', self.density.serial)
+        for st in _STAGES:
+            stage = getattr(self, st.option)
+            if st.tail is not None and stage is not None:
+                key += (st.option, stage.serial if st.tail == 'serial' else stage)
         if self.anonymize is not None:
             key += ('anonymize', self.anonymize)
         return key
 
 
-def record_layout(b, max_boxes, oks=None, track=None, nms=None, track_eval=None, zones=None, trails=None, density=None):
-    """The bytes a call brings to the host in one copy, as four slices: mpn_pose_gather's record (with pose_nms=: the
-    filtered record mpn_pose_nms wrote in its place); behind it the rows of mpn_oks_match (oks: the entry's
-    pose_metrics.OksBuffers); behind those the tracker's block (track: the entry's tracking.PoseTracker, which lays out its own
-    rows: `row_offsets`); behind that, at the next multiple of 16 bytes, mpn_pose_nms's info block (nms: the entry's
-    pose_nms.PoseNmsBuffers). A part that is not there is empty; a record of 0 bytes: more slots than mpn_pose_gather packs.
-    track_eval (the entry's track_metrics.TrackEvaluator): a fifth slice, mpn_track_eval's rows behind everything else at the
-    next multiple of 16 bytes; without it the four slices are returned, as ever. zones (the entry's zones.ZoneCounter): one
-    more slice at the end of the tuple, mpn_zone_events' rows behind everything else at the next multiple of 16 bytes; without
-    it the function returns what it returns without the argument. trails (the entry's trails.TrackTrails): one more slice at
-    the very end, behind zones' slice, mpn_track_trails' rows at the next multiple of 16 bytes; likewise. density (the entry's density.DensityMap): one more
-    slice at the very end, behind the trails' slice, mpn_density_map's rows at the next multiple of 16 bytes; likewise."""
-    record = _lib.lib().mpn_pose_gather_record_bytes(b, max_boxes)
-    rows = record + (oks.out_bytes if oks is not None else 0)
-    end = rows + (track.out_bytes(b) if track is not None else 0)
-    info = slice((end + 15) // 16 * 16, (end + 15) // 16 * 16 + nms.info_bytes) if nms is not None else slice(end, end)
-    parts = slice(0, record), slice(record, rows), slice(rows, end), info
-    if track_eval is not None:
-        at = (info.stop + 15) // 16 * 16
-        parts += (slice(at, at + track_eval.out_bytes(b)),)
-    if zones is not None:
-        at = (parts[-1].stop + 15) // 16 * 16
-        parts += (slice(at, at + zones.out_bytes(b)),)
-    if trails is not None:
-        at = (parts[-1].stop + 15) // 16 * 16
-        parts += (slice(at, at + trails.out_bytes(b)),)
-    if density is not None:
-        at = (parts[-1].stop + 15) // 16 * 16
-        parts += (slice(at, at + density.out_bytes(b)),)
-    return parts
-
-
 class _Entry:
-    """The persistent state behind one key of `Detector._graphs` / `_eager_batches`: the pinned input staging and the device
-    input, `host` (the pinned result buffers by output name), the captured graph with its outputs and the variable versions
-    it last ran with, the drawing and encode state of an annotate entry, the MapPlotter of a plot_maps entry, the
-    ground-truth buffers of a `groundtruth=` entry (a pose_metrics.OksBuffers), the inputs and merged maps of a flip / scales
-    entry (a tta.Buffers), the tracker of a `track=` entry (a tracking.PoseTracker: the graph reads and writes its state
-    buffers, so the entry keeps it alive), the style of a `track_style=` entry as (TrackStyle, its table on the device), the mpn_pose_nms stage of a `pose_nms=` entry (a pose_nms.PoseNmsBuffers: it holds the unfiltered record), the evaluator of a `track_eval=` entry (a track_metrics.TrackEvaluator, kept alive like the tracker), the counter of a `zones=` entry (a zones.ZoneCounter, kept alive like the tracker), the trails of a `trails=` entry (a trails.TrackTrails, kept alive like the tracker), the map of a `density=` entry (a density.DensityMap, kept alive like the tracker), the mpn_anonymize stage of an
-    `anonymize=` entry (an anonymize_stage.Anonymizer: it holds the anonymised frames the drawing reads), and the packed sources, descriptors (with their staging), intermediates and JPEG decoder of the ragged paths. What a path does not use
-    stays None."""
-    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'oks',
-                 'sources', 'meta_stage', 'meta', 'work', 'jpeg', 'tta', 'track', 'style', 'nms', 'track_eval', 'anonymize', 'zones', 'trails', 'density')
+    """The persistent state behind one key of `Detector._graphs` / `_eager_batches`; what a path does not use stays None.
+    stage, x: the pinned input staging and the device input. host: the pinned result buffers by output name. graph, outs, ver:
+    the captured graph, its outputs and the variable versions it last ran with. draw, encode, encode_plan, maps, tta,
+    anonymize: the buffers of annotate, plot_maps, flip / scales and anonymize= (draw.Buffers, jpeg.JpegBatchEncoder,
+    maps.MapPlotter, tta.Buffers, anonymize_stage.Anonymizer). style: (TrackStyle, its table on the device). The parts of
+    `_STAGES`: oks and nms are buffers of the entry (pose_metrics.OksBuffers, pose_nms.PoseNmsBuffers); track, track_eval,
+    zones, trails and density are the caller's objects, whose state the graph reads and writes: the entry keeps them alive.
+    layout: the RecordLayout of those parts. sources, meta_stage, meta, work, jpeg: the packed sources, descriptors (with
+    their staging), intermediates and JPEG decoder of the ragged paths."""
+    __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'sources', 'meta_stage',
+                 'meta', 'work', 'jpeg', 'tta', 'style', 'anonymize', 'layout') + tuple(st.part for st in _STAGES)
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -231,38 +214,11 @@ class _Entry:
         for name, buffer in buffers.items():
             setattr(self, name, buffer)
 
-
-def _no_persons(num_boxes=0):
-    return {'boxes': np.zeros([0, 4], np.float32), 'scores': np.zeros([0], np.float32), 'num_boxes': np.int32(num_boxes),
-            'keypoint_scores': np.zeros([0, NUM_KEYPOINTS], np.float32), 'keypoint_positions': np.zeros([0, NUM_KEYPOINTS, 2], np.float32),
-            'keypoints': np.zeros([0, NUM_KEYPOINTS, 3], np.float32)}
-
-
-def unpack_record(record, b, max_boxes, with_keypoints=True):
-    """A host copy of mpn_pose_gather's record (uint8 array) -> a list of b dicts: 'boxes' [n,4], 'scores' [n], 'num_boxes',
-    'keypoint_scores' [n,17], 'keypoint_positions' [n,17,2], 'keypoints' [n,17,3] (the three keypoint arrays empty when the
-    graph has no PRN). Raises like `check_nms` when the record carries a set NMS overflow word."""
-    lib = _lib.lib()
-    first, stride = lib.mpn_pose_gather_row_offset(b, max_boxes, 0), lib.mpn_pose_gather_row_offset(b, max_boxes, 1)
-    stride -= first
-    if stride != _ROW.itemsize or len(record) < record_layout(b, max_boxes)[0].stop:
-        raise _lib.MpnError("mpn_pose_gather: the record's layout is not the one this binding was written against")
-    header = record[:first].view(np.int32)
-    total, counts, num_boxes, overflow = int(header[0]), header[1:1 + b], header[1 + b:1 + 2 * b], int(header[1 + 2 * b])
-    if overflow != 0:
-        raise RuntimeError("mpn_retina_nms: a candidate list overflowed its workspace (MPN_ERR_WORKSPACE); the detections are incomplete")
-    rows = record[first:first + total * stride].copy().view(_ROW)      # (the pinned buffer is reused by the next call)
-    out, s = [], 0
-    for i in range(b):
-        e = s + int(counts[i])
-        r = rows[s:e]
-        p = _no_persons(num_boxes[i])
-        p.update({'boxes': np.ascontiguousarray(r['box']), 'scores': np.ascontiguousarray(r['score'])})
-        if with_keypoints:
-            p.update({k: np.ascontiguousarray(r[k]) for k in ('keypoint_scores', 'keypoint_positions', 'keypoints')})
-        out.append(p)
-        s = e
-    return out
+    def commit(self):
+        """The stateful stages advance their state: ONCE per call, outside the graph (`Detector._run` may launch twice)."""
+        for st in _STAGES:
+            if st.stateful and getattr(self, st.part) is not None:
+                getattr(self, st.part).commit()
 
 
 class Detector:
@@ -553,25 +509,15 @@ class Detector:
                 stage[i] = im
         ent.x[:b].copy_(ent.stage, non_blocking=True)               # ONE host-to-device copy
         outs = self._run(ent, lambda: self._device_side_batch(ent, opts.thr))
-        if ent.track is not None:
-            ent.track.commit()                                      # ONCE per call, outside the graph: _run may launch twice
-        if ent.track_eval is not None:
-            ent.track_eval.commit()
-        if ent.zones is not None:
-            ent.zones.commit()
-        if ent.trails is not None:
-            ent.trails.commit()
-        if ent.density is not None:
-            ent.density.commit()
+        ent.commit()
         return self._finish(ent, outs, b, opts.return_heatmaps)
 
     def _options(self, shape, **given):
         """Every argument check of the predict_* methods, in one order and before any device work -> (_Options, what shape()
-        returned). given: the keywords the three methods share, as they came: score_threshold, return_heatmaps, annotate,
-        jpeg_quality, jpeg_subsampling, plot_maps, groundtruth, flip, scales, track, track_style, pose_nms, track_eval, density, trails, zones, anonymize (the
-        last six may be absent: None; anonymize is checked last, zones before it, trails before zones, density before trails). shape(): the method's own
-        checks of its images and sizes, run behind those of annotate, track_style and plot_maps; what it returns begins with
-        (b, height, width) of the network input."""
+        returned). given: the keywords the three methods share, as they came (pose_nms, track_eval, density, trails, zones and
+        anonymize may be absent: None). shape(): the method's own checks of its images and sizes, run behind those of
+        annotate, track_style and plot_maps; what it returns begins with (b, height, width) of the network input. The order
+        behind it: groundtruth, track, flip / scales, pose_nms, track_eval, density, trails, zones, anonymize."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
         style = check_track_style(given['track_style'], given['annotate'], given['track'])
         plot_maps = check_plot_maps(given['plot_maps'], self._has_heatmaps)
@@ -587,76 +533,56 @@ class Detector:
         evaluator = self._check_track_eval(given.get('track_eval'), given['track'], given['groundtruth'], b)
         sizes = shaped[4].sizes if len(shaped) > 4 else [(h, w)]
         density = self._check_density(given.get('density'), given['track'], b, sizes)
-        trails = self._check_trails(given.get('trails'), given['track'], b, sizes)
-        counter = self._check_zones(given.get('zones'), given['track'], b, sizes)
+        trails = self._check_rider('trails', given.get('trails'), given['track'], b, sizes)
+        counter = self._check_rider('zones', given.get('zones'), given['track'], b, sizes)
         spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
                         given['return_heatmaps'], evaluator, density, trails, counter, spec, nms), shaped
 
-    def _check_zones(self, counter, track, b, sizes):
-        """The `zones` argument of the predict_* methods -> None or the ZoneCounter. sizes: (height, width) of the call's frames,
-        in whose pixels the record's keypoints are. Before any device work."""
-        if counter is None:
-            return None
-        from ..zones import ZoneCounter
-        if not isinstance(counter, ZoneCounter):
-            raise ValueError("zones must be None or a zones.ZoneCounter")
-        if track is None:
-            raise ValueError("zones= counts the tracker's identities: it needs track=, a tracking.PoseTracker")
-        if counter.streams != track.streams:
-            raise ValueError(f"zones=: the counter was made for {counter.streams} streams, the tracker for {track.streams}")
-        if counter.max_boxes != self.params['max_boxes']:
-            raise ValueError(f"zones=: the counter was made for max_boxes = {counter.max_boxes}, this Detector's is "
+    def _check_fit(self, keyword, noun, stage, track=None, limits=None):
+        """What every stateful stage must share with this Detector, in one order: the streams of the tracker it rides on (where
+        there is one), max_boxes, `limits()` - a stage's own sizes - and the device. noun: what the messages call the stage (one that ends in s is a
+        plural: "the trails were made for ...")."""
+        was, lives = ('were', 'live') if noun.endswith('s') else ('was', 'lives')
+        if track is not None and stage.streams != track.streams:
+            raise ValueError(f"{keyword}=: {noun} {was} made for {stage.streams} streams, the tracker for {track.streams}")
+        if stage.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"{keyword}=: {noun} {was} made for max_boxes = {stage.max_boxes}, this Detector's is "
                              f"{self.params['max_boxes']}")
-        if torch.device(counter.device) != torch.device(self.net.device):
-            raise ValueError(f"zones=: the counter lives on {counter.device}, this Detector on {self.net.device}")
-        counter.check_frame_sizes(sizes)
-        counter.out_bytes(b)
-        return counter
+        if limits is not None:
+            limits()
+        if torch.device(stage.device) != torch.device(self.net.device):
+            raise ValueError(f"{keyword}=: {noun} {lives} on {stage.device}, this Detector on {self.net.device}")
 
-    def _check_trails(self, trails, track, b, sizes):
-        """The `trails` argument of the predict_* methods -> None or the TrackTrails. sizes: (height, width) of the call's frames,
-        in whose pixels the record's keypoints are. Before any device work."""
-        if trails is None:
+    def _check_rider(self, keyword, stage, track, b, sizes=None, rules=None, limits=None):
+        """The `track_eval`, `zones`, `trails` or `density` argument of the predict_* methods, a stage that rides on the tracker
+        -> None or the stage. In one order: its type; that there is a tracker (where `_RIDERS` says why it needs one) and
+        `rules()`, the stage's own about the detector, the PRN and the other keywords; `_check_fit`; sizes, the (height, width)
+        of the call's frames, in whose pixels the record's keypoints are, against the stage's frame_size; `out_bytes(b)`. Before
+        any device work."""
+        if stage is None:
             return None
-        from ..trails import TrackTrails
-        if not isinstance(trails, TrackTrails):
-            raise ValueError("trails must be None or a trails.TrackTrails")
-        if track is None:
-            raise ValueError("trails= follows the tracker's identities: it needs track=, a tracking.PoseTracker")
-        if trails.streams != track.streams:
-            raise ValueError(f"trails=: the trails were made for {trails.streams} streams, the tracker for {track.streams}")
-        if trails.max_boxes != self.params['max_boxes']:
-            raise ValueError(f"trails=: the trails were made for max_boxes = {trails.max_boxes}, this Detector's is "
-                             f"{self.params['max_boxes']}")
-        if torch.device(trails.device) != torch.device(self.net.device):
-            raise ValueError(f"trails=: the trails live on {trails.device}, this Detector on {self.net.device}")
-        trails.check_frame_sizes(sizes)
-        trails.out_bytes(b)
-        return trails
+        module, cls, noun, why = _RIDERS[keyword]
+        if not isinstance(stage, getattr(importlib.import_module('..' + module, __package__), cls)):
+            raise ValueError(f"{keyword} must be None or a {module}.{cls}")
+        if why is not None and track is None:
+            raise ValueError(f"{keyword}= {why}: it needs track=, a tracking.PoseTracker")
+        if rules is not None:
+            rules()
+        self._check_fit(keyword, noun, stage, track, limits)
+        if sizes is not None:
+            stage.check_frame_sizes(sizes)
+        stage.out_bytes(b)
+        return stage
 
     def _check_density(self, density, track, b, sizes):
-        """The `density` argument of the predict_* methods -> None or the DensityMap. sizes: (height, width) of the call's frames,
-        in whose pixels the record's keypoints are. Before any device work."""
-        if density is None:
-            return None
-        from ..density import DensityMap
-        if not isinstance(density, DensityMap):
-            raise ValueError("density must be None or a density.DensityMap")
-        if self.retinanet is None:
-            raise ValueError("density= counts the persons of the record: this Detector has no person detector")
-        if track is None and density.show == 'visits':
-            raise ValueError("density=: show='visits' counts the arrivals of identities: it needs track=, a tracking.PoseTracker")
-        if track is not None and density.streams != track.streams:
-            raise ValueError(f"density=: the map was made for {density.streams} streams, the tracker for {track.streams}")
-        if density.max_boxes != self.params['max_boxes']:
-            raise ValueError(f"density=: the map was made for max_boxes = {density.max_boxes}, this Detector's is "
-                             f"{self.params['max_boxes']}")
-        if torch.device(density.device) != torch.device(self.net.device):
-            raise ValueError(f"density=: the map lives on {density.device}, this Detector on {self.net.device}")
-        density.check_frame_sizes(sizes)
-        density.out_bytes(b)
-        return density
+        """The `density` argument: `_check_rider` with its own rules - track= is optional, show='visits' needs it."""
+        def rules():
+            if self.retinanet is None:
+                raise ValueError("density= counts the persons of the record: this Detector has no person detector")
+            if track is None and density.show == 'visits':
+                raise ValueError("density=: show='visits' counts the arrivals of identities: it needs track=, a tracking.PoseTracker")
+        return self._check_rider('density', density, track, b, sizes, rules)
 
     def _check_anonymize(self, spec, annotate, track_style):
         """The `anonymize` argument of the predict_* methods -> None or the Anonymize. Before any device work."""
@@ -673,33 +599,21 @@ class Detector:
         return spec
 
     def _check_track_eval(self, evaluator, track, groundtruth, b):
-        """The `track_eval` argument of the predict_* methods -> None or the TrackEvaluator. Before any device work (and
-        before the evaluator gives an identity a dense index)."""
-        if evaluator is None:
-            return None
-        from ..track_metrics import TrackEvaluator, groundtruth_track_ids
-        if not isinstance(evaluator, TrackEvaluator):
-            raise ValueError("track_eval must be None or a track_metrics.TrackEvaluator")
-        if track is None:
-            raise ValueError("track_eval= scores the tracker's identities: it needs track=, a tracking.PoseTracker")
-        if groundtruth is None:
-            raise ValueError("track_eval= needs groundtruth=, a list of dicts that carry 'track_ids'")
-        if self.assigner is None:
-            raise ValueError("track_eval= compares keypoints, which need the PRN (prn_path)")
-        for gt in groundtruth:
-            groundtruth_track_ids(gt, len(pose_metrics.groundtruth_arrays(gt)[0]))
-        if evaluator.streams != track.streams:
-            raise ValueError(f"track_eval=: the evaluator was made for {evaluator.streams} streams, the tracker for {track.streams}")
-        if evaluator.max_boxes != self.params['max_boxes']:
-            raise ValueError(f"track_eval=: the evaluator was made for max_boxes = {evaluator.max_boxes}, this Detector's is "
-                             f"{self.params['max_boxes']}")
-        if evaluator.max_gt != pose_metrics.MAX_GT:
-            raise ValueError(f"track_eval=: the Detector's ground-truth rows are {pose_metrics.MAX_GT} per image; make the "
-                             f"evaluator with max_gt = {pose_metrics.MAX_GT} (got {evaluator.max_gt})")
-        if torch.device(evaluator.device) != torch.device(self.net.device):
-            raise ValueError(f"track_eval=: the evaluator lives on {evaluator.device}, this Detector on {self.net.device}")
-        evaluator.out_bytes(b)
-        return evaluator
+        """The `track_eval` argument: `_check_rider` with its own rules (before the evaluator gives an identity a dense index)."""
+        def rules():
+            from ..track_metrics import groundtruth_track_ids
+            if groundtruth is None:
+                raise ValueError("track_eval= needs groundtruth=, a list of dicts that carry 'track_ids'")
+            if self.assigner is None:
+                raise ValueError("track_eval= compares keypoints, which need the PRN (prn_path)")
+            for gt in groundtruth:
+                groundtruth_track_ids(gt, len(pose_metrics.groundtruth_arrays(gt)[0]))
+
+        def limits():
+            if evaluator.max_gt != pose_metrics.MAX_GT:
+                raise ValueError(f"track_eval=: the Detector's ground-truth rows are {pose_metrics.MAX_GT} per image; make the "
+                                 f"evaluator with max_gt = {pose_metrics.MAX_GT} (got {evaluator.max_gt})")
+        return self._check_rider('track_eval', evaluator, track, b, rules=rules, limits=limits)
 
     def _check_pose_nms(self, nms):
         """The `pose_nms` argument of the predict_* methods -> None or the PoseNms. Before any device work."""
@@ -741,11 +655,7 @@ class Detector:
         if track.smooth is not None and self.assigner is None:
             raise ValueError("track=: the tracker's smooth= filters keypoints, which need the PRN (prn_path)")
         track.check_batch(b)
-        if track.max_boxes != self.params['max_boxes']:
-            raise ValueError(f"track=: the tracker was made for max_boxes = {track.max_boxes}, this Detector's is "
-                             f"{self.params['max_boxes']}")
-        if torch.device(track.device) != torch.device(self.net.device):
-            raise ValueError(f"track=: the tracker lives on {track.device}, this Detector on {self.net.device}")
+        self._check_fit('track', 'the tracker', track)
         track.out_bytes(b)
 
     @staticmethod
@@ -779,35 +689,16 @@ class Detector:
         if 'record' in outs:
             record = host['record'].numpy()
             persons = unpack_record(record, b, self.params['max_boxes'], self.assigner is not None)
-            _, oks_rows, track_rows, nms_info = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms)[:4]
             counts = record[4:4 + 4 * b].view(np.int32)
-            if ent.oks is not None:                                 # the match rows lie behind the record: they came with it
-                for p, table in zip(persons, ent.oks.unpack(record[oks_rows], counts)):
-                    p['oks'] = table
-            if ent.track is not None:                               # the track rows lie behind those: the same copy
-                for p, ids in zip(persons, ent.track.unpack(record[track_rows], counts)):
-                    p.update(ids)
-            if ent.nms is not None:                                 # mpn_pose_nms's info block lies behind those: the same copy
-                for p, extra in zip(persons, ent.nms.unpack(record[nms_info], counts)):
-                    p.update(extra)
-            if ent.track_eval is not None:                          # mpn_track_eval's rows lie behind everything: the same copy
-                eval_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval)[4]
-                for p, rows in zip(persons, ent.track_eval.unpack(record[eval_rows], counts)):
-                    p['track_eval'] = rows
-            if ent.zones is not None:                               # mpn_zone_events' rows lie behind those: the same copy
-                zone_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones)[-1]
-                for p, rows in zip(persons, ent.zones.unpack(record[zone_rows], counts)):
-                    p['zones'] = rows
-            if ent.trails is not None:                              # mpn_track_trails' rows lie behind those: the same copy
-                trail_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones,
-                                           ent.trails)[-1]
-                for p, rows in zip(persons, ent.trails.unpack(record[trail_rows], counts)):
-                    p['trails'] = rows
-            if ent.density is not None:                             # mpn_density_map's rows lie behind those: the same copy
-                density_rows = record_layout(b, self.params['max_boxes'], ent.oks, ent.track, ent.nms, ent.track_eval, ent.zones,
-                                             ent.trails, ent.density)[-1]
-                for p, rows in zip(persons, ent.density.unpack(record[density_rows], counts)):
-                    p['density'] = rows
+            for st in _STAGES:                                      # every stage's rows lie behind the record: they came with it
+                stage = getattr(ent, st.part)
+                if stage is None:
+                    continue
+                for p, rows in zip(persons, stage.unpack(record[getattr(ent.layout, st.part)], counts)):
+                    if st.result is None:
+                        p.update(rows)
+                    else:
+                        p[st.result] = rows
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -829,10 +720,10 @@ class Detector:
         """The entry of one key, base + opts.tail(b), in `_graphs` (use_graph False: `_eager_batches`), made on its first use
         (`_run` adds the captured graph). make(): an _Entry with the staging and device buffers of the path. To it come the
         device input for shape = (b, h, w) (with the mirrors behind the batch and the inputs of the extra scales for flip /
-        scales) and what each option needs: the drawing's buffers, sized for sources of capacity[0] bytes; the JPEG encoder,
-        which reserves capacity[1:]; the MapPlotter; the ground-truth buffers; the tracker; the style with its table, which
-        goes to the device once, here; the mpn_pose_nms stage with its buffer for the unfiltered record. fixed_frames (predict_batch): the frames are the batch itself, so the drawing and
-        encode descriptors are placed here, for good, and the encoder reserves what their plan needs."""
+        scales), what each option needs (`_Entry`) - the drawing's buffers sized for sources of capacity[0] bytes, the JPEG
+        encoder reserving capacity[1:], the style's table, which goes to the device once, here - and the layout of the result
+        buffer. fixed_frames (predict_batch): the frames are the batch itself, so the drawing and encode descriptors are
+        placed here, for good, and the encoder reserves what their plan needs."""
         b, h, w = shape
         key = base + opts.tail(b)
         store = self._graphs if self.use_graph else self._eager_batches
@@ -864,13 +755,12 @@ class Detector:
             ent.maps = maps.MapPlotter(b, h, w, h // 4, w // 4, dev)
         if opts.oks:
             ent.oks = pose_metrics.OksBuffers(b, self.params['max_boxes'], pose_metrics.MAX_GT, dev, opts.oks[1], opts.oks[2])
-        ent.track = opts.track
-        ent.track_eval = opts.track_eval
-        ent.zones = opts.zones
-        ent.trails = opts.trails
-        ent.density = opts.density
         if opts.pose_nms is not None:
             ent.nms = pose_nms_stage.PoseNmsBuffers(b, self.params['max_boxes'], opts.pose_nms, dev)
+        for st in _STAGES:
+            if st.stateful:
+                setattr(ent, st.part, getattr(opts, st.option))
+        ent.layout = RecordLayout(b, self.params['max_boxes'], **{st.part: getattr(ent, st.part) for st in _STAGES})
         if opts.style:
             ent.style = opts.style[1], torch.from_numpy(opts.style[1].tables().copy()).to(dev)
         store[key] = ent
@@ -880,40 +770,14 @@ class Detector:
         """_device_side for the b images of the entry's input ent.x, then mpn_pose_gather: {'heat', 'seg'[, 'record']}. The PRN
         runs ONCE over all b * max_boxes slots (an instance of that batch size on the shared variables). extent
         (predict_images): f32 [b, 4] on the device; the gather is then mpn_pose_gather_sized, which maps boxes and keypoints to
-        the source images. What the entry holds decides the rest:
-        ent.draw (a draw.Buffers): mpn_draw_detections follows the gather and draws the record's persons on `frames` (flat
-        uint8; default: the batch x itself) -> 'annotated', the packed RGBA frames. ent.encode (a jpeg.JpegBatchEncoder whose
-        descriptors are in place): mpn_jpeg_forward and mpn_jpeg_entropy_encode follow on those frames, which then stay on the
-        device as 'encoded'.
-        ent.maps (a maps.MapPlotter): mpn_heatmap_minmax and mpn_plot_maps on the batch x, its heatmaps and its mask -> 'maps'.
-        ent.oks (a pose_metrics.OksBuffers whose ground truth is in place): mpn_oks_match follows the gather; its rows lie behind
-        the record in the same buffer (`record_layout`), so that they reach the host in the record's copy.
-        ent.track (a tracking.PoseTracker): mpn_pose_track follows; its rows lie behind the record and the OKS rows. It reads the
-        tracker's state and writes the next one elsewhere: launching it twice changes nothing (the caller commits). A tracker
-        with smooth= launches mpn_pose_smooth behind it, pure in the same way; its rows lie behind the track rows.
-        ent.style ((TrackStyle, its table on the device), with draw and track): the drawing is mpn_draw_tracks, which reads
-        those rows in place.
-        ent.anonymize (an anonymize_stage.Anonymizer whose descriptors are in place, with draw): mpn_anonymize follows everything that
-        writes rows, reads the record the drawing reads and `frames`, and writes its own buffer, which the drawing then takes as
-        its sources; with overlay=False the drawing gets the empty record. Pure: launching it twice gives the same bytes.
-        ent.nms (a pose_nms.PoseNmsBuffers): the gather writes to its buffer, which stays on the device, and mpn_pose_nms writes
-        the filtered record where the record lies otherwise: every launch above reads that one. Its info block lies behind the
-        tracker's rows. Pure, like the tracker's launches.
-        ent.track_eval (a track_metrics.TrackEvaluator, with track and oks): mpn_track_eval follows the tracker's launches over the
-        record the tracker read, the tracker's rows and the ground truth ent.oks holds; its rows lie behind everything else.
-        Pure in the same way: the caller commits.
-        ent.zones (a zones.ZoneCounter, with track): mpn_zone_events follows the tracker's launches (and mpn_track_eval) over the record
-        the tracker read and the tracker's rows; its rows lie behind everything else. Pure in the same way: the caller commits.
-        ent.density (a density.DensityMap, with or without track): mpn_density_map follows mpn_track_trails over the same record
-        (and, with track, the tracker's rows); its rows lie behind the trails'. Pure in the same way: the caller commits. With draw
-        and `density.draw`, mpn_draw_density follows mpn_draw_trails and blends the map into the frames in place (not with
-        anonymize's overlay=False).
-        ent.trails (a trails.TrackTrails, with track): mpn_track_trails follows mpn_zone_events over the same record and rows; its
-        rows lie behind zones'. Pure in the same way: the caller commits. With draw and `trails.draw`, mpn_draw_trails follows
-        the drawing and blends the rows' polylines into its frames in place (not with anonymize's overlay=False).
-        ent.tta (a tta.Buffers whose base input is x): x is [2b, h, w, 3] with flip, its second half written here by
-        mpn_mirror_images; backbone and subnet run over all of it and over the input of every extra scale, ONE mpn_tta_merge
-        launch averages the maps, and everything below reads the merged maps, the first b images and their features."""
+        the source images. frames: the flat uint8 sources the drawing reads (default: the batch x itself).
+        What the entry holds decides the rest (`predict_batch` describes every option, DESIGN.md "The row stages of the
+        Detector" the order): ent.tta - mirrors, extra scales and ONE mpn_tta_merge, whose maps everything below reads;
+        ent.maps -> 'maps'; behind the gather the launches that write rows into the one result buffer where `ent.layout` says
+        (-> 'record', the whole buffer): pose_nms, whose filtered record every later launch reads, oks, track, track_eval,
+        zones, trails, density; then anonymize, the drawing (mpn_draw_tracks with ent.style), mpn_draw_trails and
+        mpn_draw_density over its frames in place (-> 'annotated') and the JPEG encode (-> 'encoded' instead). Every launch is
+        a pure function of its inputs and the stages' previous state: `_run` may launch twice, the caller commits once."""
         net = self.net
         x, annotate, aug, track = ent.x, ent.draw, ent.tta, ent.track
         if aug is not None and aug.flip:
@@ -946,17 +810,14 @@ class Detector:
             a = self._assigner_for(b * max_boxes)
             crops = a.crops_of_slots(heat, pred['boxes'], pred['num_boxes'], 0, b * max_boxes)
             kscore, kpos = a.decode(a.net.predict(crops))
-        layout = record_layout(b, max_boxes, ent.oks, track, ent.nms, ent.track_eval, ent.zones, ent.trails, ent.density)
-        density_rows = layout[-1]                                   # (the end of the copy either way)
-        if ent.density is not None:                                 # the slices in front of the map's are what they are without it
-            layout = layout[:-1]
-        zone_rows = layout[-2] if ent.trails is not None else layout[-1]
-        in_record, oks_rows, track_rows, nms_info = layout[:4]
-        nbytes = in_record.stop
+        layout = ent.layout
+        nbytes = layout.record.stop
         if nbytes == 0:
             raise ValueError(f"predict_batch: {b} x {max_boxes} slots are more than mpn_pose_gather packs in one launch")
-        whole = torch.empty(density_rows.stop, dtype=torch.uint8, device=net.device)
-        filtered = whole[in_record]
+        whole = torch.empty(layout.nbytes, dtype=torch.uint8, device=net.device)
+        filtered = whole[layout.record]
+        # the tracker's identity rows, which every stage behind it reads (its smoothed and coasting rows lie behind them)
+        ids = whole[layout.track][:track.track_bytes(b)] if track is not None else None
         record = ent.nms.raw if ent.nms is not None else filtered    # what the gather writes
         if extent is None:
             _lib.call("mpn_pose_gather", _lib.ptr(pred['boxes']), _lib.ptr(pred['scores']), _lib.ptr(pred['num_boxes']), _lib.ptr(kscore),
@@ -967,23 +828,22 @@ class Detector:
                       _lib.ptr(kscore), _lib.ptr(kpos), _lib.ptr(pred['overflow']), b, max_boxes, float(score_threshold),
                       _lib.ptr(extent), _lib.ptr(record), nbytes, _lib.stream_ptr())
         if ent.nms is not None:                                     # every launch below reads the filtered record
-            record = ent.nms.launch(filtered, whole[nms_info])
+            record = ent.nms.launch(filtered, whole[layout.nms])
         if ent.oks is not None:
-            ent.oks.launch(record, whole[oks_rows])
+            ent.oks.launch(record, whole[layout.oks])
         if track is not None:                                       # (with smooth=: mpn_pose_smooth behind it, rows behind its rows)
-            track.launch_all(record, whole[track_rows], b)
+            track.launch_all(record, whole[layout.track], b)
         if ent.track_eval is not None:                              # the record the tracker read, its rows, the ground truth in place
-            ent.track_eval.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[4]], b,
-                                  *ent.oks.device_groundtruth())
+            ent.track_eval.launch(record, ids, whole[layout.track_eval], b, *ent.oks.device_groundtruth())
         if ent.zones is not None:                                   # the record the tracker read and its rows; without the PRN: boxes
-            ent.zones.launch(record, whole[track_rows][:track.track_bytes(b)], whole[zone_rows], b, self.assigner is not None)
-        if ent.trails is not None:                                  # likewise; its rows are the last part of the copy
-            ent.trails.launch(record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]], b, self.assigner is not None)
+            ent.zones.launch(record, ids, whole[layout.zones], b, self.assigner is not None)
+        if ent.trails is not None:                                  # likewise
+            ent.trails.launch(record, ids, whole[layout.trails], b, self.assigner is not None)
         density_drawn = (ent.density is not None and annotate is not None and ent.density.draw and
                          (ent.anonymize is None or ent.anonymize.spec.overlay))
         if ent.density is not None:                                 # the same record; identities where there is a tracker
-            ent.density.launch(record, whole[track_rows][:track.track_bytes(b)] if track is not None else None, whole[density_rows],
-                               b, self.assigner is not None, ent.density.snapshots(b) if density_drawn else None)
+            ent.density.launch(record, ids, whole[layout.density], b, self.assigner is not None,
+                               ent.density.snapshots(b) if density_drawn else None)
         dev['record'] = whole
         drawn = record
         if ent.anonymize is not None:                               # the drawing reads the anonymised frames in place of the sources
@@ -992,18 +852,15 @@ class Detector:
                 drawn = None                                        # (draw.Buffers.no_record: the frames with alpha 255)
         if annotate is not None and ent.style is not None:          # identities: mpn_draw_tracks on the rows just written
             style, table = ent.style
-            rows = whole[track_rows]
-            n = track.track_bytes(b)
-            smoothed = rows[n:] if style.keypoints == 'smoothed' else None
-            dev['annotated'] = annotate.launch_tracks(frames, record, rows[:n], smoothed, table, self.assigner is not None)
+            smoothed = whole[layout.track][track.track_bytes(b):] if style.keypoints == 'smoothed' else None
+            dev['annotated'] = annotate.launch_tracks(frames, record, ids, smoothed, table, self.assigner is not None)
         elif annotate is not None:
             dev['annotated'] = annotate.launch(frames, drawn, drawn is not None and self.assigner is not None)
         if annotate is not None and ent.trails is not None and ent.trails.draw and drawn is not None:
             # the polylines over the frames just written, in place, before they are encoded
-            ent.trails.launch_draw(annotate.desc, record, whole[track_rows][:track.track_bytes(b)], whole[layout[-1]],
-                                   dev['annotated'], b)
+            ent.trails.launch_draw(annotate.desc, record, ids, whole[layout.trails], dev['annotated'], b)
         if density_drawn:                                           # the map over everything drawn so far, in place
-            ent.density.launch_draw(annotate.desc, ent.density.snapshots(b), whole[density_rows], dev['annotated'], b)
+            ent.density.launch_draw(annotate.desc, ent.density.snapshots(b), whole[layout.density], dev['annotated'], b)
         return self._encode_frames(dev, ent.encode)
 
     def _keypoint_pass(self, x):
@@ -1161,16 +1018,7 @@ class Detector:
         if ent.track_eval is not None:
             ent.track_eval.place(groundtruth, len(groundtruth), rows=False)
         outs = self._run(ent, lambda: self._device_side_images(ent, opts.thr))
-        if ent.track is not None:
-            ent.track.commit()                                      # as in predict_batch: once per call, outside the graph
-        if ent.track_eval is not None:
-            ent.track_eval.commit()
-        if ent.zones is not None:
-            ent.zones.commit()
-        if ent.trails is not None:
-            ent.trails.commit()
-        if ent.density is not None:
-            ent.density.commit()
+        ent.commit()
         persons = self._finish(ent, outs, b, opts.return_heatmaps)
         if opts.return_heatmaps:
             for p, new_size in zip(persons, plan.new_sizes):

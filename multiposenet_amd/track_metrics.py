@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from .pose_metrics import GT_DOUBLES, MAX_GT, NUM_KEYPOINTS, check_max_gt, fill_record, groundtruth_arrays, pack_groundtruth
+from .stream_state import StreamState
 
 MAX_IDENTITIES = 1024                    # identities per stream the kernel's state takes
 MAX_BOXES = 64
@@ -40,8 +41,6 @@ _HYP = np.dtype([('gt', np.int32), ('flags', np.int32)])
 _TRACK_ROW = np.dtype([('track_id', np.int32), ('slot', np.int32), ('hits', np.int32), ('flags', np.int32),
                        ('similarity', np.float64)])
 _STATE_HEADER_WORDS = 4
-
-_serials = itertools.count(1)
 
 
 def groundtruth_track_ids(gt, g):
@@ -234,7 +233,7 @@ class TrackAccumulator:
         return self.stats
 
 
-class TrackEvaluator(TrackAccumulator):
+class TrackEvaluator(StreamState, TrackAccumulator):
     """CLEAR MOT and identity measures of `streams` independent cameras, on the device (`mpn_track_eval`).
 
     A call over b images sees b / streams consecutive frames per stream, stream s owning images s*F .. s*F+F-1 in time order,
@@ -247,6 +246,7 @@ class TrackEvaluator(TrackAccumulator):
     next pair on the device, and, on the host, one dict per stream from the file's ids to the dense indices the state is
     addressed by. `launch` is pure; `commit()` advances the state. `collect()` takes what `Detector.predict_*(track_eval=self)`
     returns, `update()` is the same launch for host dicts; `evaluate()` gives the numbers."""
+    keyword, _serials = 'track_eval', itertools.count(1)
 
     def __init__(self, streams=1, threshold=0.5, max_gt=MAX_GT, max_identities=256, max_boxes=25, device=None):
         self.streams, self.max_gt = int(streams), check_max_gt(max_gt)
@@ -263,12 +263,10 @@ class TrackEvaluator(TrackAccumulator):
         import torch
         self.device = torch.device(device) if device is not None else _lib.current_device()
         self.state_bytes = _lib.lib().mpn_track_eval_state_bytes(self.streams, self.max_identities)
-        self.stream_bytes = 4 * (_STATE_HEADER_WORDS + self.max_identities)
-        if self.state_bytes == 0 or self.state_bytes != self.streams * self.stream_bytes:
+        stream_bytes = 4 * (_STATE_HEADER_WORDS + self.max_identities)
+        if self.state_bytes == 0 or self.state_bytes != self.streams * stream_bytes:
             raise _lib.MpnError("mpn_track_eval: the state's layout is not the one this binding was written against")
-        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
+        self._make_state(stream_bytes)
         self._ids = [{} for _ in range(self.streams)]               # per stream: the file's id -> dense index
         self._buffers = {}
         self._placed = None                                         # (b, counts, identities) of the last `place`
@@ -277,12 +275,6 @@ class TrackEvaluator(TrackAccumulator):
         self.initialize()
 
     # ---------------------------------------------------------------- the device side
-    def check_batch(self, b):
-        """The number of images of a call -> frames per stream."""
-        if b < 1 or b % self.streams != 0:
-            raise ValueError(f"track_eval=: {b} images are not a whole number of frames for each of {self.streams} streams")
-        return b // self.streams
-
     def out_bytes(self, b):
         """The bytes of a call's rows for b images."""
         self.check_batch(b)
@@ -360,17 +352,9 @@ class TrackEvaluator(TrackAccumulator):
                   _lib.ptr(self.prev), _lib.ptr(self.next), self.state_bytes, _lib.ptr(out), out.numel(), _lib.stream_ptr())
         return out
 
-    def commit(self):
-        """The last launch's state becomes the current one: one small device copy on the current stream."""
-        self.prev.copy_(self.next, non_blocking=True)
-
     def reset(self, stream=None):
         """Forget the correspondences and the identities seen: of all streams, or of one. What was collected stays."""
-        if stream is not None and not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        part = slice(None) if stream is None else slice(int(stream) * self.stream_bytes, (int(stream) + 1) * self.stream_bytes)
-        self.prev[part].zero_()
-        self.next[part].zero_()
+        super().reset(stream)
         for s in range(self.streams) if stream is None else [int(stream)]:
             self._ids[s] = {}
             self._epoch[s] += 1
@@ -378,7 +362,7 @@ class TrackEvaluator(TrackAccumulator):
     def state(self, stream=0):
         """A host copy of one stream's current state: {'frames', 'track_ids' int32 [max_identities], 'identities' (the file's
         id -> dense index)}."""
-        raw = self.prev[int(stream) * self.stream_bytes:(int(stream) + 1) * self.stream_bytes].cpu().numpy().view(np.int32)
+        raw = self._raw_state(stream).view(np.int32)
         return {'frames': int(raw[0]), 'track_ids': raw[_STATE_HEADER_WORDS:].copy(), 'identities': dict(self._ids[int(stream)])}
 
     def unpack(self, out, counts):

@@ -22,14 +22,13 @@ import numpy as np
 
 from . import _lib
 from .pose_metrics import fill_record
+from .stream_state import StreamState, flag, integer
 from .zones import ANCHORS, MAX_BOXES, SLOTS, track_rows_of
 
 MAX_LENGTH, MAX_EVERY, MAX_GAP = 64, 255, 65535
 FLAG_TRACKED, FLAG_ANKLES, FLAG_NO_ANCHOR, FLAG_APPENDED, FLAG_RESTARTED = 1, 2, 4, 8, 16
 TABLE_HEADER_WORDS, TABLE_FADE = 4, 1
 DESC_WORDS = 8                          # mpn_draw_desc in 32-bit words
-
-_serials = itertools.count(1)
 
 
 def slot_dtype(length):
@@ -46,18 +45,6 @@ def state_dtype(length):
 def row_dtype(length):
     """A row of mpn_track_trails' out."""
     return np.dtype([('n', np.int32), ('flags', np.uint32), ('points', np.float32, (length + 1, 2))])
-
-
-def _integer(name, value, lo, hi):
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
-        raise ValueError(f"TrackTrails: {name} must be an integer in {lo}..{hi} (got {value!r})")
-    return int(value)
-
-
-def _flag(name, value):
-    if not isinstance(value, (bool, np.bool_)):
-        raise ValueError(f"TrackTrails: {name} must be False or True (got {value!r})")
-    return bool(value)
 
 
 def draw_table(palette, fade, min_alpha, length):
@@ -92,7 +79,7 @@ def rows_of(outputs, b, max_boxes, length):
     return rows.view(np.uint8)
 
 
-class TrackTrails:
+class TrackTrails(StreamState):
     """The last `length` anchors of every tracked identity, for `streams` independent cameras, on the device
     (`mpn_track_trails`), and how `annotate` draws them (`mpn_draw_trails`).
 
@@ -109,22 +96,23 @@ class TrackTrails:
     A call over b images sees b / streams consecutive frames per stream, stream s owning images s*F .. s*F+F-1 in time order,
     as `tracking.PoseTracker` does. The object owns the drawing's table on the device and the state - per stream 64 identities
     with their rings - as a prev / next pair. `launch` is pure; `commit()` advances the state. No default is tuned on video."""
+    keyword, _serials = 'trails', itertools.count(1)
 
     def __init__(self, streams=1, frame_size=None, length=32, every=1, max_gap=30, anchor='feet', min_keypoint_score=0.0,
                  draw=True, fade=True, min_alpha=64, palette=None, max_boxes=25, device=None):
         from .inference.draw import DEFAULT_PALETTE, MAX_PALETTE, _colour
         if isinstance(streams, (bool, np.bool_)) or not isinstance(streams, (int, np.integer)) or streams < 1:
             raise ValueError(f"TrackTrails: streams must be an integer >= 1 (got {streams!r})")
-        self.max_boxes = _integer('max_boxes', max_boxes, 1, MAX_BOXES)
+        self.max_boxes = integer('TrackTrails', 'max_boxes', max_boxes, 1, MAX_BOXES)
         try:
             height, width = (float(v) for v in frame_size)
         except (TypeError, ValueError):
             raise ValueError(f"TrackTrails: frame_size must be (height, width) (got {frame_size!r})") from None
         if not (math.isfinite(height) and math.isfinite(width) and height > 0 and width > 0):
             raise ValueError(f"TrackTrails: frame_size must be two positive numbers (height, width) (got {frame_size!r})")
-        self.length = _integer('length', length, 1, MAX_LENGTH)
-        self.every = _integer('every', every, 1, MAX_EVERY)
-        self.max_gap = _integer('max_gap', max_gap, 0, MAX_GAP)
+        self.length = integer('TrackTrails', 'length', length, 1, MAX_LENGTH)
+        self.every = integer('TrackTrails', 'every', every, 1, MAX_EVERY)
+        self.max_gap = integer('TrackTrails', 'max_gap', max_gap, 0, MAX_GAP)
         if not isinstance(anchor, str) or anchor not in ANCHORS:
             raise ValueError(f"TrackTrails: anchor must be one of {list(ANCHORS)} (got {anchor!r})")
         try:
@@ -133,8 +121,8 @@ class TrackTrails:
             raise ValueError(f"TrackTrails: min_keypoint_score must be a number (got {min_keypoint_score!r})") from None
         if not math.isfinite(mks):
             raise ValueError(f"TrackTrails: min_keypoint_score must be finite (got {min_keypoint_score!r})")
-        self.draw, self.fade = _flag('draw', draw), _flag('fade', fade)
-        self.min_alpha = _integer('min_alpha', min_alpha, 0, 255)
+        self.draw, self.fade = flag('TrackTrails', 'draw', draw), flag('TrackTrails', 'fade', fade)
+        self.min_alpha = integer('TrackTrails', 'min_alpha', min_alpha, 0, 255)
         if palette is None:
             palette = DEFAULT_PALETTE
         try:
@@ -152,26 +140,17 @@ class TrackTrails:
         self.row, self.state_row = row_dtype(self.length), state_dtype(self.length)
         lib = _lib.lib()
         self.state_bytes = lib.mpn_track_trails_state_bytes(self.streams, self.length)
-        self.stream_bytes = self.state_row.itemsize
-        if self.state_bytes != self.streams * self.stream_bytes:
+        if self.state_bytes != self.streams * self.state_row.itemsize:
             raise ValueError(f"TrackTrails: streams = {streams!r} are more than mpn_track_trails takes")
         self.host_table = draw_table(self.palette, self.fade, self.min_alpha, self.length)
         import torch
         self.device = torch.device(device) if device is not None else _lib.current_device()
         self.table = torch.from_numpy(self.host_table.copy()).to(self.device)
-        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
+        self._make_state(self.state_row.itemsize)
         self._update, self._work = {}, {}
         self.last_out = None
 
     # ---------------------------------------------------------------- the device side
-    def check_batch(self, b):
-        """The number of images of a call -> frames per stream."""
-        if b < 1 or b % self.streams != 0:
-            raise ValueError(f"trails=: {b} images are not a whole number of frames for each of {self.streams} streams")
-        return b // self.streams
-
     def check_frame_sizes(self, sizes):
         """Raises unless every (height, width) of `sizes` is the object's frame_size."""
         for h, w in sizes:
@@ -213,24 +192,9 @@ class TrackTrails:
                   _lib.ptr(work), work.numel(), _lib.stream_ptr())
         return out_rgba
 
-    def commit(self):
-        """The last launch's state becomes the current one: one small device copy on the current stream."""
-        self.prev.copy_(self.next, non_blocking=True)
-
-    def reset(self, stream=None):
-        """Forget every trail and set the frame count to zero: of all streams, or of one."""
-        if stream is not None and not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        part = slice(None) if stream is None else slice(int(stream) * self.stream_bytes, (int(stream) + 1) * self.stream_bytes)
-        self.prev[part].zero_()
-        self.next[part].zero_()
-
     def state(self, stream=0):
         """A host copy of one stream's current state, as a `state_dtype(length)` record."""
-        if not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        raw = self.prev[int(stream) * self.stream_bytes:(int(stream) + 1) * self.stream_bytes].cpu().numpy()
-        return raw.view(self.state_row)[0]
+        return self._raw_state(stream).view(self.state_row)[0]
 
     def unpack(self, out, counts):
         """A host copy of the output rows (uint8 array) and the record's per-image counts -> a list of b dicts. With n persons

@@ -25,6 +25,7 @@ import math
 import numpy as np
 
 from . import _lib
+from .stream_state import StreamState
 from .tracking import fill_record
 
 MAX_ZONES = MAX_LINES = MAX_VERTICES = 16
@@ -50,8 +51,6 @@ IMAGE = np.dtype([(k, np.uint32, (16,)) for k in ('occupancy', 'entries', 'exits
                                                   'total_exits', 'total_positive', 'total_negative')])
 _TRACK_ROW = np.dtype([('track_id', np.int32), ('slot', np.int32), ('hits', np.int32), ('flags', np.int32),
                        ('similarity', np.float64)])
-
-_serials = itertools.count(1)
 
 
 def _named(what, given, most):
@@ -134,7 +133,7 @@ def track_rows_of(outputs, b, max_boxes):
     return rows.view(np.uint8)
 
 
-class ZoneCounter:
+class ZoneCounter(StreamState):
     """Occupancy, entries, exits and dwell times of up to 16 polygons and signed crossings of up to 16 lines, for `streams`
     independent cameras that share one geometry, on the device (`mpn_zone_events`).
 
@@ -150,6 +149,7 @@ class ZoneCounter:
     as `tracking.PoseTracker` does. The counter owns the table on the device and the state - per stream the cumulative
     counters and 64 identities with their membership, last anchor and dwell - as a prev / next pair. `launch` is pure;
     `commit()` advances the state. No default is tuned on video."""
+    keyword, _serials = 'zones', itertools.count(1)
 
     def __init__(self, streams=1, frame_size=None, zones=None, lines=None, anchor='feet', min_frames=1, min_keypoint_score=0.0,
                  max_boxes=25, device=None):
@@ -163,8 +163,7 @@ class ZoneCounter:
         self.anchor, self.min_frames, self.min_keypoint_score = anchor, int(min_frames), float(min_keypoint_score)
         lib = _lib.lib()
         self.state_bytes = lib.mpn_zone_state_bytes(self.streams)
-        self.stream_bytes = STATE.itemsize
-        if lib.mpn_zone_table_bytes() != TABLE.itemsize or self.state_bytes != self.streams * self.stream_bytes:
+        if lib.mpn_zone_table_bytes() != TABLE.itemsize or self.state_bytes != self.streams * STATE.itemsize:
             raise _lib.MpnError("mpn_zone_events: the table's or the state's layout is not the one this binding was written against")
         import torch
         self.device = torch.device(device) if device is not None else _lib.current_device()
@@ -174,19 +173,11 @@ class ZoneCounter:
         if boxes_only[0]['anchor'] == ANCHORS['feet']:
             boxes_only[0]['anchor'] = ANCHORS['box_bottom']
         self.table_boxes = torch.from_numpy(boxes_only.view(np.uint8).copy()).to(self.device)
-        self.prev = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.next = torch.zeros(self.state_bytes, dtype=torch.uint8, device=self.device)
-        self.serial = next(_serials)                                # process-unique: part of the key of a Detector's graph
+        self._make_state(STATE.itemsize)
         self._update = {}
         self.last_out = None
 
     # ---------------------------------------------------------------- the device side
-    def check_batch(self, b):
-        """The number of images of a call -> frames per stream."""
-        if b < 1 or b % self.streams != 0:
-            raise ValueError(f"zones=: {b} images are not a whole number of frames for each of {self.streams} streams")
-        return b // self.streams
-
     def check_frame_sizes(self, sizes):
         """Raises unless every (height, width) of `sizes` is the counter's frame_size."""
         for h, w in sizes:
@@ -212,24 +203,9 @@ class ZoneCounter:
                   _lib.stream_ptr())
         return out
 
-    def commit(self):
-        """The last launch's state becomes the current one: one small device copy on the current stream."""
-        self.prev.copy_(self.next, non_blocking=True)
-
-    def reset(self, stream=None):
-        """Forget the identities and set the counters and the frame count to zero: of all streams, or of one."""
-        if stream is not None and not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        part = slice(None) if stream is None else slice(int(stream) * self.stream_bytes, (int(stream) + 1) * self.stream_bytes)
-        self.prev[part].zero_()
-        self.next[part].zero_()
-
     def state(self, stream=0):
         """A host copy of one stream's current state, as a STATE record."""
-        if not 0 <= int(stream) < self.streams:
-            raise ValueError(f"stream must be in 0..{self.streams - 1} (got {stream})")
-        raw = self.prev[int(stream) * self.stream_bytes:(int(stream) + 1) * self.stream_bytes].cpu().numpy()
-        return raw.view(STATE)[0]
+        return self._raw_state(stream).view(STATE)[0]
 
     def totals(self, stream=0):
         """A host copy of one stream's cumulative counters: {'frames', 'entries', 'exits' (by zone name), 'line_positive',

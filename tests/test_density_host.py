@@ -438,17 +438,18 @@ def test_entry_keys_with_density_and_without(use_graph):
 
 
 def test_record_layout_ends_with_the_density_rows():
-    from multiposenet_amd.inference.detector import record_layout
+    from multiposenet_amd.inference.detector import RecordLayout
     density, trails = _density(), _trails()
-    four = record_layout(4, 25)
-    assert record_layout(4, 25, density=None) == four
-    five = record_layout(4, 25, density=density)
-    assert five[:4] == four and len(five) == 5 and five[4].start % 16 == 0 and five[4].start >= four[3].stop
-    assert five[4].stop - five[4].start == density.out_bytes(4) == 4 * 25 * 16 + 4 * 16
-    with_trails = record_layout(4, 25, trails=trails)
-    six = record_layout(4, 25, trails=trails, density=density)
-    assert six[:5] == with_trails and len(six) == 6 and six[5].start % 16 == 0 and six[5].start >= with_trails[4].stop
-    assert six[5].stop - six[5].start == density.out_bytes(4)
+    four = RecordLayout(4, 25)
+    assert RecordLayout(4, 25, density=None).astuple() == four.astuple()
+    five = RecordLayout(4, 25, density=density)
+    assert five.astuple()[:-1] == four.astuple()[:-1] and five.density.start % 16 == 0 and five.density.start >= four.nms.stop
+    assert five.density.stop - five.density.start == density.out_bytes(4) == 4 * 25 * 16 + 4 * 16 and five.nbytes == five.density.stop
+    with_trails = RecordLayout(4, 25, trails=trails)
+    six = RecordLayout(4, 25, trails=trails, density=density)
+    assert six.astuple()[:-1] == with_trails.astuple()[:-1] and RecordLayout.PARTS[-1] == 'density'
+    assert six.density.start % 16 == 0 and six.density.start >= with_trails.trails.stop
+    assert six.density.stop - six.density.start == density.out_bytes(4)
 
 
 def test_track_frames_has_the_switches(capsys):

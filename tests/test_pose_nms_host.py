@@ -1,5 +1,5 @@
 """CPU: the plain-loop reference of mpn_pose_nms against an independent numpy formulation; the case table shows what it is
-there for and decides nothing within 1e-9; `PoseNms`; the checks, messages and entry keys of `pose_nms=`; `record_layout`;
+there for and decides nothing within 1e-9; `PoseNms`; the checks, messages and entry keys of `pose_nms=`; `RecordLayout`;
 the launcher's checks without a GPU; the command lines' flags."""
 import ctypes
 import re
@@ -16,7 +16,7 @@ from test_detector_options_host import B, CAP, H, SERIAL, STYLE, THR, W, _detect
 
 from multiposenet_amd import _lib
 from multiposenet_amd.inference import OneEuro, PoseNms
-from multiposenet_amd.inference.detector import record_layout
+from multiposenet_amd.inference.detector import RecordLayout
 
 N = PoseNms(0.75, 0.25, 'box*keypoints')
 
@@ -224,14 +224,16 @@ def test_record_layout_has_four_slices():
         oks = types.SimpleNamespace(out_bytes=lib.mpn_oks_match_out_bytes(b, mb))
         nms = types.SimpleNamespace(info_bytes=lib.mpn_pose_nms_info_bytes(b, mb))
         trk = _tracker(smooth=OneEuro(), max_boxes=mb)
-        assert record_layout(b, mb) == (slice(0, record), slice(record, record), slice(record, record), slice(record, record))
-        assert record_layout(b, mb, oks, trk)[:3] == record_layout(b, mb, oks, trk, None)[:3]
+        base = lambda layout: (layout.record, layout.oks, layout.track, layout.nms)     # noqa: E731
+        assert base(RecordLayout(b, mb)) == (slice(0, record), slice(record, record), slice(record, record), slice(record, record))
+        assert base(RecordLayout(b, mb, oks, trk))[:3] == base(RecordLayout(b, mb, oks, trk, None))[:3]
         end = record + oks.out_bytes + trk.out_bytes(b)
         at = (end + 15) // 16 * 16
         assert trk.out_bytes(b) % 8 == 4 * (b * mb % 2)             # 364 bytes a slot: the info block needs its own alignment
-        assert record_layout(b, mb, oks, trk, nms) == (slice(0, record), slice(record, record + oks.out_bytes),
-                                                       slice(record + oks.out_bytes, end), slice(at, at + nms.info_bytes))
-        assert record_layout(b, mb, nms=nms)[3] == slice(record, record + nms.info_bytes) and record % 16 == 0
+        assert base(RecordLayout(b, mb, oks, trk, nms)) == (slice(0, record), slice(record, record + oks.out_bytes),
+                                                            slice(record + oks.out_bytes, end), slice(at, at + nms.info_bytes))
+        assert RecordLayout(b, mb, oks, trk, nms).nbytes == at + nms.info_bytes
+        assert RecordLayout(b, mb, nms=nms).nms == slice(record, record + nms.info_bytes) and record % 16 == 0
         assert nms.info_bytes == (4 * b + 15) // 16 * 16 + 16 * b * mb == ref.info_bytes(b, mb)
         assert record == ref.record_bytes(b, mb)
 

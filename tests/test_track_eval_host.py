@@ -274,15 +274,18 @@ def test_public_names_and_keywords():
 
 
 def test_record_layout_keeps_its_four_slices():
-    from multiposenet_amd.inference.detector import record_layout
+    from multiposenet_amd.inference.detector import RecordLayout
 
     class Rows:
         def out_bytes(self, b):
             return 1000 + b
-    four = record_layout(4, 25)
-    assert len(four) == 4 and len(record_layout(4, 25, track_eval=None)) == 4
-    five = record_layout(4, 25, track_eval=Rows())
-    assert five[:4] == four and five[4].start % 16 == 0 and five[4].start >= four[3].stop and five[4].stop - five[4].start == 1004
+    base = lambda layout: (layout.record, layout.oks, layout.track, layout.nms)     # noqa: E731
+    four = RecordLayout(4, 25)
+    assert RecordLayout(4, 25, track_eval=None).astuple() == four.astuple()
+    assert four.track_eval == slice(four.nms.stop, four.nms.stop) and four.nbytes == four.record.stop
+    five = RecordLayout(4, 25, track_eval=Rows())
+    assert base(five) == base(four) and five.track_eval.start % 16 == 0 and five.track_eval.start >= four.nms.stop
+    assert five.track_eval.stop - five.track_eval.start == 1004 and five.nbytes == five.track_eval.stop
 
 
 def test_track_frames_has_the_switches(capsys):

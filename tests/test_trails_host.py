@@ -363,17 +363,20 @@ def test_entry_keys_with_trails_and_without(use_graph):
 
 
 def test_record_layout_ends_with_the_trail_rows():
-    from multiposenet_amd.inference.detector import record_layout
+    from multiposenet_amd.inference.detector import RecordLayout
     trails, counter = _trails(length=5), _counter()
-    four = record_layout(4, 25)
-    assert record_layout(4, 25, trails=None) == four
-    five = record_layout(4, 25, trails=trails)
-    assert five[:4] == four and len(five) == 5 and five[4].start % 16 == 0 and five[4].start >= four[3].stop
-    assert five[4].stop - five[4].start == trails.out_bytes(4) == 4 * 25 * 8 * 7
-    with_zones = record_layout(4, 25, zones=counter)
-    six = record_layout(4, 25, zones=counter, trails=trails)
-    assert six[:5] == with_zones and len(six) == 6 and six[5].start % 16 == 0 and six[5].start >= with_zones[4].stop
-    assert six[5].stop - six[5].start == trails.out_bytes(4)
+    base = lambda layout: (layout.record, layout.oks, layout.track, layout.nms)     # noqa: E731
+    four = RecordLayout(4, 25)
+    assert RecordLayout(4, 25, trails=None).astuple() == four.astuple()
+    five = RecordLayout(4, 25, trails=trails)
+    assert base(five) == base(four) and (five.track_eval, five.zones) == (four.track_eval, four.zones)
+    assert five.trails.start % 16 == 0 and five.trails.start >= four.nms.stop
+    assert five.trails.stop - five.trails.start == trails.out_bytes(4) == 4 * 25 * 8 * 7 and five.nbytes == five.trails.stop
+    with_zones = RecordLayout(4, 25, zones=counter)
+    six = RecordLayout(4, 25, zones=counter, trails=trails)
+    assert base(six) + (six.track_eval, six.zones) == base(with_zones) + (with_zones.track_eval, with_zones.zones)
+    assert six.trails.start % 16 == 0 and six.trails.start >= with_zones.zones.stop
+    assert six.trails.stop - six.trails.start == trails.out_bytes(4)
 
 
 def test_track_frames_has_the_switches(capsys):

@@ -256,21 +256,24 @@ def test_entry_keys_with_a_counter_and_without(use_graph):
 
 
 def test_record_layout_ends_with_the_zone_rows():
-    from multiposenet_amd.inference.detector import record_layout
+    from multiposenet_amd.inference.detector import RecordLayout
 
     class Rows:
         def out_bytes(self, b):
             return 1000 + b
     counter = _counter()
-    four = record_layout(4, 25)
-    assert record_layout(4, 25, zones=None) == four
-    five = record_layout(4, 25, zones=counter)
-    assert five[:4] == four and len(five) == 5 and five[4].start % 16 == 0 and five[4].start >= four[3].stop
-    assert five[4].stop - five[4].start == counter.out_bytes(4) == 4 * (25 * 104 + 576)
-    with_eval = record_layout(4, 25, track_eval=Rows())
-    six = record_layout(4, 25, track_eval=Rows(), zones=counter)
-    assert six[:5] == with_eval and six[5].start % 16 == 0 and six[5].start >= with_eval[4].stop
-    assert six[5].stop - six[5].start == counter.out_bytes(4)
+    base = lambda layout: (layout.record, layout.oks, layout.track, layout.nms)     # noqa: E731
+    four = RecordLayout(4, 25)
+    assert RecordLayout(4, 25, zones=None).astuple() == four.astuple()
+    five = RecordLayout(4, 25, zones=counter)
+    assert base(five) == base(four) and five.track_eval == four.track_eval
+    assert five.zones.start % 16 == 0 and five.zones.start >= four.nms.stop
+    assert five.zones.stop - five.zones.start == counter.out_bytes(4) == 4 * (25 * 104 + 576) and five.nbytes == five.zones.stop
+    with_eval = RecordLayout(4, 25, track_eval=Rows())
+    six = RecordLayout(4, 25, track_eval=Rows(), zones=counter)
+    assert base(six) + (six.track_eval,) == base(with_eval) + (with_eval.track_eval,)
+    assert six.zones.start % 16 == 0 and six.zones.start >= with_eval.track_eval.stop
+    assert six.zones.stop - six.zones.start == counter.out_bytes(4)
 
 
 def test_track_frames_has_the_switch(capsys):

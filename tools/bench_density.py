@@ -51,7 +51,6 @@ def main():
         raise SystemExit("bench_density: no GPU (a measurement path does not fall back)")
     from multiposenet_amd.density import IMAGE, ROW
     from multiposenet_amd.inference import DensityMap, PoseTracker
-    from multiposenet_amd.inference.detector import record_layout
     det = build_detector(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     b, s, thr = args.batch, args.size, args.threshold
     sh, sw = args.source
@@ -74,8 +73,8 @@ def main():
             "without": next(e for e in det._graphs.values() if getattr(e, 'track', None) is without)}
     ent = ents["with"]
     whole = ent.outs['record']
-    layout = record_layout(b, max_boxes, ent.oks, with_density, ent.nms, None, None, None, density)
-    record, rows, density_rows = whole[layout[0]], whole[layout[2]], whole[layout[-1]]
+    layout = ent.layout                                             # the entry's own: where each stage's rows lie
+    record, rows, density_rows = whole[layout.record], whole[layout.track], whole[layout.density]
     track_rows = rows[:with_density.track_bytes(b)]
     frames_rgba = ent.draw.out
     copy_of_frames = torch.empty_like(frames_rgba)

@@ -106,9 +106,8 @@ def main():
             "without": next(e for e in det._graphs.values() if getattr(e, 'track', None) is without)}
     ent = ents["with"]
     whole = ent.outs['record']
-    from multiposenet_amd.inference.detector import record_layout
-    layout = record_layout(b, max_boxes, ent.oks, with_eval, ent.nms, evaluator)
-    record, track_rows, eval_rows = whole[layout[0]], whole[layout[2]], whole[layout[4]]
+    layout = ent.layout                                             # the entry's own: where each stage's rows lie
+    record, track_rows, eval_rows = whole[layout.record], whole[layout.track], whole[layout.track_eval]
 
     def eval_and_commit():
         evaluator.launch(record, track_rows[:with_eval.track_bytes(b)], eval_rows, b, *ent.oks.device_groundtruth())

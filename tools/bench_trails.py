@@ -52,7 +52,6 @@ def main():
         raise SystemExit("bench_trails: no GPU (a measurement path does not fall back)")
     from multiposenet_amd import _lib
     from multiposenet_amd.inference import PoseTracker, TrackStyle, TrackTrails
-    from multiposenet_amd.inference.detector import record_layout
     from multiposenet_amd.trails import row_dtype
     det = build_detector(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     b, s, thr = args.batch, args.size, args.threshold
@@ -78,8 +77,8 @@ def main():
             "without": next(e for e in det._graphs.values() if getattr(e, 'track', None) is without)}
     ent = ents["with"]
     whole = ent.outs['record']
-    layout = record_layout(b, max_boxes, ent.oks, with_trails, ent.nms, None, None, trails)
-    record, rows, trail_rows = whole[layout[0]], whole[layout[2]], whole[layout[-1]]
+    layout = ent.layout                                             # the entry's own: where each stage's rows lie
+    record, rows, trail_rows = whole[layout.record], whole[layout.track], whole[layout.trails]
     track_rows = rows[:with_trails.track_bytes(b)]
     table = ent.style[1]
     frames_rgba = ent.draw.out
@@ -92,7 +91,7 @@ def main():
     start = rng.uniform(0.2, 0.8, (b * max_boxes, 1, 2)) * (sw, sh)
     hand['points'] = (start + np.cumsum(rng.uniform(-6, 6, (b * max_boxes, K + 1, 2)), axis=1)).astype(np.float32)
     hand_rows = torch.from_numpy(hand.view(np.uint8)).to(whole.device)
-    full_record = whole[layout[0]].clone()
+    full_record = whole[layout.record].clone()
     header = np.zeros(1 + b, np.int32)
     header[0], header[1:] = b * max_boxes, max_boxes
     full_record[:header.nbytes].copy_(torch.from_numpy(header.view(np.uint8)))

@@ -66,7 +66,6 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_zones: no GPU (a measurement path does not fall back)")
     from multiposenet_amd.inference import PoseTracker, ZoneCounter
-    from multiposenet_amd.inference.detector import record_layout
     det = build_detector(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     b, s, thr = args.batch, args.size, args.threshold
     sh, sw = args.source
@@ -109,8 +108,8 @@ def main():
             "without": next(e for e in det._graphs.values() if getattr(e, 'track', None) is without)}
     ent = ents["with"]
     whole = ent.outs['record']
-    layout = record_layout(b, max_boxes, ent.oks, with_zones, ent.nms, None, counter)
-    record, track_rows, zone_rows = whole[layout[0]], whole[layout[2]], whole[layout[-1]]
+    layout = ent.layout                                             # the entry's own: where each stage's rows lie
+    record, track_rows, zone_rows = whole[layout.record], whole[layout.track], whole[layout.zones]
 
     def zones_and_commit():
         counter.launch(record, track_rows[:with_zones.track_bytes(b)], zone_rows, b)
