@@ -1769,6 +1769,92 @@ int mpn_anonymize(const uint8_t* sources, size_t sources_bytes, const void* desc
                   size_t out_bytes, void* workspace, size_t workspace_bytes, mpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Person crops: per row of mpn_pose_gather[_sized]'s record the picture of that person, cut from its frame and resized to
+ * H x W, equal byte for byte to Pillow's `Image.resize((new_w, new_h), Image.BICUBIC, box=(x0, y0, x1, y1))` of the WHOLE
+ * frame (so the taps at the rectangle's edge read the frame's pixels beside it, not a border). The boxes exist only on the
+ * device: the tap tables of every crop are built there. tests/crops_ref.py restates everything below as plain loops;
+ * tests/test_person_crops_host.py holds that restatement against Pillow.
+ *
+ * All floating-point work is IEEE float64 on values widened from the record's float32, one operation at a time in the order
+ * written, no contraction (the file is compiled with contraction off); it relies on the device's float64 division being
+ * correctly rounded, as the tracker's and the smoother's sections do. h, w are the descriptor's.
+ *   rectangle  (ymin, xmin, ymax, xmax) = (h*box[0], w*box[1], h*box[2], w*box[3]), as mpn_draw_detections;
+ *              bw = xmax - xmin; bh = ymax - ymin; px = pad*bw; py = pad*bh;
+ *              x0 = xmin - px; x1 = xmax + px; y0 = ymin - py; y1 = ymax + py.
+ *              One of the four not finite: EMPTY, rect = (0, 0, 0, 0), not clipped. Else the clamps, each setting CLIPPED
+ *              when it moves a bound: if x0 < 0: x0 = 0;  if x1 > w: x1 = w;  if y0 < 0: y0 = 0;  if y1 > h: y1 = h.
+ *              rw = x1 - x0; rh = y1 - y0; not (rw > 0) or not (rh > 0): EMPTY (rect is still reported).
+ *   placement  fit 0 (stretch): (top, left, new_h, new_w) = (0, 0, H, W).
+ *              fit 1 (pad): s = min(H / rh, W / rw); new_h = (int)min(H, max(1, rint(rh*s))), new_w likewise with rw and W
+ *              (rint: half to even, what Python's `round` does in resample.resized_size); top = (H - new_h) / 2,
+ *              left = (W - new_w) / 2 (integer division). Every pixel outside the placed part is `fill`.
+ *   taps       per axis, (in0, in1, in_size, out) = (x0, x1, w, new_w) and (y0, y1, h, new_h): scale = (in1 - in0) / out;
+ *              filterscale = max(scale, 1); support = 2*filterscale; ss = 1 / filterscale;
+ *              ksize = (int)ceil(support)*2 + 1. ksize > MPN_IMAGE_RESIZE_MAX_KSIZE on either axis (a reduction beyond
+ *              16x): TOO_LARGE. For output xx: center = in0 + (xx + 0.5)*scale;
+ *              first = max((int)(center - support + 0.5), 0); last = min((int)(center + support + 0.5), in_size)
+ *              (truncation toward zero); weight k = bicubic((k + first - center + 0.5)*ss), k = 0 .. last - first - 1, with
+ *              bicubic(x), a = -0.5, on |x|: < 1: ((a + 2)*x - (a + 3))*x*x + 1;  < 2: (((x - 5)*x + 8)*x - 4)*a;  else 0.
+ *              The weights are summed in tap order from 0.0; a sum that is not 0 divides each; the coefficient is
+ *              (int)(w*2^22 + 0.5), for w < 0 (int)(w*2^22 - 0.5): 22 fractional bits, rounded half away from zero.
+ *              (Pillow multiplies by ss where one might divide by filterscale; this follows Pillow.)
+ *   passes     the integer arithmetic of mpn_image_resize: clip8((sum_k pixel[first + k]*coeff[k] + 2^21) >> 22) in int32, the
+ *              horizontal pass first, rounded to uint8, then the vertical pass. Both always run: at scale 1 and an integer
+ *              offset the taps are the identity, which is what Pillow's skipping the pass leaves.
+ *   slots      slot s is row s of the record, s < total (the header's, clamped to B*max_boxes): the order of the result
+ *              dicts' 'boxes'. An EMPTY or TOO_LARGE crop is all `fill`. A row whose image_index is not the image the
+ *              header's counts give it, or whose frame's descriptor is refused (below), is EMPTY with a zero rect. Slots at
+ *              and behind total are written as zeros, crops and info rows: both buffers are a function of the inputs.
+ *
+ *   sources, descs   as for mpn_draw_detections / mpn_anonymize: [B] mpn_draw_desc, DEVICE, 16-byte aligned; src_offset, h, w
+ *               are read. A pixel is read as one unaligned dword except the last of its frame (as mpn_image_resize reads):
+ *               nothing outside a frame's own bytes is touched. A frame that reaches outside sources_bytes, or has h, w
+ *               outside [1, 65536] or h*w > 2^29, is refused on the device.
+ *   record      as for mpn_draw_detections (with mpn_pose_nms: the filtered one): header and the rows' image_index and box
+ *   H, W        the crop: multiples of 8, 8 <= H <= MPN_PERSON_CROPS_MAX_H, 8 <= W <= MPN_PERSON_CROPS_MAX_W
+ *   pad         finite, 0 <= pad <= 4;  fit 0 or 1;  fill = R | G << 8 | B << 16
+ *   crops_out   uint8 [B*max_boxes, H, W, 3], 16-byte aligned; every byte is written
+ *   info_out    [B*max_boxes] mpn_person_crops_info, 16-byte aligned (mpn_person_crops_info_bytes(B, max_boxes))
+ *   workspace   mpn_person_crops_workspace_bytes(B, max_boxes, H, W) bytes (0 for arguments out of range), 16-byte aligned:
+ *               per slot and output coordinate (W columns, then H rows) a tap row of MPN_PERSON_CROPS_TAP_WORDS int32:
+ *               first, count, 0, then the coefficients.
+ * Two launches. (1) one thread per (slot, axis, output coordinate) writes its tap row - the weight sum sequential in tap
+ * order - and thread 0 of the slot the info row. (2) one block per (slot, tile of output rows): the horizontal pass over
+ * exactly the source rows the tile's vertical taps need, into LDS as uint8 (new_w*3 bytes a row), then the vertical pass
+ * from LDS into crops_out; no intermediate goes to global memory. The tile height depends on (H, W) alone - the largest
+ * whose tile*16 + 64 rows of W*3 bytes fit MPN_PERSON_CROPS_LDS_BYTES - and how many of those rows a slot uses is a
+ * device value. Grid and block sizes depend on (B, max_boxes, H, W) alone; rectangles, tap counts and offsets travel through
+ * device memory, so a captured graph serves every later record. The tap loops are bounded by the tap rows (count <=
+ * MPN_IMAGE_RESIZE_MAX_KSIZE, first + count <= the frame) and every LDS row index is checked against the rows the block
+ * holds: no descriptor or record makes a kernel write outside crops_out, info_out or the workspace, or read outside sources.
+ * Checked before any HIP call, the messages begin "person_crops:": null pointers (MPN_ERR_BAD_ARG); 1 <= B <= 65535,
+ * 1 <= max_boxes <= MPN_DRAW_MAX_BOXES, B*max_boxes <= 4096, H and W (MPN_ERR_BAD_SHAPE); pad, fit, fill
+ * (MPN_ERR_BAD_ARG); descs, record, crops_out, info_out, workspace 16-byte aligned (MPN_ERR_BAD_ALIGN); record_bytes,
+ * workspace_bytes, sources_bytes >= 3 (MPN_ERR_WORKSPACE).
+ */
+#define MPN_PERSON_CROPS_MAX_H 512
+#define MPN_PERSON_CROPS_MAX_W 256
+#define MPN_PERSON_CROPS_TAP_WORDS 68
+#define MPN_PERSON_CROPS_LDS_BYTES 163840
+#define MPN_PERSON_CROPS_EMPTY 1
+#define MPN_PERSON_CROPS_TOO_LARGE 2
+#define MPN_PERSON_CROPS_CLIPPED 4
+#define MPN_PERSON_CROPS_USED 8
+typedef struct mpn_person_crops_info {
+    double rect[4];                             /* x0, y0, x1, y1 in the pixels of the frame */
+    int32_t placed[4];                          /* top, left, new_h, new_w inside the crop (zeros for an EMPTY crop) */
+    int32_t flags;                              /* MPN_PERSON_CROPS_*; 0: a slot at or behind the record's total */
+    int32_t image;                              /* the row's image, -1 where a used row has none */
+    int32_t ksize_x, ksize_y;                   /* tap row lengths (clamped to 2^20), 0 for an EMPTY crop */
+} mpn_person_crops_info;
+size_t mpn_person_crops_desc_bytes(void);
+size_t mpn_person_crops_info_bytes(int B, int max_boxes);
+size_t mpn_person_crops_workspace_bytes(int B, int max_boxes, int H, int W);
+int mpn_person_crops(const uint8_t* sources, size_t sources_bytes, const void* descs, const void* record, size_t record_bytes,
+                     int B, int max_boxes, int H, int W, double pad, int fit, int fill, uint8_t* crops_out, void* info_out,
+                     void* workspace, size_t workspace_bytes, mpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Heatmap and mask overlays: `plot_maps` of the reference's inference/predict.ipynb (the cells under "Show heatmaps") for
  * a batch of B frames of one size, equal byte for byte to what Pillow and matplotlib make there. With h = H / 2, w = W / 2
  * (integer division), panel j of frame b is rows j*h .. j*h + h - 1 of out_rgba[b]: the frame resized to (w, h) with

@@ -198,6 +198,10 @@ SIGNATURES = {
     "mpn_anonymize_params_bytes": (_Z, []),
     "mpn_anonymize_workspace_bytes": (_Z, [_I, _I]),
     "mpn_anonymize": (_I, [_P, _Z, _P, _P, _Z, _I, _I, _I, _P, _P, _Z, _P, _Z, _P]),
+    "mpn_person_crops_desc_bytes": (_Z, []),
+    "mpn_person_crops_info_bytes": (_Z, [_I, _I]),
+    "mpn_person_crops_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "mpn_person_crops": (_I, [_P, _Z, _P, _P, _Z, _I, _I, _I, _I, _D, _I, _I, _P, _P, _P, _Z, _P]),
     "mpn_plot_maps_desc_bytes": (_Z, []),
     "mpn_plot_maps_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "mpn_plot_maps": (_I, [_P, _P, _P, _P, _P, _Z, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),

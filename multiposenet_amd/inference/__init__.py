@@ -2,6 +2,7 @@ from .utils import get_keypoints, get_keypoints_batch, KeypointDecoder, draw_eve
 from .detector import Detector  # noqa: F401
 from .draw import TrackStyle  # noqa: F401
 from .anonymize_stage import Anonymize, Anonymizer, anonymize  # noqa: F401
+from .crops import PersonCrops, PersonCropper, person_crops  # noqa: F401
 from .jpeg import JpegBatchEncoder, encode_jpegs  # noqa: F401
 from .maps import MapPlotter, plot_maps  # noqa: F401
 from ..tracking import PoseTracker, OneEuro, ConstantVelocity  # noqa: F401

@@ -18,6 +18,7 @@ from .. import pose_metrics
 from .. import pose_nms as pose_nms_stage
 from ..net import KeypointNet
 from . import anonymize_stage
+from . import crops as crops_stage
 from . import draw, jpeg, maps, resample, tta
 from .record import NUM_KEYPOINTS, _ROW, RecordLayout, _no_persons, unpack_record  # noqa: F401 (found here by tests and tools)
 
@@ -162,7 +163,7 @@ _RIDERS = {'track_eval': ('track_metrics', 'TrackEvaluator', 'the evaluator', "s
            'density': ('density', 'DensityMap', 'the map', None)}
 
 
-class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval density trails zones anonymize pose_nms')):
+class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tta track style return_heatmaps track_eval crops density trails zones anonymize pose_nms')):
     """The checked options of one predict_* call (`Detector._options`): the float score threshold; annotate as False, True or
     'jpeg''s (quality, sampling); plot_maps; oks, tta and style as the parts of the key that `_check_groundtruth`, `check_tta`
     and `check_track_style` return, () where the option is off; return_heatmaps; every other field the object of its keyword,
@@ -191,6 +192,8 @@ class _Options(collections.namedtuple('_Options', 'thr annotate plot_maps oks tt
                 key += (st.option, stage.serial if st.tail == 'serial' else stage)
         if self.anonymize is not None:
             key += ('anonymize', self.anonymize)
+        if self.crops is not None:
+            key += ('crops', self.crops)
         return key
 
 
@@ -199,13 +202,13 @@ class _Entry:
     stage, x: the pinned input staging and the device input. host: the pinned result buffers by output name. graph, outs, ver:
     the captured graph, its outputs and the variable versions it last ran with. draw, encode, encode_plan, maps, tta,
     anonymize: the buffers of annotate, plot_maps, flip / scales and anonymize= (draw.Buffers, jpeg.JpegBatchEncoder,
-    maps.MapPlotter, tta.Buffers, anonymize_stage.Anonymizer). style: (TrackStyle, its table on the device). The parts of
+    maps.MapPlotter, tta.Buffers, anonymize_stage.Anonymizer). crops: the buffers of crops= (crops.CropBuffers). style: (TrackStyle, its table on the device). The parts of
     `_STAGES`: oks and nms are buffers of the entry (pose_metrics.OksBuffers, pose_nms.PoseNmsBuffers); track, track_eval,
     zones, trails and density are the caller's objects, whose state the graph reads and writes: the entry keeps them alive.
     layout: the RecordLayout of those parts. sources, meta_stage, meta, work, jpeg: the packed sources, descriptors (with
     their staging), intermediates and JPEG decoder of the ragged paths."""
     __slots__ = ('stage', 'x', 'host', 'graph', 'outs', 'ver', 'draw', 'encode', 'encode_plan', 'maps', 'sources', 'meta_stage',
-                 'meta', 'work', 'jpeg', 'tta', 'style', 'anonymize', 'layout') + tuple(st.part for st in _STAGES)
+                 'meta', 'work', 'jpeg', 'tta', 'style', 'anonymize', 'crops', 'layout') + tuple(st.part for st in _STAGES)
 
     def __init__(self, **buffers):
         for name in self.__slots__:
@@ -375,7 +378,7 @@ class Detector:
     # ------------------------------------------------------------------ batched inference
     def predict_batch(self, images, score_threshold=0.05, return_heatmaps=True, annotate=False, jpeg_quality=75,
                       jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None, flip=False, scales=None, track=None, track_style=None,
-                      pose_nms=None, anonymize=None, density=None, trails=None, zones=None, track_eval=None):
+                      pose_nms=None, anonymize=None, crops=None, density=None, trails=None, zones=None, track_eval=None):
         """The joint graph over a BATCH (create_pb.py:16,53-61,96-109 are written for one), results packed on the device.
 
         Arguments:
@@ -484,13 +487,27 @@ class Detector:
                 alpha 255 (not with track_style). Without the PRN every person takes the fallback region. Every other key is
                 unchanged; `plot_maps` and the returned heatmaps still show the network's input, NOT the anonymised frame.
                 None changes nothing.
+            crops: None, or an inference.PersonCrops (needs the detector; its max_boxes is the Detector's, at most 128): the
+                picture of every kept person, cut from its frame and resized to the spec's size as Pillow's bicubic
+                `resize(box=...)` does it, byte for byte. One mpn_person_crops behind the gather (behind mpn_pose_nms: the
+                survivors) and behind mpn_anonymize inside the captured graph - a graph of its own per PersonCrops - builds the
+                tap tables of every crop on the device from the record's boxes and writes the crops to a buffer of the
+                entry; with format='jpeg' the encoder's two launches follow it there. It reads the frames the drawing reads
+                as its sources - the batch; with anonymize= the ANONYMISED buffer, never the overlays, so that no
+                un-anonymised pixel leaves through this key - and does not need annotate. Every dict gains 'crops' - uint8
+                [n, H, W, 3], or with format='jpeg' a list of n `bytes` - entry i the person i of 'boxes' (the filtered
+                order with pose_nms=), and 'crop_info': 'rect' f64 [n, 4] (x0, y0, x1, y1) in the frame's pixels, 'placed'
+                int32 [n, 4] (top, left, new_h, new_w) inside the crop and 'empty', 'too_large' (a reduction beyond 16x),
+                'clipped' bool [n]; an empty or too large crop is all `fill`. The fixed-size info block arrives with the
+                record; exactly the used crops, or their streams, follow in one more copy. Every other key is unchanged.
+                None changes nothing.
         Returns a list of b dicts, dict i holding what `__call__` returns for image i (the same keys, shapes and dtypes) plus
         'keypoints' [n, 17, 3]: (x, y, score) in image pixels (inference/predict.ipynb, draw_everything, in float32).
         """
         opts, (b, h, w) = self._options(
             lambda: check_batch(images), score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate,
             jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip,
-            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
+            scales=scales, track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density, crops=crops)
         # pinned staging; the frames are the batch itself, so the drawing and encode descriptors are fixed with the entry
         ent = self._entry(opts, (b, h, w, opts.thr) if self.use_graph else ('eager', b, h, w), (b, h, w),
                           lambda: _Entry(stage=torch.empty((b, h, w, 3), dtype=torch.uint8).pin_memory()),
@@ -517,7 +534,7 @@ class Detector:
         returned). given: the keywords the three methods share, as they came (pose_nms, track_eval, density, trails, zones and
         anonymize may be absent: None). shape(): the method's own checks of its images and sizes, run behind those of
         annotate, track_style and plot_maps; what it returns begins with (b, height, width) of the network input. The order
-        behind it: groundtruth, track, flip / scales, pose_nms, track_eval, density, trails, zones, anonymize."""
+        behind it: groundtruth, track, flip / scales, pose_nms, track_eval, density, trails, zones, anonymize, crops."""
         jp = check_annotate(given['annotate'], given['jpeg_quality'], given['jpeg_subsampling'])
         style = check_track_style(given['track_style'], given['annotate'], given['track'])
         plot_maps = check_plot_maps(given['plot_maps'], self._has_heatmaps)
@@ -536,8 +553,9 @@ class Detector:
         trails = self._check_rider('trails', given.get('trails'), given['track'], b, sizes)
         counter = self._check_rider('zones', given.get('zones'), given['track'], b, sizes)
         spec = self._check_anonymize(given.get('anonymize'), given['annotate'], given['track_style'])
+        cut = self._check_crops(given.get('crops'), b)
         return _Options(thr, jp or bool(given['annotate']), plot_maps, oks, tta_key, given['track'], style,
-                        given['return_heatmaps'], evaluator, density, trails, counter, spec, nms), shaped
+                        given['return_heatmaps'], evaluator, cut, density, trails, counter, spec, nms), shaped
 
     def _check_fit(self, keyword, noun, stage, track=None, limits=None):
         """What every stateful stage must share with this Detector, in one order: the streams of the tracker it rides on (where
@@ -596,6 +614,20 @@ class Detector:
         if self.retinanet is None:
             raise ValueError("anonymize= needs the person detector (detector_path): without it no persons are detected")
         anonymize_stage.check_max_boxes(self.params['max_boxes'])
+        return spec
+
+    def _check_crops(self, spec, b):
+        """The `crops` argument of the predict_* methods -> None or the PersonCrops. Before any device work."""
+        if spec is None:
+            return None
+        crops_stage.check_spec(spec)
+        if self.retinanet is None:
+            raise ValueError("crops= needs the person detector (detector_path): without it no persons are detected")
+        if spec.max_boxes != self.params['max_boxes']:
+            raise ValueError(f"crops=: the PersonCrops was made for max_boxes = {spec.max_boxes}, this Detector's is "
+                             f"{self.params['max_boxes']}")
+        if b * spec.max_boxes > 4096:
+            raise ValueError(f"crops=: {b} x {spec.max_boxes} slots are more than mpn_person_crops takes in one launch (4096)")
         return spec
 
     def _check_track_eval(self, evaluator, track, groundtruth, b):
@@ -666,7 +698,8 @@ class Detector:
 
     def _finish(self, ent, outs, b, return_heatmaps):
         """The host side behind the device side of predict_batch / predict_images: the record (and the maps) into pinned
-        memory, one synchronise, the record unpacked into b dicts."""
+        memory, one synchronise, the record unpacked into b dicts. With crops= the info block comes with the record; the used
+        crops follow in a second step (`crops.CropBuffers.collect`), the shape `JpegBatchEncoder.collect` has."""
         copies = [('record', outs.get('record'))]
         if return_heatmaps:
             copies += [('heat', outs['heat']), ('seg', outs['seg'])]
@@ -683,6 +716,8 @@ class Detector:
                 ent.host['annotated'] = torch.empty(outs['annotated'].shape, dtype=torch.uint8).pin_memory()
             nb = ent.draw.out_bytes
             ent.host['annotated'][:nb].copy_(outs['annotated'][:nb], non_blocking=True)
+        if 'crops' in outs:                                         # the fixed-size info block, with the record
+            ent.crops.fetch_info()
         torch.cuda.current_stream(self.net.device).synchronize()
         host = ent.host
         files = ent.encode.collect(ent.encode_plan, outs['encoded']) if 'encoded' in outs else None
@@ -699,6 +734,9 @@ class Detector:
                         p.update(rows)
                     else:
                         p[st.result] = rows
+            if 'crops' in outs:                                     # exactly the used crops (or their streams): one more step
+                for p, (cut, info) in zip(persons, ent.crops.collect([len(p['boxes']) for p in persons])):
+                    p['crops'], p['crop_info'] = cut, info
         else:                                                       # no detector_path: no boxes are detected
             persons = [_no_persons() for _ in range(b)]
         if return_heatmaps:
@@ -745,6 +783,10 @@ class Detector:
             ent.anonymize = anonymize_stage.Anonymizer(b, self.params['max_boxes'], capacity[0], dev, opts.anonymize)
             if fixed_frames:
                 ent.anonymize.place(*_batch_frames(b, h, w))
+        if opts.crops is not None:                                  # the crops, their info block, taps and (jpeg) encoder
+            ent.crops = crops_stage.CropBuffers(b, self.params['max_boxes'], opts.crops, dev)
+            if fixed_frames:
+                ent.crops.place(*_batch_frames(b, h, w))
         if opts.jpeg:                                               # the frames lie where the drawing writes them
             plan = _encode_plan(*_batch_frames(b, h, w), opts.jpeg) if fixed_frames else None
             ent.encode = jpeg.JpegBatchEncoder(dev)
@@ -775,7 +817,8 @@ class Detector:
         Detector" the order): ent.tta - mirrors, extra scales and ONE mpn_tta_merge, whose maps everything below reads;
         ent.maps -> 'maps'; behind the gather the launches that write rows into the one result buffer where `ent.layout` says
         (-> 'record', the whole buffer): pose_nms, whose filtered record every later launch reads, oks, track, track_eval,
-        zones, trails, density; then anonymize, the drawing (mpn_draw_tracks with ent.style), mpn_draw_trails and
+        zones, trails, density; then anonymize, the crops (mpn_person_crops over the frames the drawing reads -> 'crops', with
+        format='jpeg' encoded behind it), the drawing (mpn_draw_tracks with ent.style), mpn_draw_trails and
         mpn_draw_density over its frames in place (-> 'annotated') and the JPEG encode (-> 'encoded' instead). Every launch is
         a pure function of its inputs and the stages' previous state: `_run` may launch twice, the caller commits once."""
         net = self.net
@@ -797,7 +840,7 @@ class Detector:
         dev = {'heat': heat, 'seg': seg}
         if ent.maps is not None:
             dev['maps'] = ent.maps.launch(x, heat, seg, normalise=True)
-        if annotate is not None and frames is None:
+        if (annotate is not None or ent.crops is not None) and frames is None:
             frames = x.view(-1)
         if self.retinanet is None:
             if annotate is not None:                                # no detector: the frames with alpha 255
@@ -850,6 +893,8 @@ class Detector:
             frames = ent.anonymize.launch(frames, record, self.assigner is not None)
             if not ent.anonymize.spec.overlay:
                 drawn = None                                        # (draw.Buffers.no_record: the frames with alpha 255)
+        if ent.crops is not None:                                   # the sources of the drawing, never its overlays
+            dev['crops'] = ent.crops.launch(frames, record)
         if annotate is not None and ent.style is not None:          # identities: mpn_draw_tracks on the rows just written
             style, table = ent.style
             smoothed = whole[layout.track][track.track_bytes(b):] if style.keypoints == 'smoothed' else None
@@ -888,8 +933,8 @@ class Detector:
     # ------------------------------------------------------------------ ragged frames: on-device resize
     def predict_images(self, images, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                        annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, groundtruth=None,
-                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, density=None,
-                       trails=None, zones=None, track_eval=None):
+                       flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None, crops=None,
+                       density=None, trails=None, zones=None, track_eval=None):
         """`predict_batch` for frames as a camera or a dataset delivers them: the resize of inference/predict.ipynb (cell 6:
         Pillow's `image.resize`, antialiased bicubic) runs on the device inside the captured graph, equal to Pillow byte for
         byte, and the persons come back in the coordinates of the SOURCE images (its `draw_everything`).
@@ -921,6 +966,8 @@ class Detector:
             zones: as for `predict_batch`, in the pixels of the SOURCE images, which must all have the counter's frame_size.
             anonymize: as for `predict_batch`; the SOURCE frames are anonymised at their own size. `plot_maps` and the heatmaps
                 still show the network's input.
+            crops: as for `predict_batch`; the persons are cut from the SOURCE frames at their own size (the packed sources;
+                with anonymize= the anonymised ones, never the overlays), 'rect' is in source pixels.
         Returns a list of b dicts with the keys of `predict_batch`: 'boxes' normalised to the source image, 'keypoints'
         (x, y, score) in source pixels; 'scores', 'num_boxes', 'keypoint_scores', 'keypoint_positions' as `predict_batch` gives
         them for the resized batch. A resize that needs more than resample.MAX_KSIZE taps per output (a reduction beyond 16x)
@@ -933,7 +980,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density, crops=crops)
 
         def upload(ent):
             stage = ent.stage.numpy()
@@ -947,7 +994,7 @@ class Detector:
     def predict_jpegs(self, jpegs, size=(640, 640), keep_aspect_ratio=False, score_threshold=0.05, return_heatmaps=False,
                       annotate=False, jpeg_quality=75, jpeg_subsampling='4:2:0', plot_maps=False, entropy='host',
                       groundtruth=None, flip=False, scales=None, track=None, track_style=None, pose_nms=None, anonymize=None,
-                      density=None, trails=None, zones=None, track_eval=None):
+                      crops=None, density=None, trails=None, zones=None, track_eval=None):
         """`predict_images` for frames as a camera or a TFRecord holds them: JPEG bytes. The host runs the marker scan and the
         Huffman decode; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run on the device (mpn_jpeg_decode)
         and write the packed source buffer the resize reads - the bytes Pillow decodes, so every result equals
@@ -965,6 +1012,8 @@ class Detector:
                 for `predict_images` (annotate=True draws on the decoded frames; 'jpeg' also encodes them again on the device).
             groundtruth: as for `predict_images` (source pixels).
             flip, scales, track, track_style, pose_nms, track_eval, zones, anonymize: as for `predict_images`.
+            crops: as for `predict_images`: cut from the decoded frames (with anonymize= the anonymised ones, never the
+                overlays).
         Returns what `predict_images` returns. The decode launches run on the stream ahead of the captured graph, which is the
         one `predict_images` replays: keyed by capacity, not by the batch's sizes.
         """
@@ -983,7 +1032,7 @@ class Detector:
         opts, (_, _, _, items, plan) = self._options(
             shape, score_threshold=score_threshold, return_heatmaps=return_heatmaps, annotate=annotate, jpeg_quality=jpeg_quality,
             jpeg_subsampling=jpeg_subsampling, plot_maps=plot_maps, groundtruth=groundtruth, flip=flip, scales=scales,
-            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density)
+            track=track, track_style=track_style, pose_nms=pose_nms, track_eval=track_eval, anonymize=anonymize, zones=zones, trails=trails, density=density, crops=crops)
         entries = [jpeg.prepare(j, entropy, extended=True) for j in items]
         for e, (h, w) in zip(entries, plan.sizes):
             if tuple(e.shape) != (h, w, 3):
@@ -1011,6 +1060,8 @@ class Detector:
             ent.draw.place(plan.sizes, plan.src_offsets)
         if ent.anonymize is not None:
             ent.anonymize.place(plan.sizes, plan.src_offsets)
+        if ent.crops is not None:
+            ent.crops.place(plan.sizes, plan.src_offsets)
         if eplan:
             self._place_encode(ent, eplan)
         if opts.oks:

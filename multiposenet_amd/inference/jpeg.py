@@ -640,13 +640,18 @@ class JpegBatchEncoder:
         _lib.call("mpn_jpeg_entropy_encode", _lib.ptr(self._coefs), self._coefs.numel(), _lib.ptr(self._descs), self.n,
                   _lib.ptr(self._out), self._out.numel(), _lib.ptr(self._records), _lib.ptr(self._work), self._work.numel(), st)
 
-    def collect(self, plan, sources):
+    def collect(self, plan, sources, count=None):
         """The records, then the bytes used -> the files. Only [offset, offset + size) of every written stream is copied: one
         asynchronous copy per image into a PACKED pinned buffer, then one synchronise (`.copied_bytes`: records + streams). An
-        image that did not fit is fetched as pixels and left to Pillow."""
+        image that did not fit is fetched as pixels and left to Pillow. count: collect the first `count` images of the plan
+        only (a caller whose later images are unused slots); None: all of them."""
         import torch
         stream = torch.cuda.current_stream(self.device)
         n = len(plan.descs)
+        if count is not None:
+            if not 0 <= int(count) <= n:
+                raise ValueError(f"encode: count must be in 0..{n} (got {count})")
+            n = int(count)
         self._record_host[:n * RECORD_BYTES].copy_(self._records[:n * RECORD_BYTES], non_blocking=True)
         stream.synchronize()
         records = self._record_host.numpy().view(RECORD)[:n].copy()

@@ -10,6 +10,7 @@
         [--frames-out DIR [--jpeg-quality 75] [--label-size 10] [--draw-smoothed] [--hide-untracked]]
         [--anonymize [head|box] [--anonymize-mode pixelate|blur|fill] [--anonymize-shape ellipse|rectangle] [--anonymize-blocks 8]
         [--anonymize-radius 8] [--anonymize-no-overlay]]
+        [--crops-out DIR [--crop-size H W] [--crop-pad P] [--crop-fit stretch|pad] [--crop-quality Q]]
         [--annotations JSON [--eval-threshold 0.5]]
         [--zones FILE.json]
         [--trails [LENGTH] [--trail-every N] [--trail-max-gap N] [--trail-anchor feet|box_bottom|box_centre] [--no-trail-fade]
@@ -37,7 +38,10 @@ DIR/<name>.jpg with its persons drawn on it - box, keypoints and an id label in 
 the device in the same graph ('annotated_jpeg'); the JSON lines are the same with and without it. --anonymize (with
 --frames-out) makes every detected person unrecognisable in those frames first (`anonymize=`, an `inference.Anonymize`: one more
 stage in the same graph; the head by default, or the whole box; --anonymize-no-overlay writes the anonymised frames without
-boxes, skeletons and ids; the class's defaults are not tuned). --annotations JSON (a
+boxes, skeletons and ids; the class's defaults are not tuned). --crops-out DIR writes the picture of every detected person as
+DIR/<frame name>_<k>.jpg, or DIR/<frame name>_id<track id>.jpg when the person has an id (`crops=`, an `inference.PersonCrops`
+with format='jpeg': cut, resized and JPEG-encoded on the device in the same graph; the bytes are written as they arrive, not
+encoded again on the host; with --anonymize the crops show the anonymised frames). --annotations JSON (a
 COCO-style file whose annotations carry `track_id`, PoseTrack's layout; frames are found by the base name of `file_name`, a frame
 the file does not name has no annotated person) scores the identities while it tracks (`track_eval=`, a
 `track_metrics.TrackEvaluator`: one more launch in the same graph; a pair can correspond at OKS >= --eval-threshold) and adds
@@ -152,8 +156,10 @@ def main(argv=None):
                     help="write the final dwell and visits planes and the cell size (--density)")
     from . import pose_nms
     from .inference import anonymize_stage
+    from .inference import crops as crops_stage
     pose_nms.add_arguments(ap)
     anonymize_stage.add_arguments(ap)
+    crops_stage.add_arguments(ap)
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
@@ -252,6 +258,9 @@ def main(argv=None):
             counter = ZoneCounter(streams=1, max_boxes=det.params['max_boxes'], **spec)
         except ValueError as e:
             ap.error(str(e))
+    cut = crops_stage.from_arguments(ap, args, det.params['max_boxes'])
+    if cut is not None:
+        os.makedirs(args.crops_out, exist_ok=True)
     trails = density = None
     nobody = {'keypoints': np.zeros((0, 17, 3)), 'boxes': np.zeros((0, 4)), 'track_ids': np.zeros(0, np.int64)}
     frames = persons = 0
@@ -291,6 +300,8 @@ def main(argv=None):
                     ap.error(str(e))
             if trails is not None:
                 scored["trails"] = trails
+            if cut is not None:
+                scored["crops"] = cut
             if all(_is_jpeg(data) for data in files):
                 outs = det.predict_jpegs(files, size=size, score_threshold=args.score_threshold, track=tracker, pose_nms=nms,
                                         **draw, **scored)
@@ -331,6 +342,10 @@ def main(argv=None):
                 if draw:
                     with open(os.path.join(args.frames_out, os.path.splitext(name)[0] + ".jpg"), "wb") as f:
                         f.write(o["annotated_jpeg"])
+                if cut is not None:                                 # the device's bytes, as they are
+                    for file_name, data in zip(crops_stage.crop_file_names(name, o["track_ids"], len(o["crops"])), o["crops"]):
+                        with open(os.path.join(args.crops_out, file_name), "wb") as f:
+                            f.write(data)
                 persons += len(o["track_ids"])
             frames += len(batch)
     state = tracker.tracks(0)
